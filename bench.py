@@ -2,6 +2,8 @@
 """bench.py - forward throughput of the Multi-ATGCN hot path on MI355X (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs    # + the last step's prediction
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                          # + every side line below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,7 +15,11 @@ collective (forward needs none), so scaling is weak: value = all ranks' B*T*N no
 time.  Parameter-only work (support stack, node-adaptive weights: matgcn_prepare) is redone inside
 every timed step, as the reference redoes it in every forward.
 
-Rank 0 prints ONE JSON line.  Two extra objects:
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set up, warm up, time the K steps
+and print `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (one timed step, in ms) and the
+configuration.  --dump-outputs DIR also writes what the last timed step returned to its caller, as DIR/pred.npy (float32,
+(B, out, N, 1); DIR/pred_rank<r>.npy for the other ranks' shards); the inputs are seeded, so two builds can be compared
+output for output.  Everything else is measured only with --full, and adds these objects to the line:
   roofline     - the dominant kernel (k_mix, the graph-mix GEMM): algorithmic FLOPs per launch divided by
                  its average launch duration measured with HIP events in situ, on the stream it is launched
                  on, against the dense fp32 MFMA peak.  The timed steps run the layers' chains as a
@@ -31,6 +37,8 @@ Rank 0 prints ONE JSON line.  Two extra objects:
                  p10, p90.  `value` stays the driver's contract (K steps between two barriers).
   cpu_baseline - the CPU oracle in its reference-faithful order (oracle/, kind "port"), timed on this
                  host's cores on the same workload (rank 0, N=1 only).
+  and mae_at_12, frozen_weights, bf16_variant, train_step (with its own CPU baseline) and batch16, each
+  described where it is measured below; --no-* switch single ones off.
 """
 import argparse
 import datetime
@@ -383,6 +391,26 @@ def small_batch_times(w, device, batch=16, seed=0, iters=30, steps=10):
                     "inside), and the wall per step of a free-running loop"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all ranks' files together
+
+
+def dump_outputs(dirname, name, arr, world):
+    """np.save(DIR/<name>.npy) of one rank's output in float32.  Above this rank's share of DUMP_LIMIT_BYTES only every
+    s-th sample (leading axis, from sample 0) is written, s the smallest stride that fits: a fixed sample."""
+    import numpy as np
+    arr = np.ascontiguousarray(arr, dtype=np.float32)
+    share = DUMP_LIMIT_BYTES // world
+    row_bytes = arr.nbytes // max(1, arr.shape[0])
+    stride = 1
+    while -(-arr.shape[0] // stride) * row_bytes > share:
+        stride += 1
+    if stride > 1:
+        arr = np.ascontiguousarray(arr[::stride])
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), arr)
+    return {"file": name + ".npy", "shape": list(arr.shape), "dtype": "float32", "sample_stride": stride}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -402,7 +430,14 @@ def main():
     ap.add_argument("--serial-streams", action="store_true",
                     help="run the timed steps too with the layer wavefront off (one stream): the configuration the "
                          "kernel roofline is measured in; used for the rocprofv3 profile that must agree with it")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too (roofline, median protocol, bf16 variant, frozen "
+                         "weights, training step, batch-16 line, CPU baselines); a plain run times the K steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's prediction as DIR/pred.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -466,10 +501,15 @@ def main():
             pred = model.predict(batch)
         sync_all()
         elapsed = time.perf_counter() - t0
+    # the last timed step's prediction, copied before any later forward reuses its buffer
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, "pred" if rank == 0 else "pred_rank%d" % rank,
+                              pred.detach().cpu().numpy(), world)
     # the same loop with matgcn_prepare cached (weights frozen between forwards - what inference serving does and
     # what the plugin class does by default); reported beside the headline, never as `value`
     frozen_elapsed = None
-    if not args.cache_prepared:
+    if args.full and not args.cache_prepared:
         model.cache_prepared = True
         with torch.no_grad():
             model.predict(batch)
@@ -482,7 +522,7 @@ def main():
         model.cache_prepared = False
     # SURVEY.md 8d protocol: >= 20 warm-up, >= 100 forwards, every one between two HIP events, median
     median = None
-    if args.median > 0:
+    if args.full and args.median > 0:
         with torch.no_grad():
             for _ in range(args.median_warmup):
                 model.predict(batch)
@@ -501,7 +541,7 @@ def main():
     # BASELINE config 3's dtype as a side line: bf16 operands for the graph mixes (fp32 accumulate, fp32 state);
     # never `value` - narrower than the reference's fp32 - and with its own error figure against the fp32 path
     bf16_variant = None
-    if rank == 0 and not args.no_bf16_variant:
+    if args.full and rank == 0 and not args.no_bf16_variant:
         from multistgraph_amd import _lib
         lib = _lib.load()
         notes = {1: "matgcn_set_mix_precision(1): the graph mixes round their operands (support stack, state rows) to "
@@ -545,6 +585,23 @@ def main():
 
     result = None
     if rank == 0:
+        build_id = mbuild.source_id()
+        result = {
+            "metric": "forward node-steps/s (B*T*N per second), MultiATGCN.predict",
+            "value": value, "unit": "node-steps/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": w["desc"], "nodes": w["nodes"], "per_gpu_batch": w["batch"],
+                       "global_batch": w["batch"] * world, "in_steps": 24, "out_steps": w["out"],
+                       "parallelism": "batch shards, no data-path collective (dp%d)" % world,
+                       "prepare_in_timed_region": not args.cache_prepared,
+                       "layer_wavefront_streams": not args.serial_streams},
+            "build_id": build_id,
+            "full": bool(args.full),
+        }
+        if dumped is not None:
+            result["outputs"] = dumped
+    if args.full and rank == 0:
         flops_unit = algorithmic_flops_per_unit(w["nodes"], out=w["out"])
         fwd_tflops = flops_unit * w["batch"] * 24 * w["nodes"] / (ms_per_step * 1e-3) / 1e12
         n, b, h = w["nodes"], w["batch"], 64
@@ -555,7 +612,6 @@ def main():
         ks = (spec.n_first - n_diag) * (spec.cheb_k - 1)
         mix_flops = 2.0 * ks * n * n * b * h                       # executed = algorithmic of the dense slots, unpadded
 
-        build_id = mbuild.source_id()
         serial = in_situ_kernel_times(model, batch, wavefront=False, forwards=2)
         conc = in_situ_kernel_times(model, batch, wavefront=True, forwards=1)
         step_mix = serial.get("k_mix", [])       # k_mix<1>: the 96 per-step launches of each forward
@@ -631,20 +687,8 @@ def main():
         ytrue = batch["y"][..., 0:1].clone()
         from multistgraph_amd.model import masked_mae
         mae12 = float(masked_mae(pred[:, min(12, w["out"]) - 1], ytrue[:, min(12, w["out"]) - 1]).item())
-        result = {
-            "metric": "forward node-steps/s (B*T*N per second), MultiATGCN.predict",
-            "value": value, "unit": "node-steps/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": w["desc"], "nodes": w["nodes"], "per_gpu_batch": w["batch"],
-                       "global_batch": w["batch"] * world, "in_steps": 24, "out_steps": w["out"],
-                       "parallelism": "batch shards, no data-path collective (dp%d)" % world,
-                       "prepare_in_timed_region": not args.cache_prepared,
-                       "layer_wavefront_streams": not args.serial_streams},
-            "mae_at_12": mae12,
-            "build_id": build_id,
-            "roofline": roofline,
-        }
+        result["mae_at_12"] = mae12
+        result["roofline"] = roofline
         if median is not None:
             result["median"] = median
         if bf16_variant is not None:
@@ -700,7 +744,7 @@ def main():
                 cpu_train = cpu_train_baseline(w, x_np, y_np, snapshot, df)
                 result["train_step"]["cpu_baseline"] = cpu_train
                 result["train_step"]["gpu_over_cpu"] = result["train_step"]["node_steps_per_s"] / cpu_train["value"]
-    if distributed and not args.no_train_step:
+    if distributed and args.full and not args.no_train_step:
         # every rank takes part (the gradient all-reduce is a collective); rank 0 reports
         try:
             ts = train_step_times(model, batch, w, world=world, device=device, ctl=ctl_group, do_exchange=True)

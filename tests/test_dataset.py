@@ -2,22 +2,20 @@
 device-resident series.
 
 CPU: (i) the core against brute-force windows (scaler statistics with multiplicity, split, padding, loader tables);
-(ii) the Batch contract the executor relies on; (iii) - build container only - the reference's OWN MTHDataset on a
-synthetic set of atomic files against MTHDatasetResident on the same files: scaler, data_feature, and every window /
-label of the test loader and of the (same-seed shuffled) train loader bit for bit.
+(ii) the Batch contract the executor relies on; (iii) the reference's OWN MTHDataset on a synthetic set of atomic files
+(recorded in tests/golden/reference_mth_dataset_dyn*.npz) against the plugin's get_data on the same files: scaler,
+data_feature, and every window / label of the test loader and of the (same-seed shuffled) train loader bit for bit.
 GPU: one epoch over the resident loaders through the plugin class = the window path vs the oracle."""
-import importlib
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import Case, max_norm_err
+from helpers import GOLDEN_DIR, Case, max_norm_err
+from multistgraph_amd import dataset as D
 from multistgraph_amd import windows as W
 
-REFERENCE_ROOT = "/root/reference"
 KW = dict(input_window=24, output_window=12, len_closeness=2, len_period=1, len_trend=1, interval_period=2,
           interval_trend=5, train_rate=0.7, eval_rate=0.15, batch_size=8)
 
@@ -121,7 +119,7 @@ def test_resident_batch_is_batch_compatible_and_refuses_the_host():
         ResidentSeries(_series(steps=100), **KW)  # too short for the trend head (mth_dataset.py:134-137)
 
 
-# ---- against the reference's own MTHDataset on synthetic atomic files (build container only) --------------------------
+# ---- against the reference's own MTHDataset on synthetic atomic files (recorded) -----------------------------------------
 def _write_atomic_files(root, name, steps, n, seed):
     """a LibCity dataset directory: .geo / .rel / .dyna / .ext / .gbst in the format data_prepare/1.3*.py writes"""
     import pandas as pd
@@ -154,62 +152,75 @@ class _Config(dict):
     """ConfigParser-shaped: get / [] / []= / in (libcity/config/config_parser.py:134-151)"""
 
 
+class _ReferenceShell:
+    """What the reference's MTHDataset leaves for the plugin's get_data: its constructor's attributes and its ETL
+    (_load_dyna + _add_external_information: the (T, N, F) series), replayed from the fixture.  The plugin's own methods
+    (_raw_series, get_data) run on it unchanged, as they do on an MTHDatasetResident inside a LibCity checkout."""
+    _raw_series = D.MTHDatasetResident._raw_series
+    get_data = D.MTHDatasetResident.get_data
+
+    def __init__(self, attrs, etl):
+        self.__dict__.update(attrs)
+        self._etl = list(etl)
+        self.ext_loaded = False
+
+    def _load_ext(self):
+        self.ext_loaded = True
+        return "ext"
+
+    def _load_dyna(self, filename):
+        return filename
+
+    def _add_external_information(self, df, ext_data=None):
+        assert ext_data == "ext"
+        return self._etl[self.data_files.index(df)]
+
+
 @pytest.mark.parametrize("load_dynamic", [False, True])
 def test_resident_dataset_equals_the_reference_dataset(tmp_path, monkeypatch, load_dynamic):
-    if not os.path.isdir(os.path.join(REFERENCE_ROOT, "libcity")):
-        pytest.skip("reference checkout not present (GPU box): the dataset comparison runs in the build container")
-    sys.dont_write_bytecode = True
-    if REFERENCE_ROOT not in sys.path:
-        sys.path.append(REFERENCE_ROOT)
-    if not hasattr(np, "float"):      # the reference was written against numpy < 1.24 (traffic_state_datatset.py:284)
-        monkeypatch.setattr(np, "float", float, raising=False)
-    from libcity.data.dataset.dataset_subclass.mth_dataset import MTHDataset
-    import multistgraph_amd.dataset as D
-    D = importlib.reload(D)           # pick up the reference base class if the module was imported without it
-    assert issubclass(D.MTHDatasetResident, MTHDataset)
+    """tests/golden/reference_mth_dataset_dyn{0,1}.npz hold what the reference's own MTHDataset made of the atomic files
+    _write_atomic_files writes (seed 11, 6 nodes): its constructor's attributes, the series its ETL cut the windows from,
+    its data_feature, and every window / label of its test loader and of its train / eval loaders shuffled after
+    torch.manual_seed(123) / (7).  The plugin's get_data runs on that series and the same files, and must give the same
+    data_feature and the same batches bit for bit.
+    The reference's config: pad_with_last_sample = False, because the reference pads with np.repeat over a list of ragged
+    (x, y) tuples (data/utils.py:53-61), which numpy >= 1.24 refuses; the padding rule itself is pinned to the reference's
+    function on index arrays by tests/golden/windows_small.npz (tests/test_windows.py)."""
+    import json
+    import pandas as pd
+    gold = np.load(os.path.join(GOLDEN_DIR, "reference_mth_dataset_dyn%d.npz" % int(load_dynamic)))
+    attrs = json.loads(str(gold["attrs_json"]))
+    rf = json.loads(str(gold["feature_json"]))
     name = "SYNTH_SG"
     _write_atomic_files(str(tmp_path), name, steps=24 * 5 + 24 * 2 + 130, n=6, seed=11)
-    monkeypatch.chdir(tmp_path)       # the reference reads ./raw_data/<dataset>/ and writes ./libcity/cache/
-    # pad_with_last_sample = False here: the reference pads with np.repeat over a list of ragged (x, y) tuples
-    # (data/utils.py:53-61), which numpy >= 1.24 refuses; the padding rule itself is pinned to the reference's function on
-    # index arrays by tests/golden/windows_small.npz (tests/test_windows.py)
-    cfg = dict(dataset=name, batch_size=8, cache_dataset=False, num_workers=0, pad_with_last_sample=False, train_rate=0.7,
-               eval_rate=0.15, scaler="standard", ext_scaler="none", load_external=True, load_dynamic=load_dynamic,
-               normal_external=False, add_time_in_day=True, add_day_in_week=False, input_window=24, output_window=12,
-               use_3tu=True, groupstd=True, add_static=False, len_closeness=2, len_period=1, len_trend=1,
-               interval_period=2, interval_trend=5, hour_each_day=24, data_col=["Visits"], weight_col="link_weight",
-               ext_col=["holiday", "weekend", "temp"], data_files=[name], geo_file=name, rel_file=name, ext_file=name,
-               output_dim=1, time_intervals=3600, init_weight_inf_or_zero="zero", set_weight_link_or_dist="dist",
-               calculate_weight_adj=False)
-    ref = MTHDataset(_Config(cfg))
-    ref_loaders = ref.get_data()
-    # the registry change of INTEGRATION.md (one import line in dataset_subclass/__init__.py), then the reference's own
-    # resolver: get_dataset looks config['dataset_class'] up by name (libcity/data/utils.py:10-28)
-    import libcity.data.dataset.dataset_subclass as sub
-    from libcity.data.utils import get_dataset
-    monkeypatch.setattr(sub, "MTHDatasetResident", D.MTHDatasetResident, raising=False)
-    mine = get_dataset(_Config(dict(cfg, dataset_class="MTHDatasetResident")))
-    assert type(mine) is D.MTHDatasetResident
+    monkeypatch.chdir(tmp_path)       # the reference's data_path is ./raw_data/<dataset>/
+    mine = _ReferenceShell(attrs, [gold["etl_%d" % i] for i in range(int(gold["n_series"]))])
     my_loaders = mine.get_data()
-    rf, mf = ref.get_data_feature(), mine.get_data_feature()
-    assert set(rf) == set(mf)
+    assert mine.ext_loaded
+    mf = dict(num_nodes=mine.num_nodes, feature_dim=mine.feature_dim, output_dim=mine.output_dim, ext_dim=mine.ext_dim,
+              len_closeness=mine.len_closeness * mine.input_window, len_period=mine.len_period * mine.input_window,
+              len_trend=mine.len_trend * mine.input_window, num_batches=mine.num_batches)
     for k in ("num_nodes", "feature_dim", "output_dim", "ext_dim", "len_closeness", "len_period", "len_trend",
               "num_batches"):
         assert rf[k] == mf[k], k
-    assert np.array_equal(rf["adj_mx"], mf["adj_mx"]) and rf["static"] is None and mf["static"] is None
-    assert rf["ct_visit_mstd"].equals(mf["ct_visit_mstd"]) and rf["coordinate"].equals(mf["coordinate"])
-    assert abs(rf["scaler"].mean - mf["scaler"].mean) <= 1e-12 * abs(rf["scaler"].mean)
-    assert abs(rf["scaler"].std - mf["scaler"].std) <= 1e-12 * rf["scaler"].std
+    assert rf["static_is_none"] and mine.static is None
+    for tab in ("ct_visit_mstd", "coordinate"):
+        got = getattr(mine, tab)
+        assert list(got.columns) == list(gold["%s_columns" % tab]), tab
+        assert [str(t) for t in got.dtypes] == list(gold["%s_dtypes" % tab]), tab
+        for j, col in enumerate(got.columns):
+            v = got[col].to_numpy()
+            assert np.array_equal(v.astype(str) if v.dtype == object else v, gold["%s_col%d" % (tab, j)]), (tab, col)
+        assert isinstance(got, pd.DataFrame) and list(got.index) == list(range(len(got)))
+    assert abs(rf["scaler_mean"] - mine.scaler.mean) <= 1e-12 * abs(rf["scaler_mean"])
+    assert abs(rf["scaler_std"] - mine.scaler.std) <= 1e-12 * rf["scaler_std"]
     assert mf["feature_dim"] == (5 if load_dynamic else 2)
     host, rel, out = mine.core.series_host.numpy(), mine.core.rel, 12
     for which, seed in ((2, None), (0, 123), (1, 7)):       # test (in order), train and eval (shuffled by torch's RNG)
-        assert len(ref_loaders[which]) == len(my_loaders[which])
-        if seed is not None:
-            torch.manual_seed(seed)
-        ref_batches = []
-        for b in ref_loaders[which]:
-            b.to_tensor(torch.device("cpu"))
-            ref_batches.append((b["X"].numpy(), b["y"].numpy()))
+        lens = gold["lens_%d" % which]
+        assert len(lens) == len(my_loaders[which])
+        ends = np.cumsum(lens)
+        ref_batches = [(gold["X_%d" % which][e - m:e], gold["y_%d" % which][e - m:e]) for m, e in zip(lens, ends)]
         if seed is not None:
             torch.manual_seed(seed)
         for (rx, ry), b in zip(ref_batches, my_loaders[which]):

@@ -18,11 +18,11 @@ if [ "$PART" = "tests" ] || [ "$PART" = "bench" ]; then
   fi
   python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
   echo "smoke rc=$?"; tail -2 $O/smoke.log
-  python bench.py > $O/bench.json 2> $O/bench.err
+  python bench.py --full > $O/bench.json 2> $O/bench.err
   echo "bench rc=$?"
-  python bench.py --workload dc237 > $O/bench_dc237.json 2> $O/bench_dc237.err
+  python bench.py --full --workload dc237 > $O/bench_dc237.json 2> $O/bench_dc237.err
   echo "bench dc237 rc=$?"
-  python bench.py --workload synth4096 --steps 3 --warmup 1 --median 5 --median-warmup 1 > $O/bench_synth4096.json 2> $O/bench_synth4096.err
+  python bench.py --full --workload synth4096 --steps 3 --warmup 1 --median 5 --median-warmup 1 > $O/bench_synth4096.json 2> $O/bench_synth4096.err
   echo "bench 4096 rc=$?"
   python tools/host_enqueue_time.py bm403 5 > $O/host_enqueue.log 2>&1
   tail -2 $O/host_enqueue.log
@@ -37,7 +37,7 @@ else
   echo "pmc train rc=$?"; head -24 gpurun_out/pmc_train_$TAG/train_pmc_kernels.txt
   bash tools/profile_train.sh $TAG > $O/profile_train.log 2>&1
   echo "profile train rc=$?"
-  python bench.py --no-cpu-baseline > $O/bench_after_pmc.json 2> $O/bench_after_pmc.err
+  python bench.py --full --no-cpu-baseline > $O/bench_after_pmc.json 2> $O/bench_after_pmc.err
   echo "bench (PMC of this build replayed) rc=$?"
 fi
 python - $O <<'PY'

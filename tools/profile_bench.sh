@@ -9,8 +9,8 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/default -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/default.json 2> $OUT/default.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/serial -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --serial-streams > $OUT/serial.json 2> $OUT/serial.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/default -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/default.json 2> $OUT/default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/serial -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --serial-streams > $OUT/serial.json 2> $OUT/serial.err
 echo "[profile] stats done" | tee -a $OUT/progress.log
 # (HBM traffic counters: tools/pmc_traffic.sh - FETCH_SIZE and WRITE_SIZE need separate passes)
 find $OUT -name "*.csv" | head -20

@@ -4,7 +4,7 @@
 set -o pipefail
 mkdir -p gpurun_out/rehearse
 MATGCN_BENCH_ONE_DEVICE=1 MATGCN_BENCH_BACKEND=gloo timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --median 10 --median-warmup 2 \
+  --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 5 --warmup 2 --median 10 --median-warmup 2 \
   > gpurun_out/rehearse/bench_2rank.json 2> gpurun_out/rehearse/bench_2rank.err
 echo "rc=$?"; tail -c 400 gpurun_out/rehearse/bench_2rank.err
 python - <<'PY'

@@ -5,7 +5,7 @@
 set -o pipefail
 mkdir -p gpurun_out/rehearse
 MATGCN_BENCH_FORCE_DIST=1 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-  --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 1 --steps 5 --warmup 2 --median 10 --median-warmup 2 --no-cpu-baseline --no-batch16 \
+  --master-addr 127.0.0.1 --master-port 29512 bench.py --full --gpus 1 --steps 5 --warmup 2 --median 10 --median-warmup 2 --no-cpu-baseline --no-batch16 \
   > gpurun_out/rehearse/bench_rccl_1rank.json 2> gpurun_out/rehearse/bench_rccl_1rank.err
 echo "rc=$?"; tail -c 400 gpurun_out/rehearse/bench_rccl_1rank.err
 python - <<'PY'
