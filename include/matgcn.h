@@ -23,8 +23,10 @@
  * ABI 10 (round 3) over ABI 9: matgcn_metric_sums / matgcn_metric_table (the evaluator's table and the group-std
  * re-transform on the device), matgcn_series_violations (range contract of the series entry points: rows are clamped
  * and counted, never read out of bounds), matgcn_set_mix_precision(2) (bf16 operands for the node-wise contractions),
- * matgcn_set_batch_split, matgcn_set_lazy_prepare / matgcn_prepare_join; matgcn_workspace_bytes also covers two
+ * a batch-split forward switch, matgcn_set_lazy_prepare / matgcn_prepare_join; matgcn_workspace_bytes also covers two
  * half-batch plans and the bf16 copies of the weight streams.  No signature of ABI 9 changed.
+ * ABI 12 over ABI 11: the batch-split forward switch and the lab schedule matgcn_set_wavefront(2) are removed (any
+ * non-zero value now selects the wavefront); matgcn_workspace_bytes no longer counts two half-batch plans.
  */
 #ifndef MATGCN_H
 #define MATGCN_H
@@ -36,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MATGCN_ABI_VERSION 11
+#define MATGCN_ABI_VERSION 12
 
 typedef enum matgcn_status {
   MATGCN_OK = 0,
@@ -348,9 +350,8 @@ int matgcn_debug_gemm(const float* A, const float* B, float* C, const int64_t* d
  * first use; forked from and joined back into the caller's stream with events, so the caller still sees one
  * in-order stream).  matgcn_set_wavefront(0) serialises everything on the caller's stream instead - same kernels,
  * same results; used to time one kernel alone.  (A lock-step pairing of the chains through per-kernel events was
- * measured and rejected: the cross-stream waits cost more than the pairing gains.)  Returns the previous setting.
- * matgcn_set_wavefront(2) is a lab switch (round 4, measured and rejected: 8.3 against 6.8 ms): the graph mixes of all
- * chains form one global order so that a mix only ever runs beside the other chain's node kernel; same results. */
+ * measured and rejected: the cross-stream waits cost more than the pairing gains.)  Any non-zero value selects the
+ * wavefront.  Returns the previous setting. */
 int matgcn_set_wavefront(int enabled);
 
 /* Hardware queues.  The HIP runtime maps the streams of a process onto GPU_MAX_HW_QUEUES (default 4) hardware queues per
@@ -379,15 +380,6 @@ int matgcn_set_stream_pool(int own);
  * Both return MATGCN_OK / the previous setting. */
 int matgcn_set_lazy_prepare(int enabled);
 int matgcn_prepare_join(void* stream);
-
-/* matgcn_set_batch_split(2): the inference forwards (matgcn_forward, matgcn_forward_series) run the two halves of an
- * even batch as two independent forwards of B / 2 samples side by side - half 0 on the caller's stream, half 1 on a
- * library stream, each with its own layer wavefront and its own half of the workspace - and join them before the call's
- * last event.  The samples of a batch never interact (MultiATGCN.py:363-420), so the result is that of two forwards of
- * B / 2: the same kernels, the same arithmetic per sample.  Needs the wavefront on, fp32 operands and a workspace that
- * holds two B / 2 plans (matgcn_workspace_bytes of the full batch does); otherwise the plain forward runs.  0 / 1: off
- * (default).  Returns the previous setting. */
-int matgcn_set_batch_split(int parts);
 
 /* ---- precision option (BASELINE config 3's dtype; a side line, never the headline) -----------------------------
  * matgcn_set_mix_precision(1): the graph mixes of matgcn_forward / matgcn_forward_series round their operands - the

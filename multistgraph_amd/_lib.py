@@ -11,7 +11,7 @@ import os
 
 import torch  # noqa: F401  (loads the HIP runtime the library binds to)
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 MAX_LAYERS = 4
 MAX_HEADS = 8
 MAX_EXT = 16
@@ -20,8 +20,6 @@ ADP_NONE, ADP_UNI, ADP_BI = 0, 1, 2
 ADP_CODES = {"none": ADP_NONE, "unidirection": ADP_UNI, "bidirection": ADP_BI}
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmatgcn.so")
-if os.environ.get("MATGCN_LIB"):   # lab builds of the same library (build.build_variant); still HIP-only, still loud
-    LIB_PATH = os.path.abspath(os.environ["MATGCN_LIB"])
 
 
 class MatgcnError(RuntimeError):
@@ -113,7 +111,6 @@ _SIGNATURES = {
     "matgcn_set_wavefront": (C.c_int, [C.c_int]),
     "matgcn_set_stream_pool": (C.c_int, [C.c_int]),
     "matgcn_set_mix_precision": (C.c_int, [C.c_int]),
-    "matgcn_set_batch_split": (C.c_int, [C.c_int]),
     "matgcn_set_lazy_prepare": (C.c_int, [C.c_int]),
     "matgcn_prepare_join": (C.c_int, [_P]),
     "matgcn_profile_enable": (C.c_int, [C.c_int, C.c_int]),

@@ -267,7 +267,6 @@ int adaptive_grad(const Bwd& b, const float* dA, const float* U, int rows, int C
   const int S = b.c.R.S;
   for (int j = 0; j < P.per; ++j) {
     const size_t slot = nodeMajor ? (size_t)(1 + j) * P.Np * rows * Cc : (size_t)(1 + j) * P.Np * Cc;
-#ifndef ADJ_LAB_GENERIC
     if (!nodeMajor && Cc == H && rows >= 8) {   // both operands in 256-byte node rows: the dedicated kernel (k_adj_grad)
       AdjGradArgs q;
       q.A = dA + slot; q.B = U; q.aStride = (long)S * P.Np * H; q.bStride = (long)P.Np * H;
@@ -281,7 +280,6 @@ int adaptive_grad(const Bwd& b, const float* dA, const float* U, int rows, int C
       CHECK_LAUNCH();
       continue;
     }
-#endif
     if (nodeMajor && Cc == 2 && rows % 8 == 0) {   // layer 0's two-channel x part: dedicated small kernel
       const unsigned t32 = (unsigned)((P.N + 31) / 32);
       hipLaunchKernelGGL(k_adj_grad_narrow2, dim3(t32, t32, 2), dim3(256), 0, b.c.s, dA + slot, U, rows, P.N, P.Np, 2,
@@ -366,9 +364,6 @@ struct LayerBufs {
   [[maybe_unused]] float* DH = tr + R.oDH[par]; [[maybe_unused]] float* DHa = tr + R.oDHa[par];                     \
   [[maybe_unused]] float* TMP = tr + R.oTmp[par]; [[maybe_unused]] float* MixOut = tr + R.oMixOut[par]
 
-#ifndef CHAIN_FUSE_RES_NODE
-#define CHAIN_FUSE_RES_NODE 1   // 0: round 3's pair k_chain_res_fused + k_chain_node<false, 64> (A/B builds)
-#endif
 // scratch and outputs start from zero (only what is accumulated into, or what the GEMMs leave untouched)
 int bwd_clear(Pass& pass) {
   PASS_LOCALS(pass);
@@ -400,8 +395,8 @@ int bwd_clear(Pass& pass) {
                        dim3(256), 0, s, bufs, rowsTB * S, N, Np, H);
     CHECK_LAUNCH();
   }
-  if (CHAIN_FUSE_RES_NODE && !P.gcnOff) RETURN_IF(zero_async(tr + R.oZeroSlab, slab, s));
-  if (CHAIN_FUSE_RES_NODE && Np != N && !P.gcnOff) {
+  if (!P.gcnOff) RETURN_IF(zero_async(tr + R.oZeroSlab, slab, s));
+  if (Np != N && !P.gcnOff) {
     // k_chain_res_node writes the rows of the real nodes only; DPU2 / DPG2 are summed over ALL rows by the residual
     // nn.Linear gradients (column sums, weight GEMMs): the rows of the padding nodes must read as zero
     for (int q = 0; q < (P.L > 1 ? 2 : 1); ++q) {
@@ -676,7 +671,7 @@ int bwd_chain(Pass& pass, const LayerBufs& L) {
     memset(&cn, 0, sizeof(cn));
     cn.c = a; cn.I = I; cn.iOfs = C; cn.rows = B; cn.N = N; cn.Np = Np; cn.S = S;
     const dim3 ngrid((unsigned)((B + 63) / 64), (unsigned)N);
-    const bool fused = CHAIN_FUSE_RES_NODE && a.mixParts <= 4;
+    const bool fused = a.mixParts <= 4;
     if (fused && !a.hprev) { a.hprev = tr + R.oZeroSlab; cn.c.hprev = a.hprev; }
     if (fused) {
       // blend + residual cell + graph-cell output algebra of step t, the carry of step t+1, and the update block's node
@@ -1278,10 +1273,8 @@ int backward_impl(Bwd& b, const float* dOut) {
   q.xs = q.twoStreams ? g_wf.xcol : q.s;
   q.bx = b;
   q.bx.c.s = q.xs;
-#ifndef BX_CHUNKS
-#define BX_CHUNKS 4   // x-column chunks per sequence (lab switch; 2 / 8 / 12 measured: 16.3-16.4 / 16.4 / 16.2 ms against 16.1)
-#endif
-  q.chunk = P.T >= 8 ? (P.T + BX_CHUNKS - 1) / BX_CHUNKS : P.T;
+  // 4 x-column chunks per sequence (2 / 8 / 12 measured: 16.3-16.4 / 16.4 / 16.2 ms against 16.1)
+  q.chunk = P.T >= 8 ? (P.T + 4 - 1) / 4 : P.T;
 
   LayerBufs LB[MATGCN_MAX_LAYERS];
   int cur = 0;   // which of the two sequence-gradient buffers holds the gradient of the current layer's output

@@ -45,10 +45,8 @@ struct GemmArgs {
 // the LDS-active cycles as conflicts).  The fragment reads (k = 4 s + kq: the term is 8 * (s & 3), wave-uniform; kq = 0 / 1
 // of a half differ by one row = 16 banks) stay conflict-free.
 #define BG_SWZ(k) ((((k) >> 2) & 3) << 3)
-#ifndef BG_KH
-#define BG_KH 1    // 16-wide K halves per staged tile (2 was measured: no gain at the backward's shapes, twice the LDS)
-#endif
-#define BG_KT (16 * BG_KH)
+constexpr int BG_KH = 1;   // 16-wide K halves per staged tile (2 was measured: no gain at the backward's shapes, twice the LDS)
+constexpr int BG_KT = 16 * BG_KH;
 
 // ROLE only names the instantiation, so that profilers list the call sites of the backward on separate lines
 enum { BG_GENERIC = 0, BG_CHAIN_DENSE, BG_CHAIN_NODE, BG_CHAIN_MIX, BG_X_NODE, BG_X_MIX, BG_WGRAD, BG_ADJ, BG_LINEAR,
@@ -811,17 +809,12 @@ __device__ __forceinline__ float4 ld4(const float* p, size_t idx) { return *rein
 __device__ __forceinline__ float4 ld4b(const float* p, unsigned byteOfs) {
   return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(p) + byteOfs);
 }
-#ifndef CHAIN_STORE_WT
-#define CHAIN_STORE_WT 1   // the fused chain kernels' outputs are the next chain kernel's inputs: written through (sc1) like the
-#endif                     // forward's step outputs, instead of dirty L2 lines flushed at the end of the kernel
+// the fused chain kernels' outputs are the next chain kernel's inputs: written through (sc1) like the forward's step
+// outputs, instead of dirty L2 lines flushed at the end of the kernel
 __device__ __forceinline__ void st4b(float* p, unsigned byteOfs, const float4& v) {
-#if CHAIN_STORE_WT
   const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(p, 0, 0x7ffffff0, 0x00020000);   // p is wave-uniform (a kernel argument)
   const u32x4 bits = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
   __builtin_amdgcn_raw_buffer_store_b128(bits, rsrc, (int)byteOfs, 0, 16);            // aux 16 = sc1
-#else
-  *reinterpret_cast<float4*>(reinterpret_cast<char*>(p) + byteOfs) = v;
-#endif
 }
 __device__ __forceinline__ float get4(const float4& v, int x) { return x == 0 ? v.x : x == 1 ? v.y : x == 2 ? v.z : v.w; }
 
@@ -986,32 +979,6 @@ __global__ __launch_bounds__(256) void k_chain_res_gate(ChainArgs a) {
   a.dha[idx] += dzh2 * z2;
   a.dpg2[row * 128 + o] = dzh2 * ha * z2 * (1.f - z2);
   a.dpg2[row * 128 + 64 + o] = a.dr[idx] * r2 * (1.f - r2);
-}
-
-// part 3: graph cell output algebra (MultiATGCN.py:127): ha = r h + (1-r) hc
-__global__ __launch_bounds__(256) void k_chain_cell_out(ChainArgs a) {
-  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (size_t)a.B * a.Np * 64) return;
-  const float h = a.hprev ? a.hprev[idx] : 0.f, r = a.r[idx], hc = a.hc[idx], dha = a.dha[idx];
-  a.dr[idx] = dha * (h - hc);
-  a.dh[idx] = dha * r;
-  a.dpu[idx] = dha * (1.f - r) * (1.f - hc * hc);
-}
-
-// part 4: gradient of z*h arrived (slot 0 of the update AGCN's dA + transposed mix of its dense slots)
-__global__ __launch_bounds__(256) void k_chain_cell_gate(ChainArgs a) {
-  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (size_t)a.B * a.Np * 64) return;
-  const size_t row = idx >> 6;
-  const int o = idx & 63;
-  const size_t b = row / a.Np, n = row - b * a.Np;
-  float dzh = a.dzhA[((b * a.S) * a.Np + n) * 64 + o];
-  if (a.dzhMix)
-    for (int pt = 0; pt < a.mixParts; ++pt) dzh += a.dzhMix[idx + (size_t)pt * a.mixPartStride];
-  const float h = a.hprev ? a.hprev[idx] : 0.f, z = a.z[idx], r = a.r[idx];
-  a.dh[idx] += dzh * z;
-  a.dpg[row * 128 + o] = dzh * h * z * (1.f - z);
-  a.dpg[row * 128 + 64 + o] = a.dr[idx] * r * (1.f - r);
 }
 
 // gradient of a layer's initial state, unpadded (B, N, 64): dh + slot 0 of the gate AGCN's dA of step 0 + its transposed
@@ -1303,9 +1270,9 @@ __global__ __launch_bounds__(512, 4) void k_chain_res_node(ChainResNodeArgs f) {
 // workgroup per (node, 64-row block), the A tile - the pre-activation gradients of the node's rows - in XOR-swizzled
 // LDS, the plain weights read straight from global memory (a lane's B fragment is four consecutive o: one aligned
 // float4 of the plain layout), 16x16x4 MFMA, 4 row tiles x (4 S) column tiles.  GATE: the tile is not read but COMPUTED
-// in the prologue - the gate algebra of the graph cell (what k_chain_cell_gate did as a launch of its own:
+// in the prologue - the gate algebra of the graph cell (once a launch of its own:
 // dzh = slot 0 of the update block's dA + its transposed mix; dh += dzh z; dpg = [dzh h z (1-z) | dr r (1-r)]) - and
-// stored to DPG for the batched part on the way.  Replaces k_chain_cell_gate + two generic k_bgemm launches per step.
+// stored to DPG for the batched part on the way.  Replaces that launch + two generic k_bgemm launches per step.
 struct ChainNodeArgs {
   ChainArgs c;           // GATE: operands of the gate algebra (dzhA, dzhMix, hprev, z, r, dr, dh, dpg)
   const float* dPre;     // !GATE: the pre-activation gradients [rows][Np][O]   (O = 192: the 128 gate columns ...
@@ -1638,11 +1605,7 @@ __global__ __launch_bounds__(S * O, MINW) void k_wgrad_node(WgradNodeArgs a) {
       const int u = tid + q * NT, k = u / (S * 16), r = u - k * (S * 16), slot = r >> 4, c4 = r & 15;
       const int row = tile * WG_KT + k;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-#ifdef WGN_LAB_NO_LOAD
-      if (false) {
-#else
       if (row < rows) {
-#endif
         const int t = tBeg + row / a.B, b = row - (row / a.B) * a.B;
         if (slot == 0) v = *reinterpret_cast<const float4*>(a.U + (((size_t)t * a.B + b) * a.Np + n) * 64 + c4 * 4);
         else if (sg[t]) v = *reinterpret_cast<const float4*>(sg[t] + (size_t)n * sgNode[t] + ((size_t)b * a.Ks + slot - 1) * 64 + c4 * 4);
@@ -1654,11 +1617,7 @@ __global__ __launch_bounds__(S * O, MINW) void k_wgrad_node(WgradNodeArgs a) {
       const int u = tid + q * NT, k = u / (O / 4), c4 = u - k * (O / 4);
       const int row = tile * WG_KT + k;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-#ifdef WGN_LAB_NO_LOAD
-      if (false) {
-#else
       if (u < nbUnits && row < rows) {
-#endif
         const int t = tBeg + row / a.B, b = row - (row / a.B) * a.B;
         v = *reinterpret_cast<const float4*>(a.dPre + (((size_t)t * a.B + b) * a.Np + n) * O + c4 * 4);
       }
@@ -1695,15 +1654,11 @@ __global__ __launch_bounds__(S * O, MINW) void k_wgrad_node(WgradNodeArgs a) {
   const float* Bb = Bs + ns * 64 + j + kq * BM;
   for (int tile = 0; tile < nTiles; tile += 2) {
     fetch(tile + 2, ra[0], rb[0]);
-#ifndef WGN_LAB_NO_MFMA
     wg_multiply(Ab, Bb, AM, BM, acc);
-#endif
     stash(1, ra[1], rb[1]);            // tile + 1
     __syncthreads();
     fetch(tile + 3, ra[1], rb[1]);
-#ifndef WGN_LAB_NO_MFMA
     if (tile + 1 < nTiles) wg_multiply(Ab + WG_KT * AM, Bb + WG_KT * BM, AM, BM, acc);
-#endif
     stash(0, ra[0], rb[0]);            // tile + 2
     __syncthreads();
   }
@@ -1728,10 +1683,7 @@ __global__ __launch_bounds__(S * O, MINW) void k_wgrad_node(WgradNodeArgs a) {
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-#ifdef WGN_LAB_NO_ATOMIC
-        if (acc[mt][nt][e] == 12345.678f)
-#endif
-          unsafeAtomicAdd(dst + (size_t)(16 * mt + 4 * kq + e) * O + 16 * nt, acc[mt][nt][e]);
+        unsafeAtomicAdd(dst + (size_t)(16 * mt + 4 * kq + e) * O + 16 * nt, acc[mt][nt][e]);
 }
 
 // ---- gradient of the learned support (round 3): dT[n][m] += sum_r sum_i dA[r][n][i] * U[r][m][i] -------------------

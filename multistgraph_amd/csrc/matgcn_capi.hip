@@ -22,10 +22,7 @@ namespace {
 
 constexpr int H = 64;
 constexpr int MAX_STEPS = 64;     // in_steps the wavefront scheduler keeps events for
-#ifndef X_CHUNK_STEPS
-#define X_CHUNK_STEPS 2
-#endif
-constexpr int X_CHUNK = X_CHUNK_STEPS;   // steps per hoisted x-part chunk of layers >= 1 (round 3: 1 / 2 / 3 equal, 4 +1 %, 8 +3 %)
+constexpr int X_CHUNK = 2;        // steps per hoisted x-part chunk of layers >= 1 (round 3: 1 / 2 / 3 equal, 4 +1 %, 8 +3 %)
 
 inline long rup(long v, long m) { return (v + m - 1) / m * m; }
 
@@ -137,11 +134,7 @@ int make_plan(const matgcn_dims* D, Plan* P) {
   }
   P->oHead = take((long)P->headT * H * 32 * P->NTc);
   P->preparedFloats = o;
-#if PX16_PIPELINE
   P->nodeLds = 3 * 64 * 64 * (int)sizeof(float);   // the x-row chunk + two ping-pong chunks of mixed rows
-#else
-  P->nodeLds = (64 * 64 + 64 * 64 * (P->Ks > 1 ? P->Ks : 1)) * (int)sizeof(float);
-#endif
   P->RB = (P->B + 63) / 64;
   // workspace
   o = 0;
@@ -340,29 +333,18 @@ struct Wavefront {
   hipEvent_t step[MATGCN_MAX_LAYERS][MAX_STEPS];   // layer l finished step t
   hipEvent_t xdone[MATGCN_MAX_LAYERS][MAX_STEPS];  // x-part chunk starting at step t of layer l is in PX
   hipEvent_t mixed[MATGCN_MAX_LAYERS][MAX_STEPS];  // layer l has mixed h_{t-1} (phase 0 of its step t)
-  hipEvent_t mixz[MATGCN_MAX_LAYERS][MAX_STEPS];   // layer l has mixed z*h (phase 2 of its step t): the mix token's second stop
   hipEvent_t bail[2 * MATGCN_MAX_LAYERS + 4];      // error exits: one per library stream (join_library_streams)
 };
 // one set per device ordinal: a HIP stream / event belongs to the device that was current when it was created, so a
 // process that drives several GPUs (or the rehearsal runs that put two ranks on one box) must not share them.
 // (One host thread per device at a time, like the rest of the library: the reference is single-threaded too.)
 constexpr int MAX_DEVICES = 64;
-// Two sets per device: the batch-split forward (matgcn_set_batch_split) runs the two halves of the batch as two
-// independent forwards side by side, each with its own layer wavefront; g_wf_set says which set the code below sees.
-Wavefront g_wfs[MAX_DEVICES][2];
-int g_wf_set = 0;
+Wavefront g_wfs[MAX_DEVICES];
 inline Wavefront& wf_current() {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) dev = 0;
-  return g_wfs[dev][g_wf_set];
+  return g_wfs[dev];
 }
-struct SplitStreams {            // the second half's "caller stream" and the fork / join events around it
-  bool ready = false;
-  hipStream_t s1;
-  hipEvent_t fork, done;
-};
-SplitStreams g_split[MAX_DEVICES];
-int g_batch_split = 0;          // matgcn_set_batch_split: 0 / 1 off, 2 = two halves
 
 // Lazy prepare (matgcn_set_lazy_prepare(1); off by default: the plain contract is "prepared is complete in stream order
 // when matgcn_prepare returns").  The node-adaptive weight streams - 250 MB, most of matgcn_prepare's time - are written
@@ -419,18 +401,6 @@ struct MixPrecisionScope {
   ~MixPrecisionScope() { g_mix_bf16_now = false; g_node_bf16_now = false; }
 };
 
-int split_ready() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) dev = 0;
-  SplitStreams& S = g_split[dev];
-  if (S.ready) return MATGCN_OK;
-  HIP_OK(hipStreamCreateWithFlags(&S.s1, hipStreamNonBlocking));
-  HIP_OK(hipEventCreateWithFlags(&S.fork, hipEventDisableTiming));
-  HIP_OK(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-  S.ready = true;
-  return MATGCN_OK;
-}
-
 int wavefront_ready() {
   if (g_wf.ready) return MATGCN_OK;
   // The runtime hands hardware queues (GPU_MAX_HW_QUEUES of them, default 4) to the streams of a process round robin in
@@ -461,10 +431,7 @@ int wavefront_ready() {
     auto make_stream = [&](hipStream_t* st) { return hipStreamCreateWithPriority(st, hipStreamNonBlocking, prGreatest); };
     int q = 4;
     if (const char* e = getenv("GPU_MAX_HW_QUEUES")) { const int v = atoi(e); if (v >= 1 && v <= 64) q = v; }
-#ifndef WF_RES
-#define WF_RES {1, 0, 1, 2, 3, 1}
-#endif
-    const int want[6] = WF_RES;        // main, chain[1], xpart[1], aux, xcol, bchain
+    const int want[6] = {1, 0, 1, 2, 3, 1};   // main, chain[1], xpart[1], aux, xcol, bchain
     hipStream_t* tgt[6] = {&g_wf.main, &g_wf.chain[1], &g_wf.xpart[1], &g_wf.aux, &g_wf.xcol, &g_wf.bchain};
     bool made[6] = {false, false, false, false, false, false};
     hipStream_t* fill[4] = {&g_wf.chain[2], &g_wf.xpart[2], &g_wf.chain[3], &g_wf.xpart[3]};
@@ -492,7 +459,6 @@ int wavefront_ready() {
       HIP_OK(hipEventCreateWithFlags(&g_wf.step[l][t], hipEventDisableTiming));
       HIP_OK(hipEventCreateWithFlags(&g_wf.xdone[l][t], hipEventDisableTiming));
       HIP_OK(hipEventCreateWithFlags(&g_wf.mixed[l][t], hipEventDisableTiming));
-      HIP_OK(hipEventCreateWithFlags(&g_wf.mixz[l][t], hipEventDisableTiming));
       HIP_OK(hipEventCreateWithFlags(&g_wf.bready[l][t], hipEventDisableTiming));
       HIP_OK(hipEventCreateWithFlags(&g_wf.bxcol[l][t], hipEventDisableTiming));
     }
@@ -507,17 +473,8 @@ int wavefront_ready() {
 // the caller with those streams still writing into the caller's buffers (workspace, train buffer, gradient bucket - the
 // caller may free or reuse them as soon as ITS stream is idle).  Whatever is in flight on every library stream is joined
 // into the caller's stream; the error code of the failed stage is what the call returns.
-void join_one_set(Wavefront& W, hipStream_t caller);
 void join_library_streams(hipStream_t caller) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) dev = 0;
-  for (int set = 0; set < 2; ++set) join_one_set(g_wfs[dev][set], caller);
-  if (g_split[dev].ready && g_split[dev].s1 != caller &&
-      hipEventRecord(g_split[dev].done, g_split[dev].s1) == hipSuccess)
-    (void)hipStreamWaitEvent(caller, g_split[dev].done, 0);
-  (void)hipGetLastError();
-}
-void join_one_set(Wavefront& W, hipStream_t caller) {
+  Wavefront& W = g_wf;
   if (!W.ready) return;
   hipStream_t all[2 * MATGCN_MAX_LAYERS + 4];
   int n = 0;
@@ -558,24 +515,6 @@ int on_main_stream(void* callerStream, Body&& body) {
   return rc;
 }
 
-#ifdef NODE_LAB_STAMPS   // lab builds only (tools/labs/stamps_r04.py): where the node kernels' in-kernel stamps go
-unsigned int* g_lab_stamps = nullptr;
-size_t g_lab_stamp_words = 0;
-int g_lab_stamp_launch = 0;
-int g_lab_stamp_kinds = 1;   // 1: node kernels (k_gate16 / k_update16), 2: k_mix<1>
-extern "C" int matgcn_lab_stamps(void* buf, size_t words) {
-  g_lab_stamps = static_cast<unsigned int*>(buf); g_lab_stamp_words = words; g_lab_stamp_launch = 0;
-  return MATGCN_OK;
-}
-extern "C" int matgcn_lab_stamp_launches(void) { return g_lab_stamp_launch; }
-extern "C" int matgcn_lab_stamp_kinds(int kinds) { g_lab_stamp_kinds = kinds; return MATGCN_OK; }
-static unsigned int* lab_stamp_slot(unsigned gridBlocks, int wavesPerBlock = 8) {
-  const size_t per = (size_t)gridBlocks * wavesPerBlock * NODE_STAMPS;
-  if (!g_lab_stamps || (size_t)(g_lab_stamp_launch + 1) * per > g_lab_stamp_words) return nullptr;
-  return g_lab_stamps + (size_t)(g_lab_stamp_launch++) * per;
-}
-#endif
-
 // out[(k,n)][col] = sum_m S_k[n][m] X[m][col]; see k_mix
 int launch_mix(const Plan& P, const float* St, const float* X, long xTileStride, int ldX, int nColTiles,
                float* out, long sN, long sK, long sT, int Ks, int rowsM, hipStream_t s, bool stepRole = false,
@@ -588,25 +527,16 @@ int launch_mix(const Plan& P, const float* St, const float* X, long xTileStride,
   a.nRowTiles = (int)(rup(rowsM, 64) / 64);
   ProfScope prof(stepRole ? MATGCN_PROF_MIX : MATGCN_PROF_MIX_PRE, s);
   const dim3 grid((unsigned)(a.nRowTiles * nColTiles));
-#ifdef NODE_LAB_STAMPS
-  if (stepRole && (g_lab_stamp_kinds & 2)) a.stamps = lab_stamp_slot(grid.x, 4);
-#endif
   if (g_mix_bf16_now) {   // opt-in bf16-operand variant of the inference forward (fp32 accumulate, fp32 in / out)
     if (stepRole) hipLaunchKernelGGL(k_mix_bf16<1>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_mix_bf16<0>, grid, dim3(256), 0, s, a);
-#ifndef MIX_FLUSH_MIN_NK
-#define MIX_FLUSH_MIN_NK 64
-#endif
-  } else if (a.nK > MIX_FLUSH_MIN_NK) {   // more than 1 024 reduction indices: partial sums every 256 (k_mix's FLUSH)
+  } else if (a.nK > 64) {   // more than 1 024 reduction indices: partial sums every 256 (k_mix's FLUSH)
     if (stepRole) hipLaunchKernelGGL((k_mix<1, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_mix<0, true>), grid, dim3(256), 0, s, a);
-#ifndef MIX_C32_MAX_COLTILES
-#define MIX_C32_MAX_COLTILES 16    // column tiles (batch rows of a step mix) up to which the 64 x 32-tile kernel runs; 0: never
-                                   // (round 4, BM 403: B = 16 20.8 -> 18.1 us per launch, forward 3.69 -> 3.56 ms; B = 32 no gain per
-                                   //  launch and the forward 2 % SLOWER; DC 237 at B = 16 unchanged: profiles/r04_small_batch_lab.log)
-#endif
-  } else if (nColTiles <= MIX_C32_MAX_COLTILES && xTileStride % 4 == 0 && ldX >= 64) {
-    // small batches (the reference ships batch_size 16): twice the workgroups of half the width
+  } else if (nColTiles <= 16 && xTileStride % 4 == 0 && ldX >= 64) {
+    // small batches (the reference ships batch_size 16): twice the workgroups of half the width, up to 16 column tiles
+    // (batch rows of a step mix) - round 4, BM 403: B = 16 20.8 -> 18.1 us per launch, forward 3.69 -> 3.56 ms; B = 32 no
+    // gain per launch and the forward 2 % SLOWER; DC 237 at B = 16 unchanged: profiles/r04_small_batch_lab.log
     const dim3 g2((unsigned)(a.nRowTiles * nColTiles * 2));
     if (stepRole) hipLaunchKernelGGL(k_mix_c32<1>, g2, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_mix_c32<0>, g2, dim3(256), 0, s, a);
@@ -662,15 +592,13 @@ struct Ctx {
   TrainPlan R;
   const float* dropMask = nullptr;   // matgcn_forward_train: (B, headT, N, H) dropout mask of the head's input, applied by the
                                      // top layer's update kernel as it writes the sequence (graph layers)
-  size_t h0LayerStride = 0;   // floats between the layers of the caller's h0 (0: B*N*H; the batch-split halves see the
-                              // caller's full-batch layout)
 };
 
 // dynamic LDS: k_gate16 48 KB (state chunk + two ping-pong chunks), k_update16 64 KB (+ the x_t tile of the residual
 // cell), k_px16 the whole tile; sizes above 64 KB must be opted into once per kernel
-constexpr int GATE_LDS = 3 * NODE_ROWS * 64 * (int)sizeof(float);
-constexpr int UPDATE_LDS = 4 * NODE_ROWS * 64 * (int)sizeof(float);
-constexpr int UPDATE_SAVE_LDS = 5 * NODE_ROWS * 64 * (int)sizeof(float);   // training: + the tile saved activations pass through
+constexpr int GATE_LDS = 3 * 64 * 64 * (int)sizeof(float);
+constexpr int UPDATE_LDS = 4 * 64 * 64 * (int)sizeof(float);
+constexpr int UPDATE_SAVE_LDS = 5 * 64 * 64 * (int)sizeof(float);   // training: + the tile saved activations pass through
 int node_kernels_ready(int ldsBytes) {
   static int readyOn[MAX_DEVICES] = {0};   // function attributes are per device
   int dev = 0;
@@ -678,16 +606,16 @@ int node_kernels_ready(int ldsBytes) {
   int& ready = readyOn[dev];
   if (ready >= ldsBytes) return MATGCN_OK;
   const hipFuncAttribute at = hipFuncAttributeMaxDynamicSharedMemorySize;
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<false, NODE_ROWS>), at, GATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<true, NODE_ROWS>), at, GATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<0, false, NODE_ROWS>), at, UPDATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, false, NODE_ROWS>), at, UPDATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, true, NODE_ROWS>), at, UPDATE_SAVE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<2, false, NODE_ROWS>), at, UPDATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<2, true, NODE_ROWS>), at, UPDATE_SAVE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<false, NODE_ROWS, true>), at, GATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, false, NODE_ROWS, true>), at, UPDATE_LDS));
-  // 32-row work items for batches of at most 32 rows (the halves of the batch-split forward)
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<false, 64>), at, GATE_LDS));
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<true, 64>), at, GATE_LDS));
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<0, false, 64>), at, UPDATE_LDS));
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, false, 64>), at, UPDATE_LDS));
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, true, 64>), at, UPDATE_SAVE_LDS));
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<2, false, 64>), at, UPDATE_LDS));
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<2, true, 64>), at, UPDATE_SAVE_LDS));
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<false, 64, true>), at, GATE_LDS));
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, false, 64, true>), at, UPDATE_LDS));
+  // 32-row work items (batches of at most 32 rows, graphs of at most 256 nodes: cell_phase)
   HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<false, 32>), at, GATE_LDS));
   HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, false, 32>), at, UPDATE_LDS));
   HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<true, 32>), at, GATE_LDS));
@@ -815,21 +743,13 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
   if (l == 0) { a.xa = c.ws + P.oXA0 + (size_t)t * P.N * P.B * P.Kx; a.nGx = P.nGx[0]; }
   else a.px = c.ws + P.oPX[l] + (size_t)t * P.N * P.RB * NODE_PX_BLOCK;
   const bool save = c.train != nullptr && res != nullptr;
-  // a batch of at most 32 rows (the halves of the batch-split forward) runs the 32-row instantiations: a 64-row tile
-  // would be half padding
-  // ... and so does a graph of at most NODE_ROWS32_MAX_NODES nodes at any batch size: 237 (node, 64-row) items leave half of
+  // a batch of at most 32 rows runs the 32-row instantiations: a 64-row tile would be half padding
+  // ... and so does a graph of at most 256 nodes at any batch size: 237 (node, 64-row) items leave half of
   // the chip's 512 workgroup slots empty; as (node, 32-row) items they fill 474 of them (round 3 measured the compile-time
   // variant at N = 237: gate 19.4 -> 18.5 us, update 24.4 -> 22.5 us; round 4 picks it at run time)
-#ifndef NODE_ROWS32_MAX_NODES
-#define NODE_ROWS32_MAX_NODES 256
-#endif
   // (round 4: the training instantiations too - at the shipped batch size 16 the training forward ran 64-row tiles)
-  const bool rows32 = NODE_ROWS == 64 && (P.B <= 32 || P.N <= NODE_ROWS32_MAX_NODES) && res != nullptr && !raw &&
-                      !g_node_bf16_now;
-  const dim3 grid(node_items(P.N, P.B, rows32 ? 32 : NODE_ROWS));   // (node, row block) work items, XCD-paired per node
-#ifdef NODE_LAB_STAMPS
-  a.stamps = (g_lab_stamp_kinds & 1) ? lab_stamp_slot(grid.x) : nullptr;
-#endif
+  const bool rows32 = (P.B <= 32 || P.N <= 256) && res != nullptr && !raw && !g_node_bf16_now;
+  const dim3 grid(node_items(P.N, P.B, rows32 ? 32 : 64));   // (node, row block) work items, XCD-paired per node
   if (save) {
     const size_t at = (size_t)t * P.B * P.Np * H;
     a.svZ = c.train + c.R.oZ[l] + at; a.svR = c.train + c.R.oR[l] + at; a.svHC = c.train + c.R.oHC[l] + at;
@@ -842,9 +762,9 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
     ProfScope prof(MATGCN_PROF_GATE, s);
     if (rows32 && save) hipLaunchKernelGGL((k_gate16<true, 32>), grid, dim3(512), GATE_LDS / 2, s, a);
     else if (rows32) hipLaunchKernelGGL((k_gate16<false, 32>), grid, dim3(512), GATE_LDS / 2, s, a);
-    else if (bf) hipLaunchKernelGGL((k_gate16<false, NODE_ROWS, true>), grid, dim3(512), GATE_LDS, s, a);
-    else if (save) hipLaunchKernelGGL((k_gate16<true, NODE_ROWS>), grid, dim3(512), GATE_LDS, s, a);
-    else hipLaunchKernelGGL((k_gate16<false, NODE_ROWS>), grid, dim3(512), GATE_LDS, s, a);
+    else if (bf) hipLaunchKernelGGL((k_gate16<false, 64, true>), grid, dim3(512), GATE_LDS, s, a);
+    else if (save) hipLaunchKernelGGL((k_gate16<true, 64>), grid, dim3(512), GATE_LDS, s, a);
+    else hipLaunchKernelGGL((k_gate16<false, 64>), grid, dim3(512), GATE_LDS, s, a);
     return launch_ok();
   }
   a.s = ZHx; a.w = bf ? c.ws + P.oW16u[l] : c.prep + P.oWu[l]; a.r = R; a.h = Hx; a.hout = Hx;
@@ -860,11 +780,11 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
     }
     if (rows32 && save) hipLaunchKernelGGL((k_update16<1, true, 32>), grid, dim3(512), UPDATE_SAVE_LDS / 2, s, a);
     else if (rows32) hipLaunchKernelGGL((k_update16<1, false, 32>), grid, dim3(512), UPDATE_LDS / 2, s, a);
-    else if (bf) hipLaunchKernelGGL((k_update16<1, false, NODE_ROWS, true>), grid, dim3(512), UPDATE_LDS, s, a);
-    else if (save) hipLaunchKernelGGL((k_update16<1, true, NODE_ROWS>), grid, dim3(512), UPDATE_SAVE_LDS, s, a);
-    else hipLaunchKernelGGL((k_update16<1, false, NODE_ROWS>), grid, dim3(512), UPDATE_LDS, s, a);
+    else if (bf) hipLaunchKernelGGL((k_update16<1, false, 64, true>), grid, dim3(512), UPDATE_LDS, s, a);
+    else if (save) hipLaunchKernelGGL((k_update16<1, true, 64>), grid, dim3(512), UPDATE_SAVE_LDS, s, a);
+    else hipLaunchKernelGGL((k_update16<1, false, 64>), grid, dim3(512), UPDATE_LDS, s, a);
   } else {
-    hipLaunchKernelGGL((k_update16<0, false, NODE_ROWS>), grid, dim3(512), UPDATE_LDS, s, a);
+    hipLaunchKernelGGL((k_update16<0, false, 64>), grid, dim3(512), UPDATE_LDS, s, a);
   }
   return launch_ok();
 }
@@ -889,7 +809,7 @@ int res_step(const Ctx& c, int l, const float* xt, long xRowStride) {
   a.rows = P.B; a.N = P.N; a.Np = P.Np; a.Ks = P.Ks;
   fill_res_args(c, l, xt, xRowStride, nullptr, nullptr, &a);
   ProfScope prof(MATGCN_PROF_RES, c.s);
-  hipLaunchKernelGGL((k_update16<2, false, NODE_ROWS>), dim3(node_items(P.N, P.B, NODE_ROWS)), dim3(512), UPDATE_LDS, c.s, a);
+  hipLaunchKernelGGL((k_update16<2, false, 64>), dim3(node_items(P.N, P.B, 64)), dim3(512), UPDATE_LDS, c.s, a);
   return launch_ok();
 }
 
@@ -959,7 +879,7 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
       CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(k_pack_rows, dim3(blocks_for((size_t)P.B * P.Np * H)), dim3(256), 0, cs,
-                       h0User ? h0User + (size_t)l * (c.h0LayerStride ? c.h0LayerStride : (size_t)P.B * P.N * H) : nullptr,
+                       h0User ? h0User + (size_t)l * P.B * P.N * H : nullptr,
                        c.ws + P.oHx[l], P.B, P.N, P.Np, H);
     CHECK_LAUNCH();
     if (c.train && h0User) {   // the backward needs h_{-1} of every layer (gate algebra, weight gradients of step 0)
@@ -969,26 +889,6 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
       CHECK_LAUNCH();
     }
   }
-  // ---- the mix token (matgcn_set_wavefront(2), round 4) -------------------------------------------------------------
-  // In the free-running wavefront every kernel of a chain is stretched by whatever the other chain happens to run beside
-  // it (in-situ events: k_mix 41 -> 75 us on average, the wall is the sum of one chain's stretched kernels).  A graph mix
-  // is MFMA-bound with HBM idle, a node kernel streams weights with the matrix pipe a third busy, and one node workgroup
-  // fits beside the five mix workgroups of a CU (5 x 56 + 2 x 112 registers): they are complementary - two mixes, or two
-  // node kernels, are not.  With the token the graph mixes of ALL chains form one global order (every mix waits for the mix
-  // enqueued before it, on whatever stream that was); the node kernels stay free on their chains.  So a mix never runs
-  // beside another mix, and the node kernel that follows a mix runs beside the next chain's mix.  The steps are enqueued
-  // in global order (layer l runs `lag` steps behind layer l-1) so that every event is recorded before it is waited for.
-  const bool token = multi && g_wavefront_mode == 2 && !P.gcnOff && P.Ks > 0;
-  hipEvent_t lastMix = nullptr;
-  hipStream_t lastMixStream = nullptr;
-  auto mix_phase = [&](int l, int t, int phase, const Node16Args* res, hipStream_t cs) -> int {
-    if (token && lastMix && lastMixStream != cs) HIP_OK(hipStreamWaitEvent(cs, lastMix, 0));
-    RETURN_IF(cell_phase(c, l, t, phase, nullptr, res, cs));
-    if (phase == 0 && ((multi && l + 1 < P.L) || token)) HIP_OK(hipEventRecord(W.mixed[l][t], cs));
-    if (phase == 2 && token) HIP_OK(hipEventRecord(W.mixz[l][t], cs));
-    if (token) { lastMix = phase == 0 ? W.mixed[l][t] : W.mixz[l][t]; lastMixStream = cs; }
-    return MATGCN_OK;
-  };
   int nextChunk[MATGCN_MAX_LAYERS] = {0};
   // ---- one step of one layer ----
   auto enqueue_step = [&](int l, int t) -> int {
@@ -1007,13 +907,13 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
       else fill_res_args(c, l, below + t * stepRows, (long)P.Np * H, nullptr, seq + t * stepRows, &a);
       {
         ProfScope prof(MATGCN_PROF_RES, cs);
-        const dim3 grid(node_items(P.N, P.B, NODE_ROWS));
+        const dim3 grid(node_items(P.N, P.B, 64));
         if (c.train) {   // training keeps z, r, hc of the dense cell (slots of the residual cell)
           const size_t at = (size_t)t * P.B * P.Np * H;
           a.svZ2 = c.train + c.R.oZ2[l] + at; a.svR2 = c.train + c.R.oR2[l] + at; a.svHC2 = c.train + c.R.oHC2[l] + at;
-          hipLaunchKernelGGL((k_update16<2, true, NODE_ROWS>), grid, dim3(512), UPDATE_SAVE_LDS, cs, a);
+          hipLaunchKernelGGL((k_update16<2, true, 64>), grid, dim3(512), UPDATE_SAVE_LDS, cs, a);
         } else {
-          hipLaunchKernelGGL((k_update16<2, false, NODE_ROWS>), grid, dim3(512), UPDATE_LDS, cs, a);
+          hipLaunchKernelGGL((k_update16<2, false, 64>), grid, dim3(512), UPDATE_LDS, cs, a);
         }
       }
       CHECK_LAUNCH();
@@ -1047,25 +947,20 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
     else
       fill_res_args(c, l, below + t * stepRows, (long)P.Np * H, c.prm->weights_gru + (size_t)l * P.T + t,
                     seq + t * stepRows, &res);
-    RETURN_IF(mix_phase(l, t, 0, &res, cs));
+    RETURN_IF(cell_phase(c, l, t, 0, nullptr, &res, cs));
+    if (multi && l + 1 < P.L) HIP_OK(hipEventRecord(W.mixed[l][t], cs));
     // layer 0's weight streams are first read here: head fusion, the fold of x0 and the first mix ran beside their
     // preparation (lazy prepare)
     if (lazyPrep && multi && l == 0 && t == 0) RETURN_IF(prep_wait(cs, 1));
     RETURN_IF(cell_phase(c, l, t, 1, nullptr, &res, cs));
-    RETURN_IF(mix_phase(l, t, 2, &res, cs));
+    RETURN_IF(cell_phase(c, l, t, 2, nullptr, &res, cs));
     RETURN_IF(cell_phase(c, l, t, 3, nullptr, &res, cs));
     if (multi && l + 1 < P.L) HIP_OK(hipEventRecord(W.step[l][t], cs));
     return MATGCN_OK;
   };
-  // ---- global order: layer l runs `lag` steps behind layer l-1 (lag = T: layer after layer, the free-running wavefront's
-  // enqueue order - its events only tie a layer to the one below).  The x-part chunk of layer l that starts at step t waits
-  // for step t + nt (<= t + X_CHUNK) of the layer below, which must have been ENQUEUED by then: lag = X_CHUNK + 1. ----
-  const int lag = token ? X_CHUNK + 1 : P.T;
-  for (int g = 0; g < P.T + lag * (P.L - 1); ++g)
-    for (int l = 0; l < P.L; ++l) {
-      const int t = g - lag * l;
-      if (t >= 0 && t < P.T) RETURN_IF(enqueue_step(l, t));
-    }
+  // ---- layer after layer: the events only tie a layer to the one below, every one is recorded before it is waited for ----
+  for (int l = 0; l < P.L; ++l)
+    for (int t = 0; t < P.T; ++t) RETURN_IF(enqueue_step(l, t));
   // ---- per layer: final states, join ----
   for (int l = 0; l < P.L; ++l) {
     hipStream_t cs = chain_stream(l);
@@ -1242,12 +1137,6 @@ int matgcn_prepare_join(void* stream) {
   return prep_wait((hipStream_t)stream, 3);
 }
 
-int matgcn_set_batch_split(int parts) {
-  const int prev = g_batch_split;
-  g_batch_split = parts == 2 ? 2 : 0;
-  return prev;
-}
-
 int matgcn_series_violations(int64_t* count, int reset) {
   if (!count) return MATGCN_ERR_NULL;
   unsigned long long v = 0;
@@ -1269,15 +1158,14 @@ int matgcn_set_mix_precision(int mode) {
 
 int matgcn_set_stream_pool(int own) {
   for (int d = 0; d < MAX_DEVICES; ++d)
-    for (int set = 0; set < 2; ++set)
-      if (g_wfs[d][set].ready) return own ? (g_stream_pool ? MATGCN_OK : MATGCN_ERR_BAD_ARG) : (g_stream_pool ? MATGCN_ERR_BAD_ARG : MATGCN_OK);
+    if (g_wfs[d].ready) return own ? (g_stream_pool ? MATGCN_OK : MATGCN_ERR_BAD_ARG) : (g_stream_pool ? MATGCN_ERR_BAD_ARG : MATGCN_OK);
   g_stream_pool = own ? 1 : 0;
   return MATGCN_OK;
 }
 
 int matgcn_set_wavefront(int mode) {
   const int prev = g_wavefront_mode;
-  g_wavefront_mode = (mode == 1 || mode == 2) ? mode : (mode != 0 ? 1 : 0);
+  g_wavefront_mode = mode != 0 ? 1 : 0;
   return prev;
 }
 
@@ -1305,15 +1193,7 @@ int matgcn_workspace_bytes(const matgcn_dims* dims, size_t* bytes) {
   if (!bytes) return MATGCN_ERR_NULL;
   Plan P;
   RETURN_IF(make_plan(dims, &P));
-  size_t need = (size_t)(g_mix_precision == 2 ? P.workspaceFloatsBf16 : P.workspaceFloats) * sizeof(float);
-  if (dims->batch >= 2 && !(dims->batch & 1)) {     // room for the two half-batch plans of the batch-split forward
-    matgcn_dims half = *dims;
-    half.batch = dims->batch / 2;
-    Plan Q;
-    if (make_plan(&half, &Q) == MATGCN_OK && 2 * (size_t)Q.workspaceFloats * sizeof(float) > need)
-      need = 2 * (size_t)Q.workspaceFloats * sizeof(float);
-  }
-  *bytes = need;
+  *bytes = (size_t)(g_mix_precision == 2 ? P.workspaceFloatsBf16 : P.workspaceFloats) * sizeof(float);
   return MATGCN_OK;
 }
 
@@ -1428,14 +1308,9 @@ static int prepare_impl(const matgcn_dims* dims, const matgcn_params* params, vo
   int piece = 0;
   const StackMap map = build_stack_map(P, dims, params);
   const unsigned nodeGroups = (unsigned)((P.N + PREP_NB - 1) / PREP_NB);
-#ifndef PREP_KERNEL
-#define PREP_KERNEL 2      // 0: k_prep_stream (round 1, lab builds), 2: k_prep_mfma
-#endif
-#ifndef PREP_TPW
-#define PREP_TPW 4         // k_prep_mfma: 16-node tiles per wave (a workgroup = 4 waves walks 4 * PREP_TPW tiles)
-#endif
-  const bool fast = PREP_KERNEL == 2 && P.d <= 32;
-  const int nTiles = (P.N + 15) / 16, tilesPerBlock = 4 * PREP_TPW;
+  const bool fast = P.d <= 32;   // k_prep_mfma; k_prep_stream for wider embeddings
+  // k_prep_mfma: 4 16-node tiles per wave (a workgroup = 4 waves walks 16 tiles)
+  const int nTiles = (P.N + 15) / 16, tilesPerBlock = 4 * 4;
   const unsigned tileBlocks = (unsigned)((nTiles + tilesPerBlock - 1) / tilesPerBlock);
   auto launch_fast = [&](const PrepStream& q, int O, hipStream_t ws) {
     const dim3 grid((unsigned)((q.groups + q.groupsX) * (O / 16) * 2), tileBlocks);
@@ -1520,7 +1395,7 @@ static int prepare_impl(const matgcn_dims* dims, const matgcn_params* params, vo
   return MATGCN_OK;
 }
 
-// one whole inference forward of `dims->batch` samples on stream c.s with the current wavefront set: head fusion
+// one whole inference forward of `dims->batch` samples on stream c.s: head fusion
 // (from windows X, or - series != null - gathered from the resident series), encoder, head
 static int forward_once(Ctx& c, const float* X, const float* series, int64_t seriesSteps, const int32_t* labelStart,
                         const int32_t* relSteps, const float* h0, float* out) {
@@ -1532,55 +1407,6 @@ static int forward_once(Ctx& c, const float* X, const float* series, int64_t ser
   return head_padded(c, c.ws + P.oSeq[P.L - 1], out);
 }
 
-// The batch-split forward (matgcn_set_batch_split(2)): the two halves of the batch are two independent forwards of
-// B / 2 samples - no arithmetic ties them, MultiATGCN.py:363-420 is per sample - run side by side: half 0 on the caller's
-// stream with wavefront set 0, half 1 on a library stream with set 1, each in its own half of the workspace, joined at
-// the end.  Four chains of half-size kernels instead of two: their fixed launch costs hide behind each other's work and
-// their smaller grids leave room to co-reside.  Same kernels, same per-sample arithmetic - the
-// results are those of two forwards of B / 2.
-static int forward_split(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
-                         const float* series, int64_t seriesSteps, const int32_t* labelStart, const int32_t* relSteps,
-                         const float* h0, float* out, void* workspace, size_t workspace_bytes, void* stream,
-                         bool* done) {
-  *done = false;
-  if (g_batch_split != 2 || g_wavefront_mode == 0 || g_mix_precision != 0 || dims->batch < 2 || (dims->batch & 1))
-    return MATGCN_OK;
-  matgcn_dims half = *dims;
-  half.batch = dims->batch / 2;
-  Ctx c0, c1;
-  Plan probe;
-  RETURN_IF(make_plan(&half, &probe));
-  const size_t halfBytes = (size_t)probe.workspaceFloats * sizeof(float);
-  if (2 * halfBytes > workspace_bytes) return MATGCN_OK;          // does not fit: the caller runs the plain forward
-  RETURN_IF(split_ready());
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) dev = 0;
-  SplitStreams& S = g_split[dev];
-  RETURN_IF(make_ctx(&c0, &half, params, prepared, workspace, halfBytes, stream, false));
-  RETURN_IF(make_ctx(&c1, &half, params, prepared, (char*)workspace + halfBytes, halfBytes, S.s1, false));
-  const size_t layerStride = (size_t)dims->batch * dims->nodes * H;
-  c0.h0LayerStride = c1.h0LayerStride = layerStride;
-  const int hb = half.batch;
-  const size_t xHalf = (size_t)hb * dims->x_steps * dims->nodes * dims->x_feat;
-  const size_t outHalf = (size_t)hb * dims->out_channels * dims->nodes;
-  const size_t h0Half = (size_t)hb * dims->nodes * H;
-  HIP_OK(hipEventRecord(S.fork, c0.s));
-  HIP_OK(hipStreamWaitEvent(S.s1, S.fork, 0));
-  g_wf_set = 0;
-  int rc = forward_once(c0, X, series, seriesSteps, labelStart, relSteps, h0, out);
-  if (rc == MATGCN_OK) {
-    g_wf_set = 1;
-    rc = forward_once(c1, X ? X + xHalf : nullptr, series, seriesSteps, labelStart ? labelStart + hb : nullptr, relSteps,
-                      h0 ? h0 + h0Half : nullptr, out + outHalf);
-  }
-  g_wf_set = 0;
-  if (rc != MATGCN_OK) { join_library_streams(c0.s); return rc; }
-  HIP_OK(hipEventRecord(S.done, S.s1));
-  HIP_OK(hipStreamWaitEvent(c0.s, S.done, 0));
-  *done = true;
-  return MATGCN_OK;
-}
-
 static int forward_entry(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
                          const float* h0, float* out, void* workspace, size_t workspace_bytes, void* stream) {
   if (!prepared || !X || !out) return MATGCN_ERR_NULL;
@@ -1589,10 +1415,6 @@ static int forward_entry(const matgcn_dims* dims, const matgcn_params* params, c
   if (!params->weight_tsg || !params->end_conv_bias) return MATGCN_ERR_NULL;
   for (int h = 0; h < dims->n_heads; ++h) if (!params->weight_ts[h]) return MATGCN_ERR_NULL;
   RETURN_IF(check_layer_params(dims, params));
-  bool done = false;
-  RETURN_IF(forward_split(dims, params, prepared, X, nullptr, 0, nullptr, nullptr, h0, out, workspace, workspace_bytes,
-                          stream, &done));
-  if (done) return MATGCN_OK;
   MixPrecisionScope mixScope(true);
   return forward_once(c, X, nullptr, 0, nullptr, nullptr, h0, out);
 }
@@ -1626,10 +1448,6 @@ static int forward_series_entry(const matgcn_dims* dims, const matgcn_params* pa
   for (int h = 0; h < dims->n_heads; ++h) if (!params->weight_ts[h]) return MATGCN_ERR_NULL;
   RETURN_IF(check_layer_params(dims, params));
   RETURN_IF(check_series(dims, series, series_steps, label_start, rel_steps));
-  bool done = false;
-  RETURN_IF(forward_split(dims, params, prepared, nullptr, series, series_steps, label_start, rel_steps, h0, out, workspace,
-                          workspace_bytes, stream, &done));
-  if (done) return MATGCN_OK;
   MixPrecisionScope mixScope(true);
   return forward_once(c, nullptr, series, series_steps, label_start, rel_steps, h0, out);
 }

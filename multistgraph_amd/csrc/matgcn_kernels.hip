@@ -608,9 +608,7 @@ __global__ __launch_bounds__(256) void k_build_xa0(const float* __restrict__ x0p
 // so every graph of at most 1 024 nodes - the headline's 403 - keeps its kernel and its bits.
 // (round 4, measured and rejected: rotating the wave priority with the K-tile index by dispatch round so that the five
 //  workgroups of a CU leave together - they do, and every one is slower: 43.0 vs 41.3 us, profiles/r04_mix_stamps_lab.log)
-#ifndef MIX_FLUSH_TILES
-#define MIX_FLUSH_TILES 16
-#endif
+constexpr int MIX_FLUSH_TILES = 16;
 template <int ROLE, bool FLUSH = false>
 __global__ __launch_bounds__(256) void k_mix(MixArgs a) {
   // (FLUSH costs 16 registers, 72 in all: seven workgroups per CU instead of eight, +3.7 % per launch at N = 4 096; forced
@@ -631,12 +629,7 @@ __global__ __launch_bounds__(256) void k_mix(MixArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1, j = lane & 15, kq = lane >> 4;
   const int kk = tid >> 4, sg = tid & 15;
-#ifdef MIX_LAB_STAGGER   // LAB: the workgroups that share a CU (ids 256 apart) start MIX_LAB_STAGGER x 64 cycles apart
-  for (int d = 0; d < (int)(blockIdx.x >> 8); ++d) __builtin_amdgcn_s_sleep(MIX_LAB_STAGGER);
-#endif
   const int part = blockIdx.y;     // split reduction (MixArgs.parts): 0 unless the launch has a second grid dimension
-  NODE_STAMP_DECL
-  NODE_STAMP(0);
   const float* ap = a.St + (size_t)part * a.aPartStride + (size_t)kk * a.ldS + row0 + sg * 4;
   const float* bp = a.X + (size_t)part * a.xPartStride + (size_t)colTile * a.xTileStride + (size_t)kk * a.ldX + sg * 4;
   // LDS image of a K-tile: row kk (one reduction index, 64 values) rotated by 16*(kk&3) floats, so that the four
@@ -654,21 +647,13 @@ __global__ __launch_bounds__(256) void k_mix(MixArgs a) {
   float4 ra0, rb0, ra1, rb1;
   {
     const float4 a0 = ldA(0), b0 = ldB(0);
-#ifndef MIX_LAB_SERIAL_PROLOGUE
     __builtin_amdgcn_sched_barrier(0);    // tile 0 first: its stores wait for the two OLDEST requests only
-#endif
     ra0 = ldA(1); rb0 = ldB(1); ra1 = ldA(2); rb1 = ldB(2);
-#ifndef MIX_LAB_SERIAL_PROLOGUE
     __builtin_amdgcn_sched_barrier(0);
-#endif
-    NODE_STAMP(1);   // six requests issued
     *reinterpret_cast<float4*>(&As[0][stPos]) = a0;
-    NODE_STAMP(2);   // A tile 0 arrived
     *reinterpret_cast<float4*>(&Bs[0][stPos]) = b0;
-    NODE_STAMP(3);   // B tile 0 arrived
   }
   __syncthreads();
-  NODE_STAMP(4);
   // the wave's 32x32 output tile = 2x2 accumulators of v_mfma_f32_16x16x4_f32: 20 independent accumulator chains
   // per SIMD at 5 resident workgroups per CU, enough to keep the matrix pipe issuing back to back
   f32x4 acc[2][2], tot[FLUSH ? 2 : 1][2];
@@ -694,18 +679,13 @@ __global__ __launch_bounds__(256) void k_mix(MixArgs a) {
       acc[1][1] = MFMA16(a1, b1, acc[1][1]);
     }
   };
-#ifdef MIX_LAB_NK   // LAB: only the first MIX_LAB_NK K-tiles (results are garbage: timing of the fixed part only)
-  const int nKrun = a.nK < MIX_LAB_NK ? a.nK : MIX_LAB_NK;
-#else
-  const int nKrun = a.nK;
-#endif
-  for (int it = 0; it < nKrun; it += 2) {
+  for (int it = 0; it < a.nK; it += 2) {
     mma(0);                                               // tile it
     *reinterpret_cast<float4*>(&As[1][stPos]) = ra0;      // tile it+1 (a clamped copy past the end: unused)
     *reinterpret_cast<float4*>(&Bs[1][stPos]) = rb0;
     ra0 = ldA(it + 3); rb0 = ldB(it + 3);
     __syncthreads();
-    if (it + 1 < nKrun) {
+    if (it + 1 < a.nK) {
       mma(1);                                             // tile it+1
       *reinterpret_cast<float4*>(&As[0][stPos]) = ra1;    // tile it+2
       *reinterpret_cast<float4*>(&Bs[0][stPos]) = rb1;
@@ -738,10 +718,9 @@ __global__ __launch_bounds__(256) void k_mix(MixArgs a) {
   // and writes whole 128-byte row segments with 16-byte WRITE-THROUGH stores (sc1): the 20-75 MB this kernel
   // produces then leave the L2 while it is still computing instead of as one dirty-line flush at its end, which
   // the next kernel of the chain would otherwise wait for.
-  NODE_STAMP(5);   // K loop issued
   // (round 4: the last workgroup of a CU runs this stretch alone, one wave per SIMD - 8.5 k cycles by the stamps of
-  //  tools/labs/stamps_mix_r04.py: sixteen scalar LDS writes with seven address instructions each, then four times read ->
-  //  wait -> 64-bit divide -> guarded store.  Now the sixteen offsets are three adds from precomputed pieces, the four
+  //  70c9db4:tools/labs/stamps_mix_r04.py: sixteen scalar LDS writes with seven address instructions each, then four
+  //  times read -> wait -> 64-bit divide -> guarded store.  Now the sixteen offsets are three adds from precomputed pieces, the four
   //  rows are read in one batch, and a row outside the output is dropped by the buffer's range check instead of a branch.)
   float* stg = (w < 2 ? &As[0][0] : &Bs[0][0]) + (w & 1) * 1024;
   {
@@ -758,7 +737,6 @@ __global__ __launch_bounds__(256) void k_mix(MixArgs a) {
         for (int e = 0; e < 4; ++e) stg[base + xe[e]] = acc[p][q][e];
       }
   }
-  NODE_STAMP(6);   // accumulators -> LDS
   const bool wt = a.outFloats > 0 && a.outFloats < (1L << 29);   // 32-bit byte offsets
   float* outp = a.out + (size_t)part * a.outPartStride;
   const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(outp, 0, wt ? (int)(a.outFloats * 4) : 0, 0x00020000);
@@ -774,11 +752,7 @@ __global__ __launch_bounds__(256) void k_mix(MixArgs a) {
     const float4 v = v4[u];
     const int row = row0 + wr * 32 + lrow;
     const int k = row / a.Np, n = row - k * a.Np;
-#ifdef MIX_LAB_NOSTORE   // LAB: no output (a never-true condition keeps the accumulators alive)
-    const bool ok = k < a.Ks && n < a.N && v.x == 1.2345e-30f;
-#else
     const bool ok = k < a.Ks && n < a.N;
-#endif
     const size_t off = (size_t)colTile * a.sT + (size_t)n * a.sN + (size_t)k * a.sK + wc * 32 + q * 4;
     if (wt) {
       const u32x4 bits = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
@@ -788,12 +762,6 @@ __global__ __launch_bounds__(256) void k_mix(MixArgs a) {
       *reinterpret_cast<float4*>(outp + off) = v;
     }
   }
-  NODE_STAMP(7);   // stores issued
-#ifdef NODE_LAB_STAMPS
-  __builtin_amdgcn_s_waitcnt(0);
-  NODE_STAMP(8);   // stores acknowledged
-#endif
-  NODE_STAMP_FLUSH(a);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -953,13 +921,9 @@ __global__ __launch_bounds__(256) void k_mix_n32(MixArgs a) {
   float4 ra0, rb00, rb01, ra1, rb10, rb11;   // (every request of the prologue before its first wait: see k_mix)
   {
     const float4 a0 = ldA(0), b0 = ldB0(0), b1 = ldB1(0);
-#ifndef MIX_LAB_SERIAL_PROLOGUE
     __builtin_amdgcn_sched_barrier(0);
-#endif
     ra0 = ldA(1); rb00 = ldB0(1); rb01 = ldB1(1); ra1 = ldA(2); rb10 = ldB0(2); rb11 = ldB1(2);
-#ifndef MIX_LAB_SERIAL_PROLOGUE
     __builtin_amdgcn_sched_barrier(0);
-#endif
     *reinterpret_cast<float4*>(&As[0][aPos]) = a0;
     *reinterpret_cast<float4*>(&Bs[0][bPos0]) = b0;
     *reinterpret_cast<float4*>(&Bs[0][bPos1]) = b1;

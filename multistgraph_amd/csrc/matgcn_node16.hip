@@ -8,7 +8,7 @@
 // The kernels sit at the ridge of the machine (32 FLOP per weight byte; ~100 MB per launch against ~2 GFLOP), so
 // what decides their time is whether the weight stream and the matrix pipe run AT THE SAME TIME.  Round 1 staged the
 // whole 64 x 256 A tile (64 KB) plus a ten-deep weight ring before the first MFMA: memory time and MFMA time added
-// up (21 + 17 us measured, tools/nodelab.hip).  Now the K range is walked in CHUNKS of 64 (one stack slot):
+// up (21 + 17 us measured, 70c9db4:tools/labs/nodelab.hip).  Now the K range is walked in CHUNKS of 64 (one stack slot):
 //   chunk 0 = the 64 state rows (kept in LDS to the end: z*h / the blend need them), chunks 1..Ks = the mixed slots,
 //   ping-ponging through two 16 KB LDS buffers that are fed from registers two chunks ahead of the MFMAs;
 //   the node-adaptive weights - the one big stream, 131 / 65 KB per node and step - go straight from L2 / Infinity
@@ -32,37 +32,17 @@
 
 // f32x4 / MFMA16 come from matgcn_kernels.hip (same translation unit)
 
-#ifndef NODE_MIN_WAVES
-#define NODE_MIN_WAVES 4   // __launch_bounds__ second argument: 4 waves per SIMD = a budget of 128 VGPRs (no spills).
-                           // 5 (96 VGPRs: two node waves per SIMD would fit beside five 64-VGPR graph-mix waves of the
-                           // other layer's chain) was measured in round 2: the forward got SLOWER (7.37 vs 7.17 ms) -
-                           // the spills cost more than co-residency gives, the two chains phase-lock anyway
-#endif
+constexpr int NODE_MIN_WAVES = 4;   // __launch_bounds__ second argument of k_gate16 / k_update16 (both row counts): 4 waves
+                                    // per SIMD = a budget of 128 VGPRs (no spills).  5 (96 VGPRs: two node waves per SIMD
+                                    // would fit beside five 64-VGPR graph-mix waves of the other layer's chain) was measured
+                                    // in round 2: the forward got SLOWER (7.37 vs 7.17 ms) - the spills cost more than
+                                    // co-residency gives, the two chains phase-lock anyway
 // (the weight ring of the K loop runs one 64-wide K chunk = 4 k-groups ahead of the MFMAs: 32-64 MFMAs per wave and
 // chunk, shared by up to four waves per SIMD, cover the round trip)
-#ifndef NODE_MIN_WAVES_32
-#define NODE_MIN_WAVES_32 4   // the 32-row instantiations of k_gate16 / k_update16
-#endif
-#ifndef NODE_XT_LATE
-#define NODE_XT_LATE 1              // k_update16: request the residual cell's x_t rows before the last K chunk
-#endif
-#ifndef NODE_SAVE_WT
-#define NODE_SAVE_WT 1    // the activations forward_train saves leave through write-through (sc1) stores like the outputs
-#endif
-#ifndef PX16_RING
-#define PX16_RING 4        // k_px16: two rings (two column tiles per wave)
-#endif
-#ifndef PX16_OUT_WT
-#define PX16_OUT_WT 1      // k_px16 writes PX through (sc1)
-#endif
-#ifndef PX16_PIPELINE
-#define PX16_PIPELINE 1    // k_px16 stages its A tile in K chunks under the MFMAs (0: whole tile first, the round-3 form)
-#endif
-#ifndef NODE_ROWS
-#define NODE_ROWS 64       // rows (batch items) of one (node, row block) work item of k_gate16 / k_update16: 64 or 32.
-                           // The fragment-ordered PX / R blocks stay 64-row blocks either way (a 32-row item is the
-                           // lower or upper pair of row tiles of its block).
-#endif
+constexpr int PX16_RING = 4;        // k_px16: two rings (two column tiles per wave)
+// A (node, row block) work item of k_gate16 / k_update16 covers 64 rows (batch items), or 32 where the launch asks for
+// them (ROWS).  The fragment-ordered PX / R blocks stay 64-row blocks either way (a 32-row item is the lower or upper
+// pair of row tiles of its block).
 #define NODE_PX_BLOCK 12288   // floats of one fragment-ordered PX block: 12 column tiles x 4 row tiles x 64 lanes x 4
 #define NODE_R_BLOCK 4096     // floats of one fragment-ordered R block: 4 column tiles x 4 row tiles x 64 lanes x 4
 
@@ -102,39 +82,22 @@ struct Node16Args {
   const float* dropMask;
   long dropRowStride;
   float* seqDrop;
-#ifdef NODE_LAB_STAMPS   // tools/labs/stamps_r04.py: per-wave phase stamps of this launch (NODE_STAMPS words per wave)
-  unsigned int* stamps;
-#endif
 };
 
-// (in-kernel phase stamps of the lab builds: NODE_STAMP* macros, matgcn_internal.h)
-
 // Gate non-linearities of the step kernels.  The node kernels' epilogues are VALU-bound stretches in which the matrix
-// pipe idles (round 4, tools/labs/stamps_r04.py: the 16 sigmoids per lane of k_gate16 took 8 200 cycles with two
+// pipe idles (round 4, 70c9db4:tools/labs/stamps_r04.py: the 16 sigmoids per lane of k_gate16 took 8 200 cycles with two
 // workgroups on a CU): the IEEE expf + division of `1 / (1 + expf(-x))` is 26 VALU instructions, tanhf 30.  These forms
 // are 4 and 15: v_exp_f32 / v_rcp_f32 (1 ulp each); tanh keeps its RELATIVE accuracy near 0 with the odd series below
 // |x| = 0.25 (next term 9e-9 relative there) and (1 - t) / (1 + t), t = exp(-2|x|), above it (<= 3 ulp).
-// NODE_PRECISE_GATES=1 restores the libm forms (A/B builds).
-#ifndef NODE_PRECISE_GATES
-#define NODE_PRECISE_GATES 0
-#endif
 __device__ __forceinline__ float sigmoid16(float x) {
-#if NODE_PRECISE_GATES
-  return 1.0f / (1.0f + expf(-x));
-#else
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * x));
-#endif
 }
 __device__ __forceinline__ float tanh16(float x) {
-#if NODE_PRECISE_GATES
-  return tanhf(x);
-#else
   const float ax = fabsf(x), x2 = x * x;
   const float t = __builtin_amdgcn_exp2f(-2.88539008177792681472f * ax);
   const float big = (1.0f - t) * __builtin_amdgcn_rcpf(1.0f + t);
   const float small = ax * (1.0f + x2 * (-0.333333333f + x2 * (0.133333333f + x2 * (-0.0539682540f + x2 * 0.0218694885f))));
   return copysignf(ax < 0.25f ? small : big, x);
-#endif
 }
 
 // keep v where ok, else zeros - element-wise, so the float4 stays in registers (a ?: on the structs would
@@ -155,14 +118,10 @@ __device__ __forceinline__ void store_wt16(float* base, size_t off, const float4
   __builtin_amdgcn_raw_buffer_store_b128(bits, rsrc, (int)(off * 4), 0, 16);   // aux 16 = sc1
 }
 
-// a saved activation (forward_train): nothing reads it before the backward, milliseconds later.  Written through as well
-// (NODE_SAVE_WT): a plain store leaves a dirty line in this XCD's L2 for the flush at the end of the kernel
+// a saved activation (forward_train): nothing reads it before the backward, milliseconds later.  Written through as well:
+// a plain store leaves a dirty line in this XCD's L2 for the flush at the end of the kernel
 __device__ __forceinline__ void save16(float* base, size_t off, const float4& v) {
-#if NODE_SAVE_WT
   store_wt16(base, off, v);
-#else
-  *reinterpret_cast<float4*>(base + off) = v;
-#endif
 }
 
 // position (in floats) of element (row, col) of a swizzled [.][16*blocks slots] tile with `spr` slots per row
@@ -247,9 +206,6 @@ __device__ __forceinline__ void chunk_mfma(const float* buf, int rt0, int j, int
                                            f32x4 (&acc)[NRT]) {
   typedef typename NodeOp<BF>::T Op;
   if (PREFETCH) {
-#ifdef NODE_LAB_NO_WEIGHTS   // tools/labs/nodelab2.hip: every k-group re-reads the node's first one (an L1 hit)
-    gNext = 0; gLast = 0;
-#endif
 #pragma unroll
     for (int gl = 0; gl < 4; ++gl) wr[PAR ^ 1][gl] = wp[(size_t)min(gNext + gl, gLast) * gStride];
     // the scheduler would otherwise sink these loads below the chunk's MFMAs to shorten their live ranges
@@ -266,10 +222,6 @@ __device__ __forceinline__ void chunk_mfma(const float* buf, int rt0, int j, int
 #pragma unroll
       for (int q = 0; q < NRT; ++q) acc[q] = MFMA16BF(as_bf16x4(av[q]), as_bf16x4(wv), acc[q]);
     } else {
-#ifdef NODE_LAB_NO_MFMA   // tools/labs/nodelab2.hip: the same operand traffic without the matrix pipe
-#pragma unroll
-      for (int q = 0; q < NRT; ++q) acc[q][0] += av[q].x * wv.x + av[q].y * wv.y + av[q].z * wv.z + av[q].w * wv.w;
-#else
 #pragma unroll
       for (int q = 0; q < NRT; ++q) acc[q] = MFMA16(av[q].x, wv.x, acc[q]);
 #pragma unroll
@@ -278,7 +230,6 @@ __device__ __forceinline__ void chunk_mfma(const float* buf, int rt0, int j, int
       for (int q = 0; q < NRT; ++q) acc[q] = MFMA16(av[q].z, wv.z, acc[q]);
 #pragma unroll
       for (int q = 0; q < NRT; ++q) acc[q] = MFMA16(av[q].w, wv.w, acc[q]);
-#endif
     }
   }
 }
@@ -299,7 +250,7 @@ __device__ __forceinline__ void chunk_mfma(const float* buf, int rt0, int j, int
 template <int ROWS, int NRT, bool BF, typename Late>
 __device__ __forceinline__ void node_k_loop(const Node16Args& a, int n, int rowBase, float* Hs, float* Gb, int rt0, int j,
                                             int kq, const typename NodeOp<BF>::T* wp, size_t gStride, f32x4 (&acc)[NRT],
-                                            Late&& late NODE_STAMP_PARAM) {
+                                            Late&& late) {
   constexpr int NS = ROWS / 32, CH = ROWS * 64;      // float4 per thread and chunk; floats of one LDS chunk
   const int Ks = a.Ks, gLast = 4 * (1 + Ks) - 1;
   const ChunkStage<ROWS> cs = chunk_stage<ROWS>(a, n, rowBase);
@@ -320,44 +271,32 @@ __device__ __forceinline__ void node_k_loop(const Node16Args& a, int n, int rowB
   //  vector-memory issue queue before this point - changed nothing: 6.75 vs 6.74 ms, profiles/r04_node_epilogue_lab.log)
 #pragma unroll
   for (int q = 0; q < NRT; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-  NODE_STAMP(1);   // requests issued
   chunk_store<ROWS, BF>(Hs, cs, hS);
-  NODE_STAMP(2);   // state rows arrived and stored
   __syncthreads();
-  NODE_STAMP(3);
   if (Ks > 0) {
     chunk_mfma<NRT, 0, true, BF>(Hs, rt0, j, kq, wr, wp, gStride, 4, gLast, acc);
-    NODE_STAMP(4);   // chunk 0 issued
     chunk_store<ROWS, BF>(Gb, cs, st[1]);
     if (Ks > 1) chunk_store<ROWS, BF>(Gb + CH, cs, st[0]);
     chunk_load<ROWS>(cs, Ks, 3, st[1]);
     chunk_load<ROWS>(cs, Ks, 4, st[0]);
-    NODE_STAMP(5);   // chunks 1, 2 arrived and stored
     __syncthreads();
-    NODE_STAMP(6);
     for (int c = 1; c < Ks; c += 2) {
       // odd chunk c (not the last) in Gb[0]; afterwards Gb[0] <- chunk c+2 (waiting in st[1])
       chunk_mfma<NRT, 1, true, BF>(Gb, rt0, j, kq, wr, wp, gStride, 4 * (c + 1), gLast, acc);
-      NODE_STAMP(7);   // (the last odd chunk's)
       __syncthreads();
-      NODE_STAMP(8);
       if (c + 2 <= Ks) chunk_store<ROWS, BF>(Gb, cs, st[1]);
       chunk_load<ROWS>(cs, Ks, c + 4, st[1]);
       if (c + 1 < Ks) {  // even chunk c+1 (not the last) in Gb[1]; afterwards Gb[1] <- chunk c+3 (waiting in st[0])
         chunk_mfma<NRT, 0, true, BF>(Gb + CH, rt0, j, kq, wr, wp, gStride, 4 * (c + 2), gLast, acc);
-        NODE_STAMP(9);
         __syncthreads();
-        NODE_STAMP(10);
         if (c + 3 <= Ks) chunk_store<ROWS, BF>(Gb + CH, cs, st[0]);
         chunk_load<ROWS>(cs, Ks, c + 5, st[0]);
       }
     }
   }
   late();
-  NODE_STAMP(11);  // late requests issued
   if (Ks & 1) chunk_mfma<NRT, 1, false, BF>(Gb, rt0, j, kq, wr, wp, gStride, 0, gLast, acc);               // odd last chunk
   else chunk_mfma<NRT, 0, false, BF>(Ks > 0 ? Gb + CH : Hs, rt0, j, kq, wr, wp, gStride, 0, gLast, acc);  // even (or chunk 0)
-  NODE_STAMP(12);  // last chunk issued
 }
 
 // layer-0 x part: acc[q] += XA[rows of tile rt0+q][16 gx .. +16] . Wx[gx]; A fragments come straight from global
@@ -404,11 +343,8 @@ inline unsigned node_items(int N, int rows, int blockRows) {
 
 // ---- gate AGCN + sigmoid + z*h (MultiATGCN.py:122-125) -----------------------------------------------------
 // wave w = column tile w of 8 (0..3: z, 4..7: r), all ROWS/16 row tiles.  LDS 3 chunks of ROWS x 64 floats: Hs | Gb[2]
-#ifndef NODE_MIN_WAVES_GATE
-#define NODE_MIN_WAVES_GATE NODE_MIN_WAVES
-#endif
 template <bool SAVE, int ROWS, bool BF = false>
-__global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES_GATE : NODE_MIN_WAVES_32) void k_gate16(Node16Args a) {
+__global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_gate16(Node16Args a) {
   typedef typename NodeOp<BF>::T Op;
   static_assert(!(SAVE && BF), "the training forward runs fp32 operands");
   constexpr int NRT = ROWS / 16, CH = ROWS * 64;
@@ -426,8 +362,6 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES_GATE : NODE_MIN_WA
   f32x4 acc[NRT];
   float4 pxv[NRT];               // hoisted pre-activation (x rows + bias) in fragment order, added in the epilogue
   float hz[BF ? NRT : 1][4];     // BF: the fp32 state values of z*h (the LDS copy is rounded to bf16), requested late
-  NODE_STAMP_DECL
-  NODE_STAMP(0);
   node_k_loop<ROWS, NRT, BF>(a, n, rowBase, Hs, Gb, 0, j, kq, wp, gStride, acc, [&]() {
     if constexpr (BF) {
       if (w < 4) {
@@ -447,12 +381,11 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES_GATE : NODE_MIN_WA
       for (int rt = 0; rt < NRT; ++rt) pxv[rt] = make_float4(0.f, 0.f, 0.f, 0.f);
       x_groups<NRT, BF>(a, n, rowBase, 0, wp + (size_t)nG * gStride, gStride, j, kq, acc);
     }
-  } NODE_STAMP_ARG);
+  });
 #pragma unroll
   for (int rt = 0; rt < NRT; ++rt) {
     acc[rt][0] += pxv[rt].x; acc[rt][1] += pxv[rt].y; acc[rt][2] += pxv[rt].z; acc[rt][3] += pxv[rt].w;
   }
-  NODE_STAMP(13);  // accumulators + PX ready
   // epilogue: zr = sigmoid(.);  r leaves in fragment order straight from the accumulators (the update kernel of
   // this node reads it back the same way); z is gathered as a [ROWS][64] tile in LDS (the chunk buffers are dead once
   // every wave has left the K loop), and z*h leaves as whole 256-byte rows of the next mix's operand: the row sweep
@@ -462,7 +395,6 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES_GATE : NODE_MIN_WA
   // are independent, and the LDS sees 16 scalar writes and 2 wide reads per thread.  The training instantiation keeps
   // an r tile too and saves z and r as float4 rows instead of 64-byte pieces.)
   __syncthreads();
-  NODE_STAMP(14);
   float* Zt = Gb;                // z tile (BF: z*h, the LDS state copy is bf16 there)
   float* Rt = Gb + CH;           // SAVE: r tile
   const int o = 16 * w + j;
@@ -500,9 +432,7 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES_GATE : NODE_MIN_WA
         for (int e = 0; e < 4; ++e) Rt[swz(rt * 16 + 4 * kq + e, o - 64, 16)] = acc[rt][e];
     }
   }
-  NODE_STAMP(15);  // sigmoids done, tiles in LDS
   __syncthreads();
-  NODE_STAMP(16);
 #pragma unroll
   for (int it = 0; it < ROWS / 32; ++it) {          // ROWS rows x 16 slots float4 over 512 threads
     const int lb = (tid >> 4) + 32 * it, q = tid & 15, b = rowBase + lb;
@@ -520,12 +450,6 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES_GATE : NODE_MIN_WA
       save16(a.svR, ((size_t)b * a.Np + n) * 64 + q * 4, *reinterpret_cast<const float4*>(&Rt[at]));
     }
   }
-  NODE_STAMP(17);  // stores issued
-#ifdef NODE_LAB_STAMPS
-  __builtin_amdgcn_s_waitcnt(0);   // every store of this wave acknowledged
-  NODE_STAMP(18);
-#endif
-  NODE_STAMP_FLUSH(a);
 }
 
 // ---- hoisted x part of layers >= 1: PX[t][n][rb] = bias[n] + [x | mix_k(x)] . Wx[n], fragment order ---------------
@@ -541,43 +465,6 @@ struct Px16Args {
   float* pxOut;          // [steps][N][RB][12][4][64][4] slice of PX
   int steps, N, Np, Ks, B;
 };
-
-// stage the whole 64-row A tile of a (node, step, row block): Hs <- x rows (16 slots), Gs <- G rows (16*Ks slots)
-__device__ __forceinline__ void stage_node_tile(const Node16Args& a, int n, int rowBase, float* Hs, float* Gs) {
-  const ChunkStage<64> cs = chunk_stage<64>(a, n, rowBase);
-  float4 hS[2];
-  hS[0] = *reinterpret_cast<const float4*>(a.s + ((size_t)cs.g[0] * a.Np + n) * 64 + cs.sq * 4);
-  hS[1] = *reinterpret_cast<const float4*>(a.s + ((size_t)cs.g[1] * a.Np + n) * 64 + cs.sq * 4);
-  const int rA = cs.srow, rB = cs.srow + 32;
-  const int pA = cs.sq ^ (rA & 15), pB = cs.sq ^ (rB & 15);
-  const int spr = cs.spr;
-  if (a.Ks == 0) chunk_store<64>(Hs, cs, hS);
-  for (int k0 = 0; k0 < a.Ks; k0 += 4) {
-    float4 vAk[4], vBk[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const int k = min(k0 + kk, a.Ks - 1);
-      vAk[kk] = cs.gsrc[(size_t)cs.g[0] * spr + k * 16 + cs.sq];
-      vBk[kk] = cs.gsrc[(size_t)cs.g[1] * spr + k * 16 + cs.sq];
-    }
-    if (k0 == 0) chunk_store<64>(Hs, cs, hS);
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      if (k0 + kk < a.Ks) {
-        *reinterpret_cast<float4*>(&Gs[(rA * spr + (k0 + kk) * 16 + pA) * 4]) = keep4(cs.v[0], vAk[kk]);
-        *reinterpret_cast<float4*>(&Gs[(rB * spr + (k0 + kk) * 16 + pB) * 4]) = keep4(cs.v[1], vBk[kk]);
-      }
-    }
-  }
-}
-
-// A fragment of row tile rt for k-group g (g < 4: the x slots, else the mixed slots) of the whole-tile layout
-__device__ __forceinline__ float4 a_frag(const float* Hs, const float* Gs, int Ks, int rt, int g, int i, int kq) {
-  const int row = rt * 16 + i;
-  if (g < 4) return *reinterpret_cast<const float4*>(&Hs[(row * 16 + ((4 * g + kq) ^ i)) * 4]);
-  const int q = 4 * (g - 4) + kq;
-  return *reinterpret_cast<const float4*>(&Gs[(row * 16 * Ks + ((q & ~15) | ((q ^ i) & 15))) * 4]);
-}
 
 // NRT: 16-row tiles of the 64-row block that hold batch rows (4; 2 / 1 for batches of at most 32 / 16 rows - the reference
 // ships batch_size 16, where three of the four row tiles were padding: 64 us per launch at ANY batch size until round 4)
@@ -615,7 +502,6 @@ __global__ __launch_bounds__(512, 4) void k_px16(Px16Args p) {
   const float b0 = p.bias[(size_t)n * 192 + o0], b1 = two ? p.bias[(size_t)n * 192 + o1] : 0.f;
   __builtin_amdgcn_sched_barrier(0);
   f32x4 acc0[NRT], acc1[NRT];
-#if PX16_PIPELINE
   // the A tile goes through LDS in 16 KB K chunks (chunk 0 = the x rows, chunk c = mixed slot c-1) on the schedule of
   // node_k_loop: chunk c+2 is written to LDS and chunk c+4 requested while chunk c feeds the matrix pipe - the tile's
   // 64 KB no longer arrive before the first MFMA.  Both weight rings keep their one-chunk lead (refilled as consumed).
@@ -695,47 +581,7 @@ __global__ __launch_bounds__(512, 4) void k_px16(Px16Args p) {
   }
   if (Ks & 1) chunk(Gb, Ks);
   else chunk(Ks > 0 ? Gb + CH : Hs, Ks);
-#else
-  static_assert(!BF, "the bf16 form exists for the chunked A tile only");
-  stage_node_tile(a, n, rowBase, Hs, Gs);
-#pragma unroll
-  for (int rt = 0; rt < NRT; ++rt) { acc0[rt] = f32x4{b0, b0, b0, b0}; acc1[rt] = f32x4{b1, b1, b1, b1}; }
-  __syncthreads();
-  for (int g0 = 0; g0 < nG; g0 += PX16_RING) {
-#pragma unroll
-    for (int r = 0; r < PX16_RING; ++r) {
-      const int g = g0 + r;
-      const float4 wv0 = wr0[r], wv1 = wr1[r];
-      wr0[r] = wp0[(size_t)min(g + PX16_RING, nG - 1) * 12 * 64];
-      wr1[r] = wp1[(size_t)min(g + PX16_RING, nG - 1) * 12 * 64];
-      if (g < nG) {
-        float4 av[NRT];
-#pragma unroll
-        for (int rt = 0; rt < NRT; ++rt) av[rt] = a_frag(Hs, Gs, p.Ks, rt, g, j, kq);
-#pragma unroll
-        for (int rt = 0; rt < NRT; ++rt) acc0[rt] = MFMA16(av[rt].x, wv0.x, acc0[rt]);
-#pragma unroll
-        for (int rt = 0; rt < NRT; ++rt) acc0[rt] = MFMA16(av[rt].y, wv0.y, acc0[rt]);
-#pragma unroll
-        for (int rt = 0; rt < NRT; ++rt) acc0[rt] = MFMA16(av[rt].z, wv0.z, acc0[rt]);
-#pragma unroll
-        for (int rt = 0; rt < NRT; ++rt) acc0[rt] = MFMA16(av[rt].w, wv0.w, acc0[rt]);
-        if (two) {
-#pragma unroll
-          for (int rt = 0; rt < NRT; ++rt) acc1[rt] = MFMA16(av[rt].x, wv1.x, acc1[rt]);
-#pragma unroll
-          for (int rt = 0; rt < NRT; ++rt) acc1[rt] = MFMA16(av[rt].y, wv1.y, acc1[rt]);
-#pragma unroll
-          for (int rt = 0; rt < NRT; ++rt) acc1[rt] = MFMA16(av[rt].z, wv1.z, acc1[rt]);
-#pragma unroll
-          for (int rt = 0; rt < NRT; ++rt) acc1[rt] = MFMA16(av[rt].w, wv1.w, acc1[rt]);
-        }
-      }
-    }
-  }
-#endif
   // the accumulators leave as they are: one 1 KB wave row per (column tile, row tile)
-#if PX16_OUT_WT
   // written through (sc1) like every other producer -> consumer buffer of the step kernels: the 39 MB a chunk's launch
   // produces leave the L2s while it runs, not as dirty lines at its end (this (node, step, row block)'s 48 KB block is the
   // wave-uniform base, so the lane offsets stay small at any N)
@@ -746,14 +592,6 @@ __global__ __launch_bounds__(512, 4) void k_px16(Px16Args p) {
     if (two)
       store_wt16(pxb, (((size_t)(w + 8) * 4 + rt) * 64 + lane) * 4, make_float4(acc1[rt][0], acc1[rt][1], acc1[rt][2], acc1[rt][3]));
   }
-#else
-  float4* dst = reinterpret_cast<float4*>(p.pxOut) + (((size_t)tl * p.N + n) * RB + rb) * (NODE_PX_BLOCK / 4) + lane;
-#pragma unroll
-  for (int rt = 0; rt < NRT; ++rt) {
-    dst[((size_t)w * 4 + rt) * 64] = make_float4(acc0[rt][0], acc0[rt][1], acc0[rt][2], acc0[rt][3]);
-    if (two) dst[((size_t)(w + 8) * 4 + rt) * 64] = make_float4(acc1[rt][0], acc1[rt][1], acc1[rt][2], acc1[rt][3]);
-  }
-#endif
 }
 
 // ---- update AGCN + tanh + GRU blend, fused with the residual GRU cell and the per-step blend ------------------
@@ -764,7 +602,7 @@ __global__ __launch_bounds__(512, 4) void k_px16(Px16Args p) {
 // byte once).  The residual cell then runs two small GEMMs on tiles that never leave LDS.
 // LDS 4 chunks of ROWS x 64 floats: Hs | Gb[2] | X
 template <int MODE, bool SAVE, int ROWS, bool BF = false>
-__global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES : NODE_MIN_WAVES_32) void k_update16(Node16Args a) {
+__global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_update16(Node16Args a) {
   typedef typename NodeOp<BF>::T Op;
   constexpr int NRT = ROWS / 16, NR2 = ROWS / 32, NS = ROWS / 32, CH = ROWS * 64;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -785,7 +623,6 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES : NODE_MIN_WAVES_3
   const int ct = w & 3, rh = w >> 2;
   const int srow = tid >> 4, sq = tid & 15;   // staging coordinates: 32 rows x 16 slots per sweep
   const int o4 = 16 * ct + j;                 // column of this lane in a 64-wide tile
-  NODE_STAMP_DECL
   // the residual cell's x_t rows of this thread's staging slots (zero padded to Cpad); MODE 1 requests them before the
   // last K chunk - requested after the update's epilogue, their whole memory latency sat between two barriers with the
   // matrix pipe idle (round 4 stamps: 10 k cycles for that stretch)
@@ -819,7 +656,6 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES : NODE_MIN_WAVES_3
     // the previous state row-major
     float4 pxv[NR2], rv[NR2];
     float hv[NR2][4];
-    NODE_STAMP(0);
     node_k_loop<ROWS, NR2, BF>(a, n, rowBase, Hs, Gb, NR2 * rh, j, kq, wp, gStride, acc, [&]() {
       if (a.px) {
         const float4* pf = reinterpret_cast<const float4*>(a.px) +
@@ -841,17 +677,13 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES : NODE_MIN_WAVES_3
           const int b = min(rowBase + (NR2 * rh + q) * 16 + 4 * kq + e, a.rows - 1);
           hv[q][e] = a.h[((size_t)b * a.Np + n) * 64 + o4];
         }
-#if NODE_XT_LATE
       if (MODE == 1) request_xt();
-#endif
-    } NODE_STAMP_ARG);
+    });
 #pragma unroll
     for (int q = 0; q < NR2; ++q) {
       acc[q][0] += pxv[q].x; acc[q][1] += pxv[q].y; acc[q][2] += pxv[q].z; acc[q][3] += pxv[q].w;
     }
-    NODE_STAMP(13);
     __syncthreads();   // every wave is out of the K loop: Hs (z*h) may be overwritten by h'
-    NODE_STAMP(14);
 #pragma unroll
     for (int q = 0; q < NR2; ++q)
 #pragma unroll
@@ -882,7 +714,7 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES : NODE_MIN_WAVES_3
   // ---- residual GRU cell on [x_t | h'] (MultiATGCN.py:142-150) ----
   const int ngx = a.Cpad >> 4;                     // x groups of the residual GEMMs (1 or 4)
   const int nG1 = ngx + 4;                         // <= 8
-  if (MODE != 1 || !NODE_XT_LATE) request_xt();
+  if (MODE != 1) request_xt();
 #pragma unroll
   for (int it = 0; it < NS; ++it) {   // x_t tile (zero padded to Cpad)
     const int rr = srow + 32 * it;
@@ -899,9 +731,7 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES : NODE_MIN_WAVES_3
   }
   const float bg = a.rgb[16 * w + j], bu = a.rub[o4];
   const float gate = a.blend ? sigmoid_f(a.blend[0]) : 0.f;   // g = sigmoid(weights_gru[l][t]) (:208); the backward's form
-  NODE_STAMP(15);  // tanh + blend done, h' and x_t tiles stored
   __syncthreads();
-  NODE_STAMP(16);
   if constexpr (SAVE && MODE == 1) {   // hc rows -> training buffer (SV is rewritten only behind the NEXT barrier)
 #pragma unroll
     for (int it = 0; it < NS; ++it) {
@@ -966,9 +796,7 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES : NODE_MIN_WAVES_3
         for (int e = 0; e < 4; ++e) R2[swz(rt * 16 + 4 * kq + e, o - 64, 16)] = acc1[rt][e];
     }
   }
-  NODE_STAMP(17);  // residual GEMM 1 + sigmoids
   __syncthreads();
-  NODE_STAMP(18);
   if constexpr (SAVE) {   // every thread is past its hc rows: SV <- z2 (kept in the z2 waves' accumulators)
     if (w < 4) {
       const int o = 16 * w + j;
@@ -1004,7 +832,6 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES : NODE_MIN_WAVES_3
   }
   // the new state is gathered as a [ROWS][64] tile in LDS (over x_t, dead once every wave has left GEMM 2) and
   // written to the state and to Seq_l[t] as whole 256-byte rows
-  NODE_STAMP(19);  // residual GEMM 2 issued
   __syncthreads();
   float* Out = XT;
   float* HC2t = ZH2;             // SAVE: hc2 tile (z2*h' is dead once every wave has left GEMM 2)
@@ -1033,7 +860,6 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES : NODE_MIN_WAVES_3
         Out[swz(lb, o4, 16)] = a.blend ? (gate * hp + (1.0f - gate) * res) : res;
       }
   }
-  NODE_STAMP(20);  // tanh + blends
   __syncthreads();
 #pragma unroll
   for (int it = 0; it < NS; ++it) {                 // ROWS rows x 16 slots float4 over 512 threads
@@ -1055,11 +881,6 @@ __global__ __launch_bounds__(512, ROWS == 64 ? NODE_MIN_WAVES : NODE_MIN_WAVES_3
       }
     }
   }
-#ifdef NODE_LAB_STAMPS
-  __builtin_amdgcn_s_waitcnt(0);
-  NODE_STAMP(21);
-#endif
-  NODE_STAMP_FLUSH(a);
 }
 
 // bf16 copy of a fragment-ordered weight stream (same indexing, half the bytes): 8 floats per thread

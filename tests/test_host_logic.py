@@ -118,7 +118,7 @@ def test_unsupported_options_fail_loudly():
         m.predict({"X": torch.from_numpy(c.x)})      # CPU tensor: no fallback
 
 
-def test_library_exports_every_declared_symbol(lib_built):
+def test_library_exports_every_declared_symbol_of_abi_12(lib_built):
     from multistgraph_amd import _lib
     header = open(os.path.join(ROOT, "include", "matgcn.h")).read()
     declared = set(re.findall(r"\b(matgcn_[a-z_0-9]+)\s*\(", header))
@@ -126,7 +126,7 @@ def test_library_exports_every_declared_symbol(lib_built):
     lib = _lib.load()
     for sym in declared:
         assert hasattr(lib, sym)
-    assert lib.matgcn_abi_version() == _lib.ABI_VERSION == 11
+    assert lib.matgcn_abi_version() == _lib.ABI_VERSION == 12
     assert lib.matgcn_error_string(-3) == b"configuration not supported by this build"
 
 
@@ -230,7 +230,7 @@ def test_same_seed_gives_the_reference_initial_weights(name, extra):
                 "%s differs for seed %d" % (k, seed)
 
 
-def test_header_is_plain_c_and_links_against_the_library(tmp_path, lib_built):
+def test_abi_12_header_is_plain_c_and_links_against_the_library(tmp_path, lib_built):
     """include/matgcn.h is the drop-in boundary: it must compile as plain C (C99, -pedantic) and a C program that only
     includes it must link against libmatgcn.so and run the GPU-free entry points (status codes, sizes, argument checks)"""
     import shutil
@@ -250,7 +250,7 @@ int main(void) {
   if (matgcn_prepared_bytes(&d, &bytes) == MATGCN_OK) return 2;            /* all-zero dims are refused */
   if (matgcn_prepared_bytes(&d, NULL) != MATGCN_ERR_NULL) return 3;
   if (!matgcn_error_string(MATGCN_ERR_BAD_ARG)) return 4;
-  if (matgcn_set_batch_split(0) != 0 || matgcn_set_mix_precision(0) != 0) return 5;
+  if (matgcn_set_mix_precision(0) != 0) return 5;
   if (matgcn_set_stream_pool(0) != MATGCN_OK) return 6;                     /* the default mode, before any stream exists */
   printf("abi %d ok\\n", matgcn_abi_version());
   return 0;
@@ -263,7 +263,7 @@ int main(void) {
                     "-L", libdir, "-lmatgcn", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"], check=True)
     env = dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True, env=env)
-    assert "abi 11 ok" in out.stdout
+    assert "abi 12 ok" in out.stdout
 
 
 def test_bench_flop_models_are_consistent():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Lab helper: time the forward (and optionally the training step) of a bench workload in THIS process' library
-configuration (env knobs such as MATGCN_CU_SPLIT / MATGCN_LIB are read by the library at first use).
+configuration (MATGCN_POOL=1: the stream-pool mode of the data-parallel jobs).
     python tools/fwd_time.py [--workload bm403] [--iters 60] [--train] [--tag text]"""
 import argparse
 import os
@@ -21,9 +21,7 @@ def main():
     ap.add_argument("--train", action="store_true")
     ap.add_argument("--serial", action="store_true")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override (16 = the reference's shipped batch_size)")
-    ap.add_argument("--token", action="store_true", help="matgcn_set_wavefront(2): the graph mixes of all chains in one global order")
     ap.add_argument("--cache-prepared", action="store_true")
-    ap.add_argument("--split", type=int, default=0, help="matgcn_set_batch_split(n)")
     ap.add_argument("--kernels", action="store_true", help="per-kernel launch averages, wavefront off (HIP events)")
     ap.add_argument("--tag", default="")
     args = ap.parse_args()
@@ -38,10 +36,6 @@ def main():
         _lib.check(_lib.load().matgcn_set_stream_pool(1), "matgcn_set_stream_pool")
     if args.serial:
         _lib.load().matgcn_set_wavefront(0)
-    if args.token:
-        _lib.load().matgcn_set_wavefront(2)
-    if args.split:
-        _lib.load().matgcn_set_batch_split(args.split)
     x_np, y_np = syn.make_batch_arrays(w["batch"], w["nodes"], w["out"], 0, feat=2)
     batch = {"X": torch.from_numpy(x_np).to(dev), "y": torch.from_numpy(y_np).to(dev)}
     with torch.no_grad():
