@@ -119,10 +119,10 @@ typedef struct matgcn_params { /* device pointers, names = the reference state_d
 int matgcn_abi_version(void);
 const char* matgcn_error_string(int status);
 
-/* Bytes of the two caller-owned device buffers for `dims`.  matgcn_workspace_bytes depends on ONE library setting: while
- * matgcn_set_mix_precision(2) is in force it also counts the bf16 copies of the recurrent weight streams (half the bytes of
- * the fp32 streams, behind everything else); a mode-2 forward on a workspace sized without them returns
- * MATGCN_ERR_SMALL_BUFFER (ask again and re-allocate).  The fp32 product path and training never pay for them. */
+/* Bytes of the two caller-owned device buffers for `dims`.  matgcn_workspace_bytes depends on two library settings: while
+ * matgcn_set_mix_precision(2) or matgcn_set_train_precision(2) is in force it also counts the bf16 copies of the recurrent
+ * weight streams (half the bytes of the fp32 streams, behind everything else); a mode-2 forward on a workspace sized
+ * without them returns MATGCN_ERR_SMALL_BUFFER (ask again and re-allocate).  The fp32 paths never pay for them. */
 int matgcn_prepared_bytes(const matgcn_dims* dims, size_t* bytes);
 int matgcn_workspace_bytes(const matgcn_dims* dims, size_t* bytes);
 
@@ -391,10 +391,35 @@ int matgcn_prepare_join(void* stream);
  * a step), the rows [s | mix(s)] / [x | mix(x)] are rounded on their way into LDS, fp32 accumulation; the state, the
  * layer-0 x part, the residual cell and every epilogue stay fp32.
  * Both are NARROWER than the reference's fp32 arithmetic: measured max-normalised deviation from the fp32 path <= 3e-3
- * (mode 1) at N = 403 (tests/test_hip_parity.py::test_bf16_mix_variant holds both modes to 5e-3).  matgcn_prepare, the
- * training entry points and the unit entry points always use fp32 operands.  Returns the previous setting; 0 (default)
- * = fp32. */
+ * (mode 1) at N = 403 (tests/test_hip_parity.py::test_bf16_mix_variant holds both modes to 5e-3).  Governs
+ * matgcn_forward / matgcn_forward_series only: matgcn_prepare and the unit entry points always use fp32 operands, the
+ * training entry points follow matgcn_set_train_precision.  Returns the previous setting; 0 (default) = fp32; any other
+ * value means 0. */
 int matgcn_set_mix_precision(int mode);
+
+/* The same modes for the training entry points (matgcn_forward_train, matgcn_backward); 0 (default) = fp32, any other
+ * value means 0; returns the previous setting.  The two settings are independent (a model can train in bf16 and
+ * evaluate in fp32).
+ *   matgcn_forward_train runs the kernels of the inference forward of that mode - mode >= 1: bf16 operands for the
+ *   graph mixes (the mixed rows it saves for the weight gradients are their fp32 outputs); mode 2: also for the
+ *   node-wise contractions of the recurrent step and of the hoisted x part of layers >= 1 (bf16 copies of the weight
+ *   streams, made once per call in the workspace).  The saved activations, the state, the residual cell and every
+ *   epilogue stay fp32.
+ *   matgcn_backward, mode >= 1: the transposed graph mixes (the chain's two per step and layer, the x columns of the
+ *   last step and of layer 0) take bf16 operands with fp32 accumulation; mode 2: also the node-wise data-gradient
+ *   contractions (the h columns of both AGCNs in the chain, the x columns of the layers), from bf16 copies of the plain
+ *   folded weights that matgcn_forward_train makes in the train buffer.  Every parameter-gradient product, the
+ *   gradients themselves and everything in memory stay fp32.
+ * Contract between the two calls: matgcn_backward FOLLOWS the mode its matching matgcn_forward_train ran with (the library
+ * remembers it per train buffer), whatever the setting is when the backward is called - a mode switch between the two
+ * never mixes kernels of two modes.  A backward on a train buffer whose last forward_train failed returns
+ * MATGCN_ERR_BAD_ARG; one the library has no record of runs with the current setting.
+ * matgcn_workspace_bytes counts the bf16 weight-stream copies while either setting is 2; a mode-2 forward_train on a
+ * workspace sized without them returns MATGCN_ERR_SMALL_BUFFER (ask again and re-allocate); likewise matgcn_train_bytes
+ * counts the bf16 weight copies of the backward while matgcn_set_train_precision(2) is set, and a mode-2 forward_train /
+ * backward on a train buffer without them returns MATGCN_ERR_SMALL_BUFFER.  Measured gap to the reference's autograd: <= 1.4e-2 max-normalised per gradient tensor
+ * (tests/test_train_precision.py holds both modes to 2.7e-2; figures in DESIGN.md section 5). */
+int matgcn_set_train_precision(int mode);
 
 /* ---- measurement hooks (bench.py; not on the hot path) ---------------------------------------
  * Time individual kernel launches in situ with HIP events recorded on the caller's stream.

@@ -118,7 +118,12 @@ int mix_transposed(const Bwd& b, const float* src, int rows, int Cc, float* dst,
     }
     if ((rows & 1) == 0) {   // 32-row x 128-column tiles: 3 % row padding instead of 10 %, 4.9 workgroups per CU (k_mix_n32)
       a.nRowTiles = (P.N + 31) / 32;
-      hipLaunchKernelGGL(k_mix_n32, dim3((unsigned)(a.nRowTiles * (rows / 2)), (unsigned)a.parts), dim3(256), 0, b.c.s, a);
+      const dim3 grid((unsigned)(a.nRowTiles * (rows / 2)), (unsigned)a.parts);
+      // training precision mode >= 1 (matgcn_set_train_precision): bf16 operands, fp32 accumulation
+      if (g_tmix_bf16_now) hipLaunchKernelGGL(k_mix_n32<true>, grid, dim3(256), 0, b.c.s, a);
+      else hipLaunchKernelGGL(k_mix_n32<false>, grid, dim3(256), 0, b.c.s, a);
+    } else if (g_tmix_bf16_now) {
+      hipLaunchKernelGGL(k_mix_bf16<2>, dim3((unsigned)(a.nRowTiles * rows), (unsigned)a.parts), dim3(256), 0, b.c.s, a);
     } else {
       hipLaunchKernelGGL(k_mix<2>, dim3((unsigned)(a.nRowTiles * rows), (unsigned)a.parts), dim3(256), 0, b.c.s, a);
     }
@@ -153,14 +158,16 @@ int node_gemm_transposed(const Bwd& b, const float* dPre, int O, const float* Wp
 // output block - 627 MB for the 23 x-column steps of a layer at BM / B = 64 - is written once instead of written, read
 // and written again)
 int node_contract(const Bwd& b, const float* dPreG, const float* WpG, const float* dPreU, const float* WpU, int I,
-                  int iOfs, int rows, float* dA, float beta) {
+                  int iOfs, int rows, float* dA, float beta, bool bf = false) {
   const Plan& P = b.c.P;
   ChainNodeArgs cn;
   memset(&cn, 0, sizeof(cn));
   cn.dPre = dPreG; cn.Wp = WpG; cn.dPre2 = dPreU; cn.Wp2 = WpU; cn.dA = dA; cn.I = I; cn.iOfs = iOfs; cn.rows = rows;
   cn.N = P.N; cn.Np = P.Np; cn.S = b.c.R.S; cn.beta = beta;
   const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)P.N);
-  hipLaunchKernelGGL((k_chain_node<false, 192>), grid, dim3(512), 0, b.c.s, cn);
+  // bf (training precision mode 2): WpG / WpU are the bf16 copies
+  if (bf) hipLaunchKernelGGL((k_chain_node<false, 192, true>), grid, dim3(512), 0, b.c.s, cn);
+  else hipLaunchKernelGGL((k_chain_node<false, 192>), grid, dim3(512), 0, b.c.s, cn);
   return launch_ok();
 }
 
@@ -335,6 +342,7 @@ struct LayerBufs {
   float* dXall;              // gradient of the layer's input sequence (dSeq of the layer below / dX0)
   float *DPU, *DPG, *DPU2, *DPG2, *DAg, *DAu, *DAx;
   const float *WpG, *WpU, *RG, *RU;
+  const float *WpG16, *WpU16;   // training precision mode 2: bf16 copies of WpG / WpU (element order of the plain layout)
   bool mergeAbove;           // the gate block already holds the x-column gradient of the layer above
   bool narrow;               // layer 0 with a handful of input channels
 };
@@ -420,7 +428,7 @@ int bwd_clear(Pass& pass) {
 // plain copies the backward GEMMs contract with: the support stack and the folded node-adaptive weights.  Parameter-only
 // work: matgcn_forward_train runs it on a side stream beside the forward (it used to open every backward: 0.8 ms on the
 // critical path), matgcn_backward finds the copies in the train buffer.
-int plain_operands(const Ctx& c, float* tr, hipStream_t s) {
+int plain_operands(const Ctx& c, float* tr, hipStream_t s, bool bf16Copies) {
   const Plan& P = c.P;
   const TrainPlan& R = c.R;
   const StackMap map = build_stack_map(P, c.D, c.prm);
@@ -450,6 +458,12 @@ int plain_operands(const Ctx& c, float* tr, hipStream_t s) {
                            0, s, q);
       }
       CHECK_LAUNCH();
+      if (bf16Copies) {   // training precision mode 2: the backward's node contractions stream this copy
+        const size_t octets = perNode * P.N / 8;
+        hipLaunchKernelGGL(k_stream_to_bf16, dim3(blocks_for(octets)), dim3(256), 0, s, tr + R.oWp[l][part],
+                           reinterpret_cast<unsigned int*>(tr + R.oWp16[l][part]), octets);
+        CHECK_LAUNCH();
+      }
     }
   // fragment-ordered transposes of the residual cell's nn.Linear weights (hidden columns): k_chain_res_node's B operands
   for (int l = 0; l < P.L && !P.gcnOff; ++l) {
@@ -599,6 +613,7 @@ int bwd_x_chunk(Pass& pass, const LayerBufs& L, int t0, int t1) {
   LAYER_LOCALS(L);
   const Bwd& bx = pass.bx;
   hipStream_t xs = pass.xs;
+  const bool bfn = g_tnode_bf16_now;   // training precision mode 2: bf16 weight copies in the node contractions
   float* DAgBelow = tr + R.oDAg[(l - 1) & 1];
   const size_t last = (size_t)(T - 1) * B;
   if (t1 == T) {   // the first chunk processed: what the whole layer needs once
@@ -615,10 +630,11 @@ int bwd_x_chunk(Pass& pass, const LayerBufs& L, int t0, int t1) {
   RETURN_IF(zero_async(dXall + r0 * Np * C, (long)rows * Np * C, xs));
   const int tEnd = t1 < T - 1 ? t1 : T - 1;
   if (tEnd > t0)
-    RETURN_IF(node_contract(bx, DPG + r0 * Np * 128, WpG, DPU + r0 * Np * 64, WpU, I, 0, (tEnd - t0) * B,
-                            DAgBelow + slab * S * (t0 + 1), 0.f));
+    RETURN_IF(node_contract(bx, DPG + r0 * Np * 128, bfn ? L.WpG16 : WpG, DPU + r0 * Np * 64, bfn ? L.WpU16 : WpU, I, 0,
+                            (tEnd - t0) * B, DAgBelow + slab * S * (t0 + 1), 0.f, bfn));
   if (t1 == T) {
-    RETURN_IF(node_contract(bx, DPG + last * Np * 128, WpG, DPU + last * Np * 64, WpU, I, 0, B, DAx, 0.f));
+    RETURN_IF(node_contract(bx, DPG + last * Np * 128, bfn ? L.WpG16 : WpG, DPU + last * Np * 64, bfn ? L.WpU16 : WpU, I, 0,
+                            B, DAx, 0.f, bfn));
     RETURN_IF(mix_transposed(bx, DAx, B, C, dXall + last * Np * C));
     hipLaunchKernelGGL(k_add_slot0, dim3(blocks_for((size_t)B * Np * C)), dim3(256), 0, xs, dXall + last * Np * C, DAx,
                        (size_t)B, Np, C, S);
@@ -644,6 +660,9 @@ int bwd_x_chunk(Pass& pass, const LayerBufs& L, int t0, int t1) {
 int bwd_chain(Pass& pass, const LayerBufs& L) {
   PASS_LOCALS(pass);
   LAYER_LOCALS(L);
+  // training precision mode 2: the node contractions of the fused kernels stream the bf16 weight copies (the pair of
+  // kernels for more than four dense slots stays fp32)
+  const bool bfn = g_tnode_bf16_now;
   // ---------------- chain ----------------
   for (int t = T - 1; t >= 0; --t) {
     const size_t at = (size_t)t * slab;
@@ -683,10 +702,14 @@ int bwd_chain(Pass& pass, const LayerBufs& L) {
       f.carryA = (t == T - 1) ? nullptr : DAg + (at + slab) * S;
       f.carryMix = (t == T - 1 || P.Ks <= 0) ? nullptr : MixOut;
       f.ruf = tr + R.oRUf[l]; f.rgf = tr + R.oRGf[l];
-      f.Wp = WpU; f.dA = DAu + at * S; f.I = I; f.iOfs = C;
+      f.Wp = bfn ? L.WpU16 : WpU; f.dA = DAu + at * S; f.I = I; f.iOfs = C;
       const bool carry = t != T - 1;
       const int parts = (carry && f.carryMix) ? a.mixParts : 0;
-#define CRN_LAUNCH(C_, P_) hipLaunchKernelGGL((k_chain_res_node<C_, true, P_>), ngrid, dim3(512), CRN_LDS, s, f)
+#define CRN_LAUNCH(C_, P_)                                                                                 \
+  do {                                                                                                     \
+    if (bfn) hipLaunchKernelGGL((k_chain_res_node<C_, true, P_, true>), ngrid, dim3(512), CRN_LDS, s, f);  \
+    else hipLaunchKernelGGL((k_chain_res_node<C_, true, P_>), ngrid, dim3(512), CRN_LDS, s, f);            \
+  } while (0)
       if (!carry) CRN_LAUNCH(false, 0);
       else switch (parts) {
         case 0: CRN_LAUNCH(true, 0); break; case 1: CRN_LAUNCH(true, 1); break; case 2: CRN_LAUNCH(true, 2); break;
@@ -716,9 +739,12 @@ int bwd_chain(Pass& pass, const LayerBufs& L) {
     cn.dPre = nullptr; cn.Wp = WpG; cn.dA = DAg + at * S; cn.beta = mergeAbove ? 1.f : 0.f;
     if (fused) {
       const int parts = P.Ks > 0 ? a.mixParts : 0;
+      if (bfn) cn.Wp = L.WpG16;
 #define CGN_LAUNCH(P_)                                                                                     \
   do {                                                                                                     \
-    if (mergeAbove) hipLaunchKernelGGL((k_chain_gate_node<P_, true>), ngrid, dim3(512), 0, s, cn);         \
+    if (bfn && mergeAbove) hipLaunchKernelGGL((k_chain_gate_node<P_, true, true>), ngrid, dim3(512), 0, s, cn); \
+    else if (bfn) hipLaunchKernelGGL((k_chain_gate_node<P_, false, true>), ngrid, dim3(512), 0, s, cn);    \
+    else if (mergeAbove) hipLaunchKernelGGL((k_chain_gate_node<P_, true>), ngrid, dim3(512), 0, s, cn);    \
     else hipLaunchKernelGGL((k_chain_gate_node<P_, false>), ngrid, dim3(512), 0, s, cn);                   \
   } while (0)
       switch (parts) {
@@ -800,7 +826,8 @@ int bwd_x_columns(Pass& pass, const LayerBufs& L) {
       a.outFloats = (long)N * cols;
       a.Np = P.NpC; a.N = N; a.Ks = 1; a.nK = P.Ks * Np / 16; a.nColTiles = (int)(cols / 64);
       a.nRowTiles = P.NpC / 64;
-      hipLaunchKernelGGL(k_mix<2>, dim3((unsigned)(a.nRowTiles * a.nColTiles), 1u), dim3(256), 0, s, a);
+      if (g_tmix_bf16_now) hipLaunchKernelGGL(k_mix_bf16<2>, dim3((unsigned)(a.nRowTiles * a.nColTiles), 1u), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL(k_mix<2>, dim3((unsigned)(a.nRowTiles * a.nColTiles), 1u), dim3(256), 0, s, a);
       CHECK_LAUNCH();
     } else if (P.Ks > 0) {
       GemmArgs q = gemm_args(c.prep + P.oSt, DAx + (size_t)Np * cols, MixN, N, (int)cols, P.Ks * Np);
@@ -811,7 +838,8 @@ int bwd_x_columns(Pass& pass, const LayerBufs& L) {
                        P.Ks > 0 ? MixN : nullptr, DAx, dXall, (size_t)rowsTB, N, Np, C);
     CHECK_LAUNCH();
   } else if (l == 0) {   // a 64-channel input layer: nothing below to ride with
-    RETURN_IF(node_contract(b, DPG, WpG, DPU, WpU, I, 0, rowsTB, DAx, 0.f));
+    RETURN_IF(node_contract(b, DPG, g_tnode_bf16_now ? L.WpG16 : WpG, DPU, g_tnode_bf16_now ? L.WpU16 : WpU, I, 0, rowsTB,
+                            DAx, 0.f, g_tnode_bf16_now));
     RETURN_IF(zero_async(dXall, (long)rowsTB * Np * C, s));
     RETURN_IF(mix_transposed(b, DAx, rowsTB, C, dXall));
     hipLaunchKernelGGL(k_add_slot0, dim3(blocks_for((size_t)rowsTB * Np * C)), dim3(256), 0, s, dXall, DAx,
@@ -1288,6 +1316,7 @@ int backward_impl(Bwd& b, const float* dOut) {
     L.DPU = tr + R.oDPU[L.par]; L.DPG = tr + R.oDPG[L.par]; L.DPU2 = tr + R.oDPU2[L.par]; L.DPG2 = tr + R.oDPG2[L.par];
     L.DAg = tr + R.oDAg[L.par]; L.DAu = tr + R.oDAu[L.par]; L.DAx = tr + R.oDAx[L.par];
     L.WpG = tr + R.oWp[l][0]; L.WpU = tr + R.oWp[l][1];
+    L.WpG16 = tr + R.oWp16[l][0]; L.WpU16 = tr + R.oWp16[l][1];
     L.RG = b.c.prm->res_gate[l].weight;     // (128, I)
     L.RU = b.c.prm->res_update[l].weight;   // (64, I)
     // x_t of layer l+1 IS h_t of layer l: the gradient of [x | mix(x)] of the layer above (steps 0..T-2) was written
@@ -1356,7 +1385,7 @@ int matgcn_train_bytes(const matgcn_dims* dims, size_t* bytes) {
   RETURN_IF(make_plan(dims, &P));
   TrainPlan R;
   RETURN_IF(make_train_plan(P, &R));
-  *bytes = (size_t)R.floats * sizeof(float);
+  *bytes = (size_t)(g_train_precision == 2 && !P.gcnOff ? R.floatsBf16 : R.floats) * sizeof(float);
   return MATGCN_OK;
 }
 
@@ -1376,6 +1405,15 @@ static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* para
   RETURN_IF(make_train_plan(P, &c.R));
   if (train_bytes < (size_t)c.R.floats * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;
   c.train = (float*)train;
+  // precision (matgcn_set_train_precision): bf16 operands for the graph mixes (mode >= 1) and the node-wise contractions
+  // (mode 2, bf16 copies of the weight streams in the workspace) - as the inference forward of that mode; the saved
+  // activations, the state and every epilogue stay fp32.  The matching backward follows this mode (train_mode_of).
+  const int mode = g_train_precision;
+  if (mode == 2 && !P.gcnOff && (workspace_bytes < (size_t)P.workspaceFloatsBf16 * sizeof(float) ||
+                                 train_bytes < (size_t)c.R.floatsBf16 * sizeof(float)))
+    return MATGCN_ERR_SMALL_BUFFER;   // sized without mode 2's bf16 copies
+  MixPrecisionScope mixScope(mode);
+  note_train_mode(train, -1);   // until this call has enqueued everything: a backward on this buffer is refused
   // the forward kernels write the rows of the real nodes only: the rows of the padding nodes must read as zero.  The
   // saved tensors are contiguous [T][B][Np][64] blocks, so one launch clears the padding rows of all of them.
   if (P.Np != P.N) {
@@ -1393,7 +1431,7 @@ static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* para
     HIP_OK(hipEventRecord(g_wf.auxFork, c.s));
     HIP_OK(hipStreamWaitEvent(aux, g_wf.auxFork, 0));
   }
-  RETURN_IF(plain_operands(c, c.train, aux));
+  RETURN_IF(plain_operands(c, c.train, aux, mode == 2 && !P.gcnOff));
   if (side) HIP_OK(hipEventRecord(g_wf.auxDone, aux));
   float* x0p = c.ws + P.oX0p;
   if (src) RETURN_IF(fuse_padded(c, src->series, x0p, src->label_start, src->rel_steps, src->series_steps));
@@ -1415,7 +1453,9 @@ static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* para
     CHECK_LAUNCH();
     seqTop = dropped;
   }
-  return head_padded(c, seqTop, out);
+  RETURN_IF(head_padded(c, seqTop, out));
+  note_train_mode(train, mode);
+  return MATGCN_OK;
 }
 
 // a failure between a fork onto the library streams and their join (side stream of the plain operands, the layers'
@@ -1449,6 +1489,11 @@ static int backward_entry(const matgcn_dims* dims, const matgcn_params* params, 
   if (train_bytes < (size_t)b.c.R.floats * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;
   b.X = X; b.dropMask = drop_mask; b.g = grads; b.tr = (float*)train;
   b.hasH0 = h0 != nullptr; b.dH0 = d_h0; b.src = src;
+  // the mode the matching forward_train ran with, whatever the setting is now (-1: that forward_train failed)
+  const int mode = train_mode_of(train);
+  if (mode < 0) return MATGCN_ERR_BAD_ARG;
+  if (mode == 2 && !b.c.P.gcnOff && train_bytes < (size_t)b.c.R.floatsBf16 * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;
+  MixPrecisionScope mixScope(mode, true);
   JOINED(backward_impl(b, d_out), stream);
 }
 

@@ -1036,14 +1036,41 @@ __global__ __launch_bounds__(256) void k_prep_linear_t16(const float* __restrict
 }
 
 #define CRN_LDS (3 * 4096 * (int)sizeof(float))
+// BF (matgcn_set_train_precision(2)): the node contractions of the chain kernels below stream a bf16 copy of the plain
+// folded weights (same element order, half the bytes - the stream that bounds them) and round their A values to bf16 as
+// they leave LDS (each element is rounded once, as a bf16 LDS tile would be); one v_mfma_f32_16x16x16_bf16 per k-group of
+// 16 o replaces the four 16x16x4 f32 ones: a lane's four o (16 g + 4 kq + e) are the four consecutive k of its A and B
+// fragments.  fp32 accumulation; everything written to memory stays fp32.
+template <bool BF>
+__device__ __forceinline__ const typename NodeOp<BF>::T* plain_w(const float* base, size_t elems) {
+  if constexpr (BF) return reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(base) + elems);
+  else return reinterpret_cast<const float4*>(base + elems);
+}
+template <bool BF, int NRT>
+__device__ __forceinline__ void node_group_mfma(const float4 (&av)[NRT], const typename NodeOp<BF>::T& wg, f32x4 (&acc)[NRT]) {
+  if constexpr (BF) {
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) acc[rt] = MFMA16BF(as_bf16x4(to_bf16x4(av[rt])), as_bf16x4(wg), acc[rt]);
+  } else {
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) acc[rt] = MFMA16(av[rt].x, wg.x, acc[rt]);
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) acc[rt] = MFMA16(av[rt].y, wg.y, acc[rt]);
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) acc[rt] = MFMA16(av[rt].z, wg.z, acc[rt]);
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) acc[rt] = MFMA16(av[rt].w, wg.w, acc[rt]);
+  }
+}
 __device__ __forceinline__ float4 f4_add(const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 f4_mul(const float4& a, const float4& b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
 
 // CARRY: step t+1 exists (dcarry, carryA and PARTS partial transposed mixes are added to the incoming gradient); HPREV: h_{t-1}
 // exists.  Template parameters, not runtime branches: a request behind a branch ends a basic block and the compiler drains the
 // whole queue (vmcnt(0)) where the paths meet - phase 1 is ONE batch of 8 + 2 + PARTS requests per row sweep.
-template <bool CARRY, bool HPREV, int PARTS>
+template <bool CARRY, bool HPREV, int PARTS, bool BF = false>
 __global__ __launch_bounds__(512, 4) void k_chain_res_node(ChainResNodeArgs f) {
+  typedef typename NodeOp<BF>::T Op;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* R0 = lds;             // dpu2 tile -> z half of dpg2 -> dpu tile
   float* R1 = lds + 4096;      // r half of dpg2 -> output tile 0 of the node contraction
@@ -1163,10 +1190,10 @@ __global__ __launch_bounds__(512, 4) void k_chain_res_node(ChainResNodeArgs f) {
     if (b < a.B) st4b(a.dpg2, (((unsigned)b * a.Np + n) * 128 + sq * 4) * 4u, dz);
   }
   const int nCt = 4 * a.S;
-  auto wload = [&](int tile, int gq) -> float4 {
+  auto wload = [&](int tile, int gq) -> Op {
     const int slot = tile >> 2, i0 = (tile & 3) * 16;
     const size_t wrow = ((size_t)n * a.S + slot) * f.I + f.iOfs + i0 + j;
-    return (reinterpret_cast<const float4*>(f.Wp + wrow * 64) + kq)[gq * 4];
+    return (plain_w<BF>(f.Wp, wrow * 64) + kq)[gq * 4];
   };
   // what phase 5 needs again of the saved state (read in phase 1: L2 hits), in flight under phase 4
   float4 hk[2], rk[2], hck[2];
@@ -1190,7 +1217,7 @@ __global__ __launch_bounds__(512, 4) void k_chain_res_node(ChainResNodeArgs f) {
   }
   to_tile(R2);   // (phase 3 read R2 before the barrier above)
   // the node contraction's weights of this wave's first column tile land under phase 5
-  float4 wt[4];
+  Op wt[4];
 #pragma unroll
   for (int gq = 0; gq < 4; ++gq) wt[gq] = wload(min(w, nCt - 1), gq);
   __syncthreads();
@@ -1229,19 +1256,22 @@ __global__ __launch_bounds__(512, 4) void k_chain_res_node(ChainResNodeArgs f) {
       const int nextTile = min(tile + 8, nCt - 1);
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
-        float4 av[4];
+        if constexpr (BF) {   // A values rounded as they are read: half the live registers of the float4 set
+          uint2 ab[4];
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) av[rt] = frag(R0, rt, gq);
-        const float4 wv = wt[gq];
-        wt[gq] = wload(nextTile, gq);
+          for (int rt = 0; rt < 4; ++rt) ab[rt] = to_bf16x4(frag(R0, rt, gq));
+          const Op wv = wt[gq];
+          wt[gq] = wload(nextTile, gq);
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) ac[rt] = MFMA16(av[rt].x, wv.x, ac[rt]);
+          for (int rt = 0; rt < 4; ++rt) ac[rt] = MFMA16BF(as_bf16x4(ab[rt]), as_bf16x4(wv), ac[rt]);
+        } else {
+          float4 av[4];
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) ac[rt] = MFMA16(av[rt].y, wv.y, ac[rt]);
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt) ac[rt] = MFMA16(av[rt].z, wv.z, ac[rt]);
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt) ac[rt] = MFMA16(av[rt].w, wv.w, ac[rt]);
+          for (int rt = 0; rt < 4; ++rt) av[rt] = frag(R0, rt, gq);
+          const Op wv = wt[gq];
+          wt[gq] = wload(nextTile, gq);
+          node_group_mfma<false, 4>(av, wv, ac);
+        }
       }
       float* tileOut = (w >> 2) ? R2 : R1;
       const int col = (w & 3) * 16 + j;
@@ -1286,8 +1316,9 @@ struct ChainNodeArgs {
 
 // (grid: x = 64-row block, y = node - the row blocks of one node are neighbours in launch order, so the batched
 // x-column calls, which have 23 row blocks per node, re-read a node's weights from L2.)
-template <bool GATE, int O>
+template <bool GATE, int O, bool BF = false>
 __global__ __launch_bounds__(512, 4) void k_chain_node(ChainNodeArgs p) {
+  typedef typename NodeOp<BF>::T Op;
   constexpr int NG = O / 16;
   static_assert(!GATE || O == 128, "the gate algebra produces the 128 gate columns");
   __shared__ __attribute__((aligned(16))) float As[(O / 64) * 4096];   // [O/64 chunks][64 rows][16 slots], swizzled
@@ -1298,15 +1329,15 @@ __global__ __launch_bounds__(512, 4) void k_chain_node(ChainNodeArgs p) {
   // requested before the A tile is built and land under the gate algebra ----
   const int nCt = 4 * p.S;
   constexpr int O1 = O == 192 ? 128 : O;     // columns of the first operand pair (O = 192: gate 128 | update 64)
-  auto wload1 = [&](int ct, int g) -> float4 {
+  auto wload1 = [&](int ct, int g) -> Op {
     const int slot = ct >> 2, i0 = (ct & 3) * 16;
     const size_t wrow = ((size_t)n * p.S + slot) * p.I + p.iOfs + i0 + j;
-    if (O == 192 && g >= O1 / 16) return (reinterpret_cast<const float4*>(p.Wp2 + wrow * 64) + kq)[(g - O1 / 16) * 4];
-    return (reinterpret_cast<const float4*>(p.Wp + wrow * O1) + kq)[g * 4];
+    if (O == 192 && g >= O1 / 16) return (plain_w<BF>(p.Wp2, wrow * 64) + kq)[(g - O1 / 16) * 4];
+    return (plain_w<BF>(p.Wp, wrow * O1) + kq)[g * 4];
   };
   // ONE register set of weights: group g of the next column tile is requested as soon as group g of this one has been
   // consumed, so the loads of tile ct + 8 fly under the MFMAs of tile ct (two whole sets - 96 registers at O = 192 - spill)
-  float4 wt[NG];
+  Op wt[NG];
 #pragma unroll
   for (int g = 0; g < NG; ++g) wt[g] = wload1(min(w, nCt - 1), g);
   // ---- A tile ----
@@ -1357,16 +1388,9 @@ __global__ __launch_bounds__(512, 4) void k_chain_node(ChainNodeArgs p) {
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt)
         av[rt] = *reinterpret_cast<const float4*>(&buf[((rt * 16 + j) * 16 + ((4 * (g & 3) + kq) ^ j)) * 4]);
-      const float4 wg = wt[g];
+      const Op wg = wt[g];
       wt[g] = wload1(nextCt, g);
-#pragma unroll
-      for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA16(av[rt].x, wg.x, acc[rt]);
-#pragma unroll
-      for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA16(av[rt].y, wg.y, acc[rt]);
-#pragma unroll
-      for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA16(av[rt].z, wg.z, acc[rt]);
-#pragma unroll
-      for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA16(av[rt].w, wg.w, acc[rt]);
+      node_group_mfma<BF, 4>(av, wg, acc);
       __builtin_amdgcn_sched_barrier(0);        // keeps the A reads of later groups from being hoisted (they spilled)
     }
   };
@@ -1434,8 +1458,9 @@ __global__ __launch_bounds__(512, 4) void k_chain_node(ChainNodeArgs p) {
 // Here the PARTS partial mixes and the presence of old values are template parameters, h_{t-1} always exists (the launcher
 // passes a zero slab at t = 0), every request of a row sweep leaves in one batch with 32-bit byte offsets from SGPR bases,
 // and the old values of a pass are requested before its MFMAs.
-template <int PARTS, bool BETA>
+template <int PARTS, bool BETA, bool BF = false>
 __global__ __launch_bounds__(512, 4) void k_chain_gate_node(ChainNodeArgs p) {
+  typedef typename NodeOp<BF>::T Op;
   constexpr int NG = 8;
   __shared__ __attribute__((aligned(16))) float As[2 * 4096];    // [gz | gr][64 rows][16 slots], swizzled
   __shared__ __attribute__((aligned(16))) float Out[2 * 4096];
@@ -1444,12 +1469,13 @@ __global__ __launch_bounds__(512, 4) void k_chain_gate_node(ChainNodeArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), j = lane & 15, kq = lane >> 4;
   const int srow = tid >> 4, sq = tid & 15;
   const int nCt = 4 * p.S;
-  auto wload1 = [&](int ct, int g) -> float4 {
+  auto wload1 = [&](int ct, int g) -> Op {
     const int slot = ct >> 2, i0 = (ct & 3) * 16;
     const size_t wrow = ((size_t)n * p.S + slot) * p.I + p.iOfs + i0 + j;
-    return (reinterpret_cast<const float4*>(p.Wp + wrow * 128) + kq)[g * 4];
+    if constexpr (BF) return (plain_w<true>(p.Wp, wrow * 128) + kq)[g * 4];
+    else return (reinterpret_cast<const float4*>(p.Wp + wrow * 128) + kq)[g * 4];
   };
-  float4 wt[NG];
+  Op wt[NG];
 #pragma unroll
   for (int g = 0; g < NG; ++g) wt[g] = wload1(min(w, nCt - 1), g);
   // ---- A tile = the gate algebra of the graph cell (MultiATGCN.py:122-125 transposed), row layout ----
@@ -1505,16 +1531,20 @@ __global__ __launch_bounds__(512, 4) void k_chain_gate_node(ChainNodeArgs p) {
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt)
           av[rt] = *reinterpret_cast<const float4*>(&buf[((rt * 16 + j) * 16 + ((4 * (g & 3) + kq) ^ j)) * 4]);
-        const float4 wg = wt[g];
+        const Op wg = wt[g];
         wt[g] = wload1(nextCt, g);
+        if constexpr (BF) {
+          node_group_mfma<true, 4>(av, wg, acc);
+        } else {
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA16(av[rt].x, wg.x, acc[rt]);
+          for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA16(av[rt].x, wg.x, acc[rt]);
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA16(av[rt].y, wg.y, acc[rt]);
+          for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA16(av[rt].y, wg.y, acc[rt]);
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA16(av[rt].z, wg.z, acc[rt]);
+          for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA16(av[rt].z, wg.z, acc[rt]);
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA16(av[rt].w, wg.w, acc[rt]);
+          for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA16(av[rt].w, wg.w, acc[rt]);
+        }
         __builtin_amdgcn_sched_barrier(0);        // keeps the A reads of later groups from being hoisted (they spilled)
       }
       float* tileOut = Out + (w >> 2) * 4096;

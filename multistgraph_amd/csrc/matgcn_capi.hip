@@ -156,8 +156,8 @@ int make_plan(const matgcn_dims* D, Plan* P) {
   }
   P->workspaceFloats = o;
   // optional tail, precision mode 2 only (half the bytes of the fp32 weight streams - +125 MB at N = 403,
-  // several hundred MB at N = 4096 - that the fp32 product path and training never touch): matgcn_workspace_bytes counts
-  // it only while mode 2 is set, and a mode-2 forward on a workspace without it returns MATGCN_ERR_SMALL_BUFFER
+  // several hundred MB at N = 4096 - that the fp32 paths never touch): matgcn_workspace_bytes counts it only while mode 2
+  // is set for inference or training, and a mode-2 forward on a workspace without it returns MATGCN_ERR_SMALL_BUFFER
   for (int l = 0; l < P->L; ++l) {
     P->oW16g[l] = take((P->wgFloats[l] + 1) / 2);   // bf16: two values per float slot
     P->oW16u[l] = take((P->wuFloats[l] + 1) / 2);
@@ -198,6 +198,10 @@ struct TrainPlan {
   long oDT, oDL, oEK, oFK, oTmpK, oDGain, oDPoolGain, oDOutRows;
   long oStP;                               // [Ks*Np][NpC] plain support stack (A operand of the transposed mix)
   long floats;
+  // optional tail, training precision mode 2 only: bf16 copies of the plain folded weights (oWp), the B operands of the
+  // backward's node-wise data-gradient contractions; matgcn_train_bytes counts it only while mode 2 is set
+  long oWp16[MATGCN_MAX_LAYERS][2];
+  long floatsBf16;
 };
 
 int make_train_plan(const Plan& P, TrainPlan* R) {
@@ -256,6 +260,12 @@ int make_train_plan(const Plan& P, TrainPlan* R) {
   R->oDOutRows = take((long)P.B * P.Np * P.CH);
   R->oStP = take((long)P.Ks * P.Np * P.NpC);
   R->floats = o;
+  for (int l = 0; l < P.L && !P.gcnOff; ++l)
+    for (int part = 0; part < 2; ++part) {
+      const long O = part == 0 ? 128 : 64, I = P.Cl[l] + H;
+      R->oWp16[l][part] = take(((long)P.N * R->S * I * O + 1) / 2);   // bf16: two values per float slot
+    }
+  R->floatsBf16 = o;
   return MATGCN_OK;
 }
 
@@ -391,15 +401,49 @@ int prep_wait(hipStream_t s, int which) {
 int g_wavefront_mode = 1;     // matgcn_set_wavefront: 0 serial, 1 free-running chains
 int g_mix_precision = 0;      // matgcn_set_mix_precision: 0 fp32 operands, 1 bf16 operands for the inference graph mixes,
                               // 2 bf16 operands for the graph mixes AND the node-wise contractions (bf16 weight streams)
-bool g_mix_bf16_now = false;  // set for the duration of an inference forward only (MixPrecisionScope)
+int g_train_precision = 0;    // matgcn_set_train_precision: the same values for matgcn_forward_train / matgcn_backward
+bool g_mix_bf16_now = false;  // set for the duration of a forward whose mode asks for it (MixPrecisionScope)
 bool g_node_bf16_now = false;
+bool g_tmix_bf16_now = false; // backward: bf16 operands for the transposed graph mixes (mode of the matching forward_train)
+bool g_tnode_bf16_now = false;// backward, mode 2: bf16 weight copies for the node-wise data-gradient contractions
+// mode: the precision setting that governs the call in flight (g_mix_precision for the inference forwards,
+// g_train_precision - or, in the backward, the mode its forward_train ran with - for training)
 struct MixPrecisionScope {
-  explicit MixPrecisionScope(bool inferenceForward) {
-    g_mix_bf16_now = inferenceForward && g_mix_precision >= 1;
-    g_node_bf16_now = inferenceForward && g_mix_precision == 2;
+  explicit MixPrecisionScope(int mode, bool backward = false) {
+    g_mix_bf16_now = !backward && mode >= 1;
+    g_node_bf16_now = !backward && mode == 2;
+    g_tmix_bf16_now = backward && mode >= 1;
+    g_tnode_bf16_now = backward && mode == 2;
   }
-  ~MixPrecisionScope() { g_mix_bf16_now = false; g_node_bf16_now = false; }
+  ~MixPrecisionScope() {
+    g_mix_bf16_now = false; g_node_bf16_now = false; g_tmix_bf16_now = false; g_tnode_bf16_now = false;
+  }
 };
+// The backward follows the mode its forward_train ran with: forward_train notes (device, train buffer) -> mode here and
+// matgcn_backward looks its train buffer up (a buffer without an entry runs with the current setting).  The last
+// TRAIN_MODE_SLOTS buffers are remembered - far more than the one per model a training loop keeps.
+constexpr int TRAIN_MODE_SLOTS = 64;
+struct TrainModeRec { int dev; const void* train; int mode; };
+TrainModeRec g_train_modes[TRAIN_MODE_SLOTS];
+int g_train_modes_next = 0;
+inline int current_device() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  return dev;
+}
+void note_train_mode(const void* train, int mode) {
+  const int dev = current_device();
+  for (int i = 0; i < TRAIN_MODE_SLOTS; ++i)
+    if (g_train_modes[i].train == train && g_train_modes[i].dev == dev) { g_train_modes[i].mode = mode; return; }
+  g_train_modes[g_train_modes_next] = TrainModeRec{dev, train, mode};
+  g_train_modes_next = (g_train_modes_next + 1) % TRAIN_MODE_SLOTS;
+}
+int train_mode_of(const void* train) {
+  const int dev = current_device();
+  for (int i = 0; i < TRAIN_MODE_SLOTS; ++i)
+    if (g_train_modes[i].train == train && g_train_modes[i].dev == dev) return g_train_modes[i].mode;
+  return g_train_precision;
+}
 
 int wavefront_ready() {
   if (g_wf.ready) return MATGCN_OK;
@@ -615,6 +659,8 @@ int node_kernels_ready(int ldsBytes) {
   HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<2, true, 64>), at, UPDATE_SAVE_LDS));
   HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<false, 64, true>), at, GATE_LDS));
   HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, false, 64, true>), at, UPDATE_LDS));
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<true, 64, true>), at, GATE_LDS));
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, true, 64, true>), at, UPDATE_SAVE_LDS));
   // 32-row work items (batches of at most 32 rows, graphs of at most 256 nodes: cell_phase)
   HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<false, 32>), at, GATE_LDS));
   HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, false, 32>), at, UPDATE_LDS));
@@ -676,8 +722,8 @@ int hoist_x(const Ctx& c, int l, const float* xin, int t0, int nt, hipStream_t s
   a.steps = nt; a.N = P.N; a.Np = P.Np; a.Ks = P.Ks; a.B = P.B;
   ProfScope prof(MATGCN_PROF_PX, s);
   const dim3 grid((unsigned)(rup(P.N, 8) * nt * P.RB));
-  // precision mode 2 (inference forwards only): the bf16 copy of the stream, A rows rounded on their way into LDS
-  const bool bf = g_node_bf16_now && !c.train;
+  // precision mode 2: the bf16 copy of the stream, A rows rounded on their way into LDS
+  const bool bf = g_node_bf16_now;
   if (bf) a.w = c.ws + P.oW16x[l];
 #define PX16_LAUNCH(NRT)                                                                                   \
   do {                                                                                                     \
@@ -755,13 +801,14 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
     a.svZ = c.train + c.R.oZ[l] + at; a.svR = c.train + c.R.oR[l] + at; a.svHC = c.train + c.R.oHC[l] + at;
     a.svZ2 = c.train + c.R.oZ2[l] + at; a.svR2 = c.train + c.R.oR2[l] + at; a.svHC2 = c.train + c.R.oHC2[l] + at;
   }
-  // precision mode 2 (inference forwards only): bf16 copies of the weight streams, made by encoder_chains
-  const bool bf = g_node_bf16_now && !save && res != nullptr && !raw;
+  // precision mode 2 (inference forward or training forward): bf16 copies of the weight streams, made by encoder_chains
+  const bool bf = g_node_bf16_now && res != nullptr && !raw;
   if (phase == 1) {
     a.s = Hx; a.w = bf ? c.ws + P.oW16g[l] : c.prep + P.oWg[l]; a.zh = ZHx; a.r = R; a.raw = raw;
     ProfScope prof(MATGCN_PROF_GATE, s);
     if (rows32 && save) hipLaunchKernelGGL((k_gate16<true, 32>), grid, dim3(512), GATE_LDS / 2, s, a);
     else if (rows32) hipLaunchKernelGGL((k_gate16<false, 32>), grid, dim3(512), GATE_LDS / 2, s, a);
+    else if (bf && save) hipLaunchKernelGGL((k_gate16<true, 64, true>), grid, dim3(512), GATE_LDS, s, a);
     else if (bf) hipLaunchKernelGGL((k_gate16<false, 64, true>), grid, dim3(512), GATE_LDS, s, a);
     else if (save) hipLaunchKernelGGL((k_gate16<true, 64>), grid, dim3(512), GATE_LDS, s, a);
     else hipLaunchKernelGGL((k_gate16<false, 64>), grid, dim3(512), GATE_LDS, s, a);
@@ -780,6 +827,7 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
     }
     if (rows32 && save) hipLaunchKernelGGL((k_update16<1, true, 32>), grid, dim3(512), UPDATE_SAVE_LDS / 2, s, a);
     else if (rows32) hipLaunchKernelGGL((k_update16<1, false, 32>), grid, dim3(512), UPDATE_LDS / 2, s, a);
+    else if (bf && save) hipLaunchKernelGGL((k_update16<1, true, 64, true>), grid, dim3(512), UPDATE_SAVE_LDS, s, a);
     else if (bf) hipLaunchKernelGGL((k_update16<1, false, 64, true>), grid, dim3(512), UPDATE_LDS, s, a);
     else if (save) hipLaunchKernelGGL((k_update16<1, true, 64>), grid, dim3(512), UPDATE_SAVE_LDS, s, a);
     else hipLaunchKernelGGL((k_update16<1, false, 64>), grid, dim3(512), UPDATE_LDS, s, a);
@@ -835,7 +883,7 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
   const bool lazyPrep = prep_current().pending;
   // one stream, the bf16 copies (they read every stream) and the dense-GRU ablation take everything up front
   if (lazyPrep && (!multi || g_node_bf16_now || P.gcnOff)) RETURN_IF(prep_wait(c.s, 3));
-  if (g_node_bf16_now && !P.gcnOff && !c.train) {
+  if (g_node_bf16_now && !P.gcnOff) {
     if (c.wsBytes < (size_t)P.workspaceFloatsBf16 * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;   // sized without mode 2
     // precision mode 2: bf16 copies of the recurrent weight streams into the workspace, once per forward and in front
     // of the fork (every chain reads them); 240 MB of traffic, part of what the side line's time includes
@@ -1156,6 +1204,12 @@ int matgcn_set_mix_precision(int mode) {
   return prev;
 }
 
+int matgcn_set_train_precision(int mode) {
+  const int prev = g_train_precision;
+  g_train_precision = (mode == 1 || mode == 2) ? mode : 0;
+  return prev;
+}
+
 int matgcn_set_stream_pool(int own) {
   for (int d = 0; d < MAX_DEVICES; ++d)
     if (g_wfs[d].ready) return own ? (g_stream_pool ? MATGCN_OK : MATGCN_ERR_BAD_ARG) : (g_stream_pool ? MATGCN_ERR_BAD_ARG : MATGCN_OK);
@@ -1193,7 +1247,8 @@ int matgcn_workspace_bytes(const matgcn_dims* dims, size_t* bytes) {
   if (!bytes) return MATGCN_ERR_NULL;
   Plan P;
   RETURN_IF(make_plan(dims, &P));
-  *bytes = (size_t)(g_mix_precision == 2 ? P.workspaceFloatsBf16 : P.workspaceFloats) * sizeof(float);
+  const bool bf16Streams = g_mix_precision == 2 || g_train_precision == 2;
+  *bytes = (size_t)(bf16Streams ? P.workspaceFloatsBf16 : P.workspaceFloats) * sizeof(float);
   return MATGCN_OK;
 }
 
@@ -1415,7 +1470,7 @@ static int forward_entry(const matgcn_dims* dims, const matgcn_params* params, c
   if (!params->weight_tsg || !params->end_conv_bias) return MATGCN_ERR_NULL;
   for (int h = 0; h < dims->n_heads; ++h) if (!params->weight_ts[h]) return MATGCN_ERR_NULL;
   RETURN_IF(check_layer_params(dims, params));
-  MixPrecisionScope mixScope(true);
+  MixPrecisionScope mixScope(g_mix_precision);
   return forward_once(c, X, nullptr, 0, nullptr, nullptr, h0, out);
 }
 
@@ -1448,7 +1503,7 @@ static int forward_series_entry(const matgcn_dims* dims, const matgcn_params* pa
   for (int h = 0; h < dims->n_heads; ++h) if (!params->weight_ts[h]) return MATGCN_ERR_NULL;
   RETURN_IF(check_layer_params(dims, params));
   RETURN_IF(check_series(dims, series, series_steps, label_start, rel_steps));
-  MixPrecisionScope mixScope(true);
+  MixPrecisionScope mixScope(g_mix_precision);
   return forward_once(c, nullptr, series, series_steps, label_start, rel_steps, h0, out);
 }
 

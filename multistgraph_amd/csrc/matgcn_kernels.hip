@@ -886,6 +886,11 @@ __global__ __launch_bounds__(256) void k_mix_c32(MixArgs a) {
 // and all 32 rows: the same 2 x 2 accumulators, K-tile 16, two tiles ahead in registers, rotated LDS rows (16 floats per odd
 // k: the two k rows a 32-lane half reads sit half a bank row apart) and write-through row-store epilogue as k_mix.
 // Needs an even number of column tiles (the launcher falls back to k_mix<2> otherwise).
+// BF (matgcn_set_train_precision(1|2), the training side line): bf16 OPERANDS, fp32 accumulation, on
+// v_mfma_f32_16x16x32_bf16 - see k_mix_n32_bf_loop below; tiles, work split and epilogue are the fp32 kernel's.
+__device__ __forceinline__ void k_mix_n32_bf_loop(const MixArgs& a, unsigned int (*As)[16 * 32], unsigned int (*Bs)[16 * 128],
+                                                  int row0, int colPair, int part, f32x4 (&acc)[2][2]);
+template <bool BF = false>
 __global__ __launch_bounds__(256) void k_mix_n32(MixArgs a) {
   __shared__ __attribute__((aligned(16))) float As[2][16 * 32];
   __shared__ __attribute__((aligned(16))) float Bs[2][16 * 128];
@@ -904,6 +909,11 @@ __global__ __launch_bounds__(256) void k_mix_n32(MixArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int j = lane & 15, kq = lane >> 4;
   const int part = blockIdx.y;
+  f32x4 acc[2][2];
+  if constexpr (BF) {
+    k_mix_n32_bf_loop(a, reinterpret_cast<unsigned int (*)[16 * 32]>(As), reinterpret_cast<unsigned int (*)[16 * 128]>(Bs),
+                          row0, colPair, part, acc);
+  } else {
   // staging: A tile 16 k x 32 rows = 128 float4 (threads t and t + 128 fetch and store the same one: no branch in the
   // pipeline), B tile 16 k x 128 columns = two float4 per thread (column tiles 2 colPair and 2 colPair + 1)
   const int akk = (tid & 127) >> 3, asg = tid & 7;
@@ -929,7 +939,6 @@ __global__ __launch_bounds__(256) void k_mix_n32(MixArgs a) {
     *reinterpret_cast<float4*>(&Bs[0][bPos1]) = b1;
   }
   __syncthreads();
-  f32x4 acc[2][2];
 #pragma unroll
   for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -966,6 +975,7 @@ __global__ __launch_bounds__(256) void k_mix_n32(MixArgs a) {
       ra1 = ldA(it + 4); rb10 = ldB0(it + 4); rb11 = ldB1(it + 4);
       __syncthreads();
     }
+  }
   }
   // epilogue as k_mix (batched, branch-free: round 4): the wave's 32 x 32 tile through LDS (Bs is free after the last
   // barrier), 16-byte write-through stores
@@ -1014,7 +1024,8 @@ __global__ __launch_bounds__(256) void k_mix_n32(MixArgs a) {
 // -------------------------------------------------------------------------------------------------
 // 5b. the same graph mix with bf16 OPERANDS (BASELINE config 3's dtype): fp32 accumulation, fp32 inputs and outputs
 // -------------------------------------------------------------------------------------------------
-// Opt-in variant (matgcn_set_mix_precision(1); inference only, never the headline: narrower than the reference's fp32).
+// Opt-in variant (matgcn_set_mix_precision(1) / matgcn_set_train_precision(1): never the headline, narrower than the
+// reference's fp32; ROLE 2: the backward's transposed mixes of odd row counts, split by slot like k_mix<2>).
 // The supports and the state stay fp32 in memory; they are rounded to bf16 (round to nearest even) on their way into
 // LDS, two consecutive reduction indices packed into one 32-bit word, so that a lane's v_mfma_f32_16x16x16_bf16
 // fragment (4 consecutive k of one row / column) is two ds_read_b32.  K-tile 32 = 16 packed rows of 64 words; packed
@@ -1031,6 +1042,86 @@ __device__ __forceinline__ unsigned int bf16_rne(float x) {     // upper 16 bits
 __device__ __forceinline__ uint4 pack_bf16_rows(const float4& k0, const float4& k1) {   // word j = (k0[j], k1[j])
   return make_uint4(bf16_rne(k0.x) | (bf16_rne(k1.x) << 16), bf16_rne(k0.y) | (bf16_rne(k1.y) << 16),
                     bf16_rne(k0.z) | (bf16_rne(k1.z) << 16), bf16_rne(k0.w) | (bf16_rne(k1.w) << 16));
+}
+
+// K loop of k_mix_n32<true>: K-tile 32 = 16 packed rows (word = bf16 of reduction indices 2 pr, 2 pr + 1, rounded to
+// nearest even on the way into LDS; indices past the last one read as zero).  One v_mfma_f32_16x16x32_bf16 per
+// accumulator and K-tile: lane (j, kq) reads the four words of packed rows 4 kq .. 4 kq + 3 in its row / column - the
+// 8 consecutive k of its A and B fragments - and its accumulator holds rows 4 kq + e, column j, as the fp32 16x16x4 one.
+// Rows pr with (pr >> 2) odd are rotated by 16 words (the two k groups a 32-lane half reads sit half a bank row apart).
+// Register prefetch two K-tiles ahead, one barrier per tile, as the fp32 kernel.
+typedef __bf16 bf16x8v_t __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void k_mix_n32_bf_loop(const MixArgs& a, unsigned int (*As)[16 * 32], unsigned int (*Bs)[16 * 128],
+                                                  int row0, int colPair, int part, f32x4 (&acc)[2][2]) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int j = lane & 15, kq = lane >> 4;
+  const int apr = (tid & 127) >> 3, asg = tid & 7;   // A: packed row, 4-row segment (threads t, t + 128 duplicate)
+  const int bpr = tid >> 4, bsg = tid & 15;          // B: packed row, 4-column segment in each of the two column tiles
+  const int kLast = 16 * a.nK - 1;
+  const int nT = (a.nK + 1) >> 1;
+  const float* ap = a.St + (size_t)part * a.aPartStride + row0 + asg * 4;
+  const float* bp0 = a.X + (size_t)part * a.xPartStride + (size_t)(2 * colPair) * a.xTileStride + bsg * 4;
+  const float* bp1 = bp0 + a.xTileStride;
+  const int aPos = apr * 32 + ((asg * 4 + 16 * ((apr >> 2) & 1)) & 31);
+  const int bPos0 = bpr * 128 + ((bsg * 4 + 16 * ((bpr >> 2) & 1)) & 127);
+  const int bPos1 = bpr * 128 + ((64 + bsg * 4 + 16 * ((bpr >> 2) & 1)) & 127);
+  auto ld = [&](const float* base, size_t ld_, int pr, int t, float4& r0, float4& r1) {
+    const int k0 = 32 * min(t, nT - 1) + 2 * pr, k1 = k0 + 1;
+    const float4 v0 = *reinterpret_cast<const float4*>(base + (size_t)min(k0, kLast) * ld_);
+    const float4 v1 = *reinterpret_cast<const float4*>(base + (size_t)min(k1, kLast) * ld_);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    r0 = k0 <= kLast ? v0 : z;
+    r1 = k1 <= kLast ? v1 : z;
+  };
+  struct Tile { float4 a0, a1, b00, b01, b10, b11; };
+  auto load = [&](int t, Tile& r) {
+    ld(ap, a.ldS, apr, t, r.a0, r.a1);
+    ld(bp0, a.ldX, bpr, t, r.b00, r.b01);
+    ld(bp1, a.ldX, bpr, t, r.b10, r.b11);
+  };
+  auto store = [&](int buf, const Tile& r) {
+    *reinterpret_cast<uint4*>(&As[buf][aPos]) = pack_bf16_rows(r.a0, r.a1);
+    *reinterpret_cast<uint4*>(&Bs[buf][bPos0]) = pack_bf16_rows(r.b00, r.b01);
+    *reinterpret_cast<uint4*>(&Bs[buf][bPos1]) = pack_bf16_rows(r.b10, r.b11);
+  };
+  Tile r0, r1, r2;
+  load(0, r0);
+  load(1, r1);
+  load(2, r2);
+  store(0, r0);
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) acc[p][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int rot = 16 * (kq & 1);
+  const int cA0 = (j + rot) & 31, cA1 = (16 + j + rot) & 31;
+  const int cB0 = (w * 32 + j + rot) & 127, cB1 = (w * 32 + 16 + j + rot) & 127;
+  auto frag = [&](const unsigned int* T, int width, int c) {
+    const uint4 u = make_uint4(T[(4 * kq) * width + c], T[(4 * kq + 1) * width + c], T[(4 * kq + 2) * width + c],
+                               T[(4 * kq + 3) * width + c]);
+    return __builtin_bit_cast(bf16x8v_t, u);
+  };
+  auto mma = [&](int cur) {
+    const bf16x8v_t fa0 = frag(As[cur], 32, cA0), fa1 = frag(As[cur], 32, cA1);
+    const bf16x8v_t fb0 = frag(Bs[cur], 128, cB0), fb1 = frag(Bs[cur], 128, cB1);
+    acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa0, fb0, acc[0][0], 0, 0, 0);
+    acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa0, fb1, acc[0][1], 0, 0, 0);
+    acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa1, fb0, acc[1][0], 0, 0, 0);
+    acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa1, fb1, acc[1][1], 0, 0, 0);
+  };
+  for (int it = 0; it < nT; it += 2) {
+    mma(0);                 // tile it
+    store(1, r1);           // tile it+1 (a clamped copy past the end: unused)
+    load(it + 3, r1);
+    __syncthreads();
+    if (it + 1 < nT) {
+      mma(1);               // tile it+1
+      store(0, r2);         // tile it+2
+      load(it + 4, r2);
+      __syncthreads();
+    }
+  }
 }
 
 template <int ROLE>
@@ -1054,8 +1145,10 @@ __global__ __launch_bounds__(256) void k_mix_bf16(MixArgs a) {
   const int kLast = 16 * a.nK - 1;                         // reduction indices 0 .. Np-1 (a.nK = Np / 16)
   const int nT = (a.nK + 1) >> 1;                          // K-tiles of 32
   const int stPos = pr * 64 + (((sg + 4 * ((pr >> 1) & 3)) & 15) << 2);
-  const float* ap = a.St + row0 + sg * 4;
-  const float* bp = a.X + (size_t)colTile * a.xTileStride + sg * 4;
+  // split reduction (ROLE 2, the backward's transposed mix, MixArgs.parts): part p reads its own rows, writes its own output
+  const int part = ROLE == 2 ? (int)blockIdx.y : 0;
+  const float* ap = a.St + (size_t)part * a.aPartStride + row0 + sg * 4;
+  const float* bp = a.X + (size_t)part * a.xPartStride + (size_t)colTile * a.xTileStride + sg * 4;
   // loads are unconditional (row index clamped, values past the last reduction index zeroed by a select)
   auto ld = [&](const float* base, size_t ld_, int t, float4& r0, float4& r1) {
     const int k0 = 32 * min(t, nT - 1) + 2 * pr, k1 = k0 + 1;
@@ -1123,7 +1216,8 @@ __global__ __launch_bounds__(256) void k_mix_bf16(MixArgs a) {
         stg[lrow * 32 + (((lcol >> 2) ^ (lrow & 7)) << 2) + (lcol & 3)] = acc[p][q][e];
       }
   const bool wt = a.outFloats > 0 && a.outFloats < (1L << 29);   // 32-bit byte offsets
-  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, wt ? (int)(a.outFloats * 4) : 0, 0x00020000);
+  float* outp = a.out + (size_t)part * a.outPartStride;
+  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(outp, 0, wt ? (int)(a.outFloats * 4) : 0, 0x00020000);
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int lrow = u * 8 + (lane >> 3), q = lane & 7;
@@ -1136,7 +1230,7 @@ __global__ __launch_bounds__(256) void k_mix_bf16(MixArgs a) {
         const u32x4 bits = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
         __builtin_amdgcn_raw_buffer_store_b128(bits, rsrc, (int)(off * 4), 0, 16);   // aux 16 = sc1
       } else {
-        *reinterpret_cast<float4*>(a.out + off) = v;
+        *reinterpret_cast<float4*>(outp + off) = v;
       }
     }
   }

@@ -132,7 +132,8 @@ __device__ __forceinline__ int swz(int row, int col, int spr) {
 
 // ---- operand precision of the K loop ----------------------------------------------------------------------------
 // BF = false: fp32 operands on v_mfma_f32_16x16x4_f32 (the product path, bit-for-bit an fp32 fma chain).
-// BF = true (matgcn_set_mix_precision(2), inference only, a side line with its own tolerance): the node-adaptive weights
+// BF = true (matgcn_set_mix_precision(2) / matgcn_set_train_precision(2), a side line with its own tolerance; the SAVE
+// instantiations keep the same fp32 activations as the fp32 training forward): the node-adaptive weights
 // arrive as a bf16 copy of the same fragment stream - HALF the bytes of the one big stream of these kernels - and the A
 // rows are rounded to bf16 on their way into LDS; one v_mfma_f32_16x16x16_bf16 per k-group, fp32 accumulation.  A lane's
 // four bf16 of a k-group are exactly the four fp32 of its float4 in the fp32 stream (k = 16 g + 4 (l >> 4) + s), so both
@@ -346,7 +347,6 @@ inline unsigned node_items(int N, int rows, int blockRows) {
 template <bool SAVE, int ROWS, bool BF = false>
 __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_gate16(Node16Args a) {
   typedef typename NodeOp<BF>::T Op;
-  static_assert(!(SAVE && BF), "the training forward runs fp32 operands");
   constexpr int NRT = ROWS / 16, CH = ROWS * 64;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* Hs = lds;               // [ROWS][16 slots] the state rows: chunk 0, and the h of z*h
@@ -397,6 +397,7 @@ __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_gate16(Node16Args a) {
   __syncthreads();
   float* Zt = Gb;                // z tile (BF: z*h, the LDS state copy is bf16 there)
   float* Rt = Gb + CH;           // SAVE: r tile
+  float* Zs = BF ? Hs : Zt;      // SAVE: z tile (BF: in the state chunk, dead after the K loop - z*h took h from memory)
   const int o = 16 * w + j;
   if (a.raw) {                   // unit entry point: pre-activation dump
 #pragma unroll
@@ -417,8 +418,12 @@ __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_gate16(Node16Args a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int lb = rt * 16 + 4 * kq + e;
-        if constexpr (BF) Zt[swz(lb, o, 16)] = acc[rt][e] * hz[rt][e];
-        else Zt[swz(lb, o, 16)] = acc[rt][e];
+        if constexpr (BF) {
+          Zt[swz(lb, o, 16)] = acc[rt][e] * hz[rt][e];
+          if constexpr (SAVE) Zs[swz(lb, o, 16)] = acc[rt][e];
+        } else {
+          Zt[swz(lb, o, 16)] = acc[rt][e];
+        }
       }
   } else {
     const size_t base = (((((size_t)n * RB + rb) * 4 + (w - 4)) * 4) + rtb) * 256 + (size_t)lane * 4;
@@ -446,7 +451,7 @@ __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_gate16(Node16Args a) {
     }
     store_wt16(a.zh, ((size_t)b * a.Np + n) * 64 + q * 4, v);
     if constexpr (SAVE) {
-      save16(a.svZ, ((size_t)b * a.Np + n) * 64 + q * 4, z);
+      save16(a.svZ, ((size_t)b * a.Np + n) * 64 + q * 4, BF ? *reinterpret_cast<const float4*>(&Zs[at]) : z);
       save16(a.svR, ((size_t)b * a.Np + n) * 64 + q * 4, *reinterpret_cast<const float4*>(&Rt[at]));
     }
   }
@@ -614,7 +619,6 @@ __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_update16(Node16Args a) 
   float* SV = lds + 4 * CH;      // SAVE only (80 KB of LDS): the tile an activation passes through on its way to the
                                  // training buffer - hc, then z2 - so that it is saved as float4 rows (round 4; scalar
                                  // stores from the accumulator layout were 64-byte pieces, +1.1 ms per training forward)
-  static_assert(!(SAVE && BF), "the training forward runs fp32 operands");
   int n, rbr;
   if (!node_item(blockIdx.x, (a.rows + ROWS - 1) / ROWS, a.N, n, rbr)) return;
   const int rowBase = rbr * ROWS;

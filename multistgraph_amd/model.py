@@ -113,10 +113,20 @@ def _is_series_batch(batch) -> bool:
     return isinstance(batch, dict) and "label_start" in batch and "series" in batch
 
 
+HIP_PRECISIONS = {"fp32": 0, "bf16_mix": 1, "bf16": 2}   # config['hip_precision'] -> matgcn_set_*_precision mode
+
+
+def _precision_mode(name) -> int:
+    if name not in HIP_PRECISIONS:
+        raise ValueError("hip_precision = %r: expected one of %s" % (name, ", ".join(sorted(HIP_PRECISIONS))))
+    return HIP_PRECISIONS[name]
+
+
 class _TrainStep(torch.autograd.Function):
     """autograd node of one training-mode forward: matgcn_forward_train / matgcn_backward.
     The parameters ride along as inputs so that autograd routes their gradients; X gets none (the reference
-    never differentiates w.r.t. the batch)."""
+    never differentiates w.r.t. the batch).  The backward runs in the precision mode of its forward (the library
+    records it per train buffer)."""
 
     @staticmethod
     def forward(ctx, path, x, drop_mask, h0, names, *params):
@@ -134,6 +144,7 @@ class _TrainStep(torch.autograd.Function):
             raise RuntimeError("MultiATGCN backward: another forward ran on this model between this forward and its "
                                "backward; the saved activations live in the shared workspace (one graph at a time)")
         state = {k: p for k, p in zip(ctx.names, ctx.params)}
+        # (no precision setting here: the library runs the backward in the mode its forward_train ran with)
         grads = path.backward(ctx.x, d_out.contiguous(), state, ctx.mask, ctx.h0)
         # the initial state (static features, :406-409) gets its gradient back: torch autograd carries it on through
         # expand() and static_initial_gru
@@ -153,6 +164,12 @@ class MultiATGCN(AbstractTrafficStateModel):
         self.node_specific_off = get("node_specific_off", False)
         self.fnn_off = get("fnn_off", False)
         self.gcn_off = get("gcn_off", False)
+        # operand precision of the HIP kernels (not a reference key): "fp32" (default) | "bf16_mix" (bf16 operands for the
+        # graph mixes) | "bf16" (also for the node-wise contractions); fp32 accumulation and fp32 state, parameters and
+        # gradients in every mode.  Applies to this model's inference forwards and training steps; an attribute, so a
+        # model can train in bf16 and evaluate in fp32 by reassigning it.
+        self.hip_precision = get("hip_precision", "fp32")
+        _precision_mode(self.hip_precision)
         self.batch_size = get("batch_size", 64)
         self.device = get("device", torch.device("cpu"))
         config["num_nodes"] = self.num_nodes  # the reference writes this back (:233)
@@ -279,6 +296,10 @@ class MultiATGCN(AbstractTrafficStateModel):
             self._prepared_key = None
         if self._static_host is not None and (self._static_dev is None or self._static_dev.device != device):
             self._static_dev = self._static_host.to(device).contiguous()
+        # "fp32" leaves the library settings alone (process-wide matgcn_set_*_precision calls still apply, as before this
+        # key existed); the bf16 modes are set around each of this model's library calls and restored afterwards
+        mode = _precision_mode(self.hip_precision)
+        hp.precision = mode if mode else None
         key = (id(hp),) + self._params_key()
         if key != self._prepared_key or not self.cache_prepared:
             hp.bind(self._state(), self._static_dev)

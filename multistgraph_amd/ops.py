@@ -7,6 +7,7 @@ device pointers and the current HIP stream cross the boundary.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
@@ -314,6 +315,11 @@ class HotPath:
         self._train = None
         self.train_generation = 0
         self.grad_bucket: Optional[torch.Tensor] = None   # flat buffer the gradients of the LAST backward() are views of
+        # precision mode of this binding's calls (1 bf16 graph mixes, 2 + bf16 node-wise contractions, 0 fp32): the
+        # library settings are process-global, so every call sets the one it needs and restores the previous value
+        # (matgcn_set_mix_precision for the inference forwards, matgcn_set_train_precision for the training step).
+        # None (default): the calls leave the settings as they are - whatever the process set, fp32 unless it did.
+        self.precision: Optional[int] = None
 
     # ---- plumbing ------------------------------------------------------------------------------
     def _stream(self):
@@ -324,20 +330,42 @@ class HotPath:
         self.train_generation += 1
         return C.c_void_p(self.workspace.data_ptr()), C.c_size_t(self.workspace.numel() * 4)
 
-    def _with_workspace(self, call, what: str) -> None:
+    def _with_workspace(self, call, what: str, train: bool = False) -> None:
         """Run ``call(ws_ptr, ws_bytes)``; a workspace that is too small for the CURRENT library mode - precision mode 2
         was switched on after this binding sized it: the bf16 weight-stream copies are counted only while that mode is
-        set - is re-sized once and the call repeated."""
+        set - is re-sized once and the call repeated (train: the train buffer too - matgcn_train_bytes counts the bf16
+        copies of the plain weights while training precision mode 2 is set)."""
         ws, wsb = self._ws()
         status = call(ws, wsb)
         if status == -4:      # MATGCN_ERR_SMALL_BUFFER
             nbytes = C.c_size_t()
+            grown = False
             _lib.check(self.lib.matgcn_workspace_bytes(C.byref(self.dims), C.byref(nbytes)), "matgcn_workspace_bytes")
             if nbytes.value > self.workspace.numel() * 4:
                 self.workspace = torch.empty(nbytes.value // 4, dtype=torch.float32, device=self.device)
+                grown = True
+            if train and self._train is not None:
+                _lib.check(self.lib.matgcn_train_bytes(C.byref(self.dims), C.byref(nbytes)), "matgcn_train_bytes")
+                if nbytes.value > self._train.numel() * 4:
+                    self._train = None
+                    self._train_buffer()
+                    grown = True
+            if grown:
                 ws, wsb = self._ws()
                 status = call(ws, wsb)
         _lib.check(status, what)
+
+    @contextlib.contextmanager
+    def _mode(self, setter):
+        """the library setting ``setter`` at this binding's precision for the calls inside (None: untouched)"""
+        if self.precision is None:
+            yield
+            return
+        prev = setter(int(self.precision))
+        try:
+            yield
+        finally:
+            setter(prev)
 
     def bind(self, state: Dict[str, torch.Tensor], static_supports: Optional[torch.Tensor]):
         """Point matgcn_params at the tensors of a reference-named state dict."""
@@ -460,9 +488,10 @@ class HotPath:
         h0 = self._h0(h0)
         self._need_prepared()
         out = torch.empty(self.batch, s.out_window, s.nodes, s.out_dim, dtype=torch.float32, device=self.device)
-        self._with_workspace(lambda ws, wsb: self.lib.matgcn_forward(
-            C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()), C.c_void_p(x.data_ptr()),
-            C.c_void_p(_ptr(h0)), C.c_void_p(out.data_ptr()), ws, wsb, self._stream()), "matgcn_forward")
+        with self._mode(self.lib.matgcn_set_mix_precision):
+            self._with_workspace(lambda ws, wsb: self.lib.matgcn_forward(
+                C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()), C.c_void_p(x.data_ptr()),
+                C.c_void_p(_ptr(h0)), C.c_void_p(out.data_ptr()), ws, wsb, self._stream()), "matgcn_forward")
         return out
 
     # ---- training step ---------------------------------------------------
@@ -490,15 +519,14 @@ class HotPath:
         drop_mask = self._mask(drop_mask)
         h0 = self._h0(h0)
         self._need_prepared()
-        tr = self._train_buffer()
+        self._train_buffer()
         out = torch.empty(self.batch, s.out_window, s.nodes, s.out_dim, dtype=torch.float32, device=self.device)
-        ws, wsb = self._ws()
-        _lib.check(self.lib.matgcn_forward_train(C.byref(self.dims), C.byref(self.params),
-                                                 C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
-                                                 C.byref(src) if src is not None else None,
-                                                 C.c_void_p(_ptr(h0)), C.c_void_p(_ptr(drop_mask)),
-                                                 C.c_void_p(out.data_ptr()), ws, wsb, C.c_void_p(tr.data_ptr()),
-                                                 C.c_size_t(tr.numel() * 4), self._stream()), "matgcn_forward_train")
+        with self._mode(self.lib.matgcn_set_train_precision):
+            self._with_workspace(lambda ws, wsb: self.lib.matgcn_forward_train(
+                C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
+                C.byref(src) if src is not None else None, C.c_void_p(_ptr(h0)), C.c_void_p(_ptr(drop_mask)),
+                C.c_void_p(out.data_ptr()), ws, wsb, C.c_void_p(self._train.data_ptr()),
+                C.c_size_t(self._train.numel() * 4), self._stream()), "matgcn_forward_train", train=True)
         return out
 
     D_H0 = "__d_h0__"   # key of the initial-state gradient in backward()'s result
@@ -522,7 +550,8 @@ class HotPath:
                  drop_mask: Optional[torch.Tensor] = None, h0: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """Gradients of every tensor of `state` (the dict bind() saw) that the loss depends on, keyed by the same
         names; must directly follow the matching forward_train (same workspace, same train buffer).  With h0 (the
-        tensor forward_train saw) the result also holds its gradient (L, B, N, H) under HotPath.D_H0."""
+        tensor forward_train saw) the result also holds its gradient (L, B, N, H) under HotPath.D_H0.  The library runs
+        the backward in the precision mode of the matching forward_train, whatever the settings are now."""
         s = self.spec
         xp, src, _keep = self._source(x)
         d_out = _check_tensor(d_out, "d_out", (self.batch, s.out_window, s.nodes, s.out_dim))
@@ -571,7 +600,7 @@ class HotPath:
             if name not in grads and (t.requires_grad or not isinstance(t, torch.nn.Parameter)):   # adaptive adjacency)
                 grads[name] = views[name].zero_()
         tr = self._train_buffer()
-        ws, wsb = self._ws()
+        ws, wsb = self._ws()   # (the workspace as forward_train left it: no re-sizing here)
         _lib.check(self.lib.matgcn_backward(C.byref(self.dims), C.byref(self.params),
                                             C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
                                             C.byref(src) if src is not None else None,
@@ -600,10 +629,11 @@ class HotPath:
         self._need_prepared()
         out = torch.empty(self.batch, s.out_window, s.nodes, s.out_dim, dtype=torch.float32, device=self.device)
         rel_c = (C.c_int32 * len(rel))(*rel)
-        self._with_workspace(lambda ws, wsb: self.lib.matgcn_forward_series(
-            C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()),
-            C.c_void_p(series.data_ptr()), C.c_int64(series.shape[0]), C.c_void_p(label_start.contiguous().data_ptr()),
-            rel_c, C.c_void_p(_ptr(h0)), C.c_void_p(out.data_ptr()), ws, wsb, self._stream()), "matgcn_forward_series")
+        with self._mode(self.lib.matgcn_set_mix_precision):
+            self._with_workspace(lambda ws, wsb: self.lib.matgcn_forward_series(
+                C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()),
+                C.c_void_p(series.data_ptr()), C.c_int64(series.shape[0]), C.c_void_p(label_start.contiguous().data_ptr()),
+                rel_c, C.c_void_p(_ptr(h0)), C.c_void_p(out.data_ptr()), ws, wsb, self._stream()), "matgcn_forward_series")
         return out
 
     def fuse_heads(self, x: torch.Tensor) -> torch.Tensor:

@@ -1,6 +1,8 @@
 """Training steps of the bench workload (default Baltimore 403, B=64): forward_train + backward through the plugin
-surface (calculate_loss().backward()), timed with HIP events.  usage: train_step.py [workload] [steps] [serial|wave] [batch]
-(serial: matgcn_set_wavefront(0) - every kernel alone on one stream, so a profiler's durations are the kernels' own)"""
+surface (calculate_loss().backward()), timed with HIP events.
+usage: train_step.py [workload] [steps] [serial|wave] [batch] [fp32|bf16_mix|bf16]
+(serial: matgcn_set_wavefront(0) - every kernel alone on one stream, so a profiler's durations are the kernels' own;
+the last argument is the model's hip_precision; the last line gives the medians over the steps after the first three)"""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,6 +17,8 @@ if len(sys.argv) > 4:
 dev = torch.device("cuda:0")
 model, df, cfg = bench.build_model(w, dev, 0)
 model.train()
+if len(sys.argv) > 5:
+    model.hip_precision = sys.argv[5]
 if len(sys.argv) > 3 and sys.argv[3] == "serial":
     from multistgraph_amd import _lib
     _lib.load().matgcn_set_wavefront(0)
@@ -22,6 +26,7 @@ x_np, y_np = syn.make_batch_arrays(w["batch"], w["nodes"], w["out"], 0, feat=2)
 batch = {"X": torch.from_numpy(x_np).to(dev), "y": torch.from_numpy(y_np).to(dev)}
 opt = torch.optim.Adam(model.parameters(), lr=1e-3)
 ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+times = []
 for i in range(steps):
     opt.zero_grad()
     ev[0].record()
@@ -32,8 +37,14 @@ for i in range(steps):
     opt.step()
     ev[3].record()
     torch.cuda.synchronize()
+    times.append((ev[0].elapsed_time(ev[3]), ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])))
     print("step %d loss %.5f  forward %.2f ms  backward %.2f ms  adam %.2f ms" % (
         i, float(loss), ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2]), ev[2].elapsed_time(ev[3])), flush=True)
 print("train buffer %.2f GB  workspace %.2f GB  peak torch memory %.2f GB" % (
     next(iter(model._paths.values()))._train.numel() * 4 / 2**30,
     next(iter(model._paths.values())).workspace.numel() * 4 / 2**30, torch.cuda.max_memory_allocated() / 2**30))
+if len(times) > 3:
+    import statistics
+    med = [statistics.median(t[k] for t in times[3:]) for k in range(3)]
+    print("median of %d steps (%s, B = %d, %s): step %.3f ms  forward %.3f ms  backward %.3f ms" % (
+        len(times) - 3, name, w["batch"], model.hip_precision, med[0], med[1], med[2]))
