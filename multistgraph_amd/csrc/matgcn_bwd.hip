@@ -120,9 +120,9 @@ int mix_transposed(const Bwd& b, const float* src, int rows, int Cc, float* dst,
       a.nRowTiles = (P.N + 31) / 32;
       const dim3 grid((unsigned)(a.nRowTiles * (rows / 2)), (unsigned)a.parts);
       // training precision mode >= 1 (matgcn_set_train_precision): bf16 operands, fp32 accumulation
-      if (g_tmix_bf16_now) hipLaunchKernelGGL(k_mix_n32<true>, grid, dim3(256), 0, b.c.s, a);
+      if (b.c.prec.mix) hipLaunchKernelGGL(k_mix_n32<true>, grid, dim3(256), 0, b.c.s, a);
       else hipLaunchKernelGGL(k_mix_n32<false>, grid, dim3(256), 0, b.c.s, a);
-    } else if (g_tmix_bf16_now) {
+    } else if (b.c.prec.mix) {
       hipLaunchKernelGGL(k_mix_bf16<2>, dim3((unsigned)(a.nRowTiles * rows), (unsigned)a.parts), dim3(256), 0, b.c.s, a);
     } else {
       hipLaunchKernelGGL(k_mix<2>, dim3((unsigned)(a.nRowTiles * rows), (unsigned)a.parts), dim3(256), 0, b.c.s, a);
@@ -613,7 +613,7 @@ int bwd_x_chunk(Pass& pass, const LayerBufs& L, int t0, int t1) {
   LAYER_LOCALS(L);
   const Bwd& bx = pass.bx;
   hipStream_t xs = pass.xs;
-  const bool bfn = g_tnode_bf16_now;   // training precision mode 2: bf16 weight copies in the node contractions
+  const bool bfn = c.prec.node;   // training precision mode 2: bf16 weight copies in the node contractions
   float* DAgBelow = tr + R.oDAg[(l - 1) & 1];
   const size_t last = (size_t)(T - 1) * B;
   if (t1 == T) {   // the first chunk processed: what the whole layer needs once
@@ -662,7 +662,7 @@ int bwd_chain(Pass& pass, const LayerBufs& L) {
   LAYER_LOCALS(L);
   // training precision mode 2: the node contractions of the fused kernels stream the bf16 weight copies (the pair of
   // kernels for more than four dense slots stays fp32)
-  const bool bfn = g_tnode_bf16_now;
+  const bool bfn = c.prec.node;
   // ---------------- chain ----------------
   for (int t = T - 1; t >= 0; --t) {
     const size_t at = (size_t)t * slab;
@@ -826,7 +826,7 @@ int bwd_x_columns(Pass& pass, const LayerBufs& L) {
       a.outFloats = (long)N * cols;
       a.Np = P.NpC; a.N = N; a.Ks = 1; a.nK = P.Ks * Np / 16; a.nColTiles = (int)(cols / 64);
       a.nRowTiles = P.NpC / 64;
-      if (g_tmix_bf16_now) hipLaunchKernelGGL(k_mix_bf16<2>, dim3((unsigned)(a.nRowTiles * a.nColTiles), 1u), dim3(256), 0, s, a);
+      if (c.prec.mix) hipLaunchKernelGGL(k_mix_bf16<2>, dim3((unsigned)(a.nRowTiles * a.nColTiles), 1u), dim3(256), 0, s, a);
       else hipLaunchKernelGGL(k_mix<2>, dim3((unsigned)(a.nRowTiles * a.nColTiles), 1u), dim3(256), 0, s, a);
       CHECK_LAUNCH();
     } else if (P.Ks > 0) {
@@ -838,8 +838,8 @@ int bwd_x_columns(Pass& pass, const LayerBufs& L) {
                        P.Ks > 0 ? MixN : nullptr, DAx, dXall, (size_t)rowsTB, N, Np, C);
     CHECK_LAUNCH();
   } else if (l == 0) {   // a 64-channel input layer: nothing below to ride with
-    RETURN_IF(node_contract(b, DPG, g_tnode_bf16_now ? L.WpG16 : WpG, DPU, g_tnode_bf16_now ? L.WpU16 : WpU, I, 0, rowsTB,
-                            DAx, 0.f, g_tnode_bf16_now));
+    const bool bfn = c.prec.node;
+    RETURN_IF(node_contract(b, DPG, bfn ? L.WpG16 : WpG, DPU, bfn ? L.WpU16 : WpU, I, 0, rowsTB, DAx, 0.f, bfn));
     RETURN_IF(zero_async(dXall, (long)rowsTB * Np * C, s));
     RETURN_IF(mix_transposed(b, DAx, rowsTB, C, dXall));
     hipLaunchKernelGGL(k_add_slot0, dim3(blocks_for((size_t)rowsTB * Np * C)), dim3(256), 0, s, dXall, DAx,
@@ -1284,15 +1284,9 @@ int backward_impl(Bwd& b, const float* dOut) {
   // chain of the layer below (small dependent launches); matgcn_set_wavefront(0) keeps everything on one stream
   RETURN_IF(wavefront_ready());
   q.fusedLds = 128 * CF_LD * (int)sizeof(float);
-  {
-    static bool optedIn[MAX_DEVICES] = {false};   // dynamic LDS above 64 KB must be opted into once per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) dev = 0;
-    if (!optedIn[dev]) {
-      HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain_res_fused<64>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, q.fusedLds));
-      optedIn[dev] = true;
-    }
+  if (DeviceState& dev = dev_current(); !dev.chainFusedLds) {
+    RETURN_IF(lds_opt_in(reinterpret_cast<const void*>(k_chain_res_fused<64>), q.fusedLds));
+    dev.chainFusedLds = true;
   }
   q.twoStreams = g_wavefront_mode != 0 && P.L > 1 && !P.gcnOff;
   q.ws = q.twoStreams ? g_wf.chain[1] : q.s;
@@ -1412,7 +1406,7 @@ static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* para
   if (mode == 2 && !P.gcnOff && (workspace_bytes < (size_t)P.workspaceFloatsBf16 * sizeof(float) ||
                                  train_bytes < (size_t)c.R.floatsBf16 * sizeof(float)))
     return MATGCN_ERR_SMALL_BUFFER;   // sized without mode 2's bf16 copies
-  MixPrecisionScope mixScope(mode);
+  c.prec = precision_of(mode);
   note_train_mode(train, -1);   // until this call has enqueued everything: a backward on this buffer is refused
   // the forward kernels write the rows of the real nodes only: the rows of the padding nodes must read as zero.  The
   // saved tensors are contiguous [T][B][Np][64] blocks, so one launch clears the padding rows of all of them.
@@ -1493,7 +1487,7 @@ static int backward_entry(const matgcn_dims* dims, const matgcn_params* params, 
   const int mode = train_mode_of(train);
   if (mode < 0) return MATGCN_ERR_BAD_ARG;
   if (mode == 2 && !b.c.P.gcnOff && train_bytes < (size_t)b.c.R.floatsBf16 * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;
-  MixPrecisionScope mixScope(mode, true);
+  b.c.prec = precision_of(mode);
   JOINED(backward_impl(b, d_out), stream);
 }
 

@@ -349,12 +349,6 @@ struct Wavefront {
 // process that drives several GPUs (or the rehearsal runs that put two ranks on one box) must not share them.
 // (One host thread per device at a time, like the rest of the library: the reference is single-threaded too.)
 constexpr int MAX_DEVICES = 64;
-Wavefront g_wfs[MAX_DEVICES];
-inline Wavefront& wf_current() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) dev = 0;
-  return g_wfs[dev];
-}
 
 // Lazy prepare (matgcn_set_lazy_prepare(1); off by default: the plain contract is "prepared is complete in stream order
 // when matgcn_prepare returns").  The node-adaptive weight streams - 250 MB, most of matgcn_prepare's time - are written
@@ -367,13 +361,24 @@ struct PrepEvents {
   bool ready = false, pending = false;
   hipEvent_t l0[2], l1[2];
 };
-PrepEvents g_prep[MAX_DEVICES];
 int g_lazy_prepare = 0;
-inline PrepEvents& prep_current() {
+// everything the library keeps per device ordinal, and the one place that asks which device is current
+struct DeviceState {
+  Wavefront wf;
+  PrepEvents prep;
+  int nodeLds = 0;           // node_kernels_ready: dynamic LDS bytes the node kernels are opted into (function
+                             // attributes are per device)
+  bool chainFusedLds = false;   // backward_impl: k_chain_res_fused<64> is opted into its dynamic LDS
+};
+DeviceState g_dev[MAX_DEVICES];
+inline int current_device() {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) dev = 0;
-  return g_prep[dev];
+  return dev;
 }
+inline DeviceState& dev_current() { return g_dev[current_device()]; }
+inline Wavefront& wf_current() { return dev_current().wf; }
+inline PrepEvents& prep_current() { return dev_current().prep; }
 int prep_events_ready() {
   PrepEvents& E = prep_current();
   if (E.ready) return MATGCN_OK;
@@ -402,23 +407,6 @@ int g_wavefront_mode = 1;     // matgcn_set_wavefront: 0 serial, 1 free-running 
 int g_mix_precision = 0;      // matgcn_set_mix_precision: 0 fp32 operands, 1 bf16 operands for the inference graph mixes,
                               // 2 bf16 operands for the graph mixes AND the node-wise contractions (bf16 weight streams)
 int g_train_precision = 0;    // matgcn_set_train_precision: the same values for matgcn_forward_train / matgcn_backward
-bool g_mix_bf16_now = false;  // set for the duration of a forward whose mode asks for it (MixPrecisionScope)
-bool g_node_bf16_now = false;
-bool g_tmix_bf16_now = false; // backward: bf16 operands for the transposed graph mixes (mode of the matching forward_train)
-bool g_tnode_bf16_now = false;// backward, mode 2: bf16 weight copies for the node-wise data-gradient contractions
-// mode: the precision setting that governs the call in flight (g_mix_precision for the inference forwards,
-// g_train_precision - or, in the backward, the mode its forward_train ran with - for training)
-struct MixPrecisionScope {
-  explicit MixPrecisionScope(int mode, bool backward = false) {
-    g_mix_bf16_now = !backward && mode >= 1;
-    g_node_bf16_now = !backward && mode == 2;
-    g_tmix_bf16_now = backward && mode >= 1;
-    g_tnode_bf16_now = backward && mode == 2;
-  }
-  ~MixPrecisionScope() {
-    g_mix_bf16_now = false; g_node_bf16_now = false; g_tmix_bf16_now = false; g_tnode_bf16_now = false;
-  }
-};
 // The backward follows the mode its forward_train ran with: forward_train notes (device, train buffer) -> mode here and
 // matgcn_backward looks its train buffer up (a buffer without an entry runs with the current setting).  The last
 // TRAIN_MODE_SLOTS buffers are remembered - far more than the one per model a training loop keeps.
@@ -426,11 +414,6 @@ constexpr int TRAIN_MODE_SLOTS = 64;
 struct TrainModeRec { int dev; const void* train; int mode; };
 TrainModeRec g_train_modes[TRAIN_MODE_SLOTS];
 int g_train_modes_next = 0;
-inline int current_device() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  return dev;
-}
 void note_train_mode(const void* train, int mode) {
   const int dev = current_device();
   for (int i = 0; i < TRAIN_MODE_SLOTS; ++i)
@@ -543,8 +526,6 @@ void join_library_streams(hipStream_t caller) {
 // the caller's stream and joined back into it before they return - success or failure - so the caller still sees one
 // in-order stream - in the own-pool mode (matgcn_set_stream_pool(1)) only.  See wavefront_ready() for why.  (matgcn_set_wavefront(0), the one-stream schedule for kernel timing,
 // keeps the caller's stream.)
-int wavefront_ready();
-extern int g_wavefront_mode;
 template <class Body>
 int on_main_stream(void* callerStream, Body&& body) {
   if (!g_stream_pool || g_wavefront_mode == 0) return body(callerStream);
@@ -559,8 +540,8 @@ int on_main_stream(void* callerStream, Body&& body) {
   return rc;
 }
 
-// out[(k,n)][col] = sum_m S_k[n][m] X[m][col]; see k_mix
-int launch_mix(const Plan& P, const float* St, const float* X, long xTileStride, int ldX, int nColTiles,
+// out[(k,n)][col] = sum_m S_k[n][m] X[m][col]; see k_mix.  bf16: the call's Precision::mix
+int launch_mix(const Plan& P, bool bf16, const float* St, const float* X, long xTileStride, int ldX, int nColTiles,
                float* out, long sN, long sK, long sT, int Ks, int rowsM, hipStream_t s, bool stepRole = false,
                long outFloats = 0) {
   if (Ks <= 0 || rowsM <= 0) return MATGCN_OK;   // every support folded away: nothing to mix
@@ -571,7 +552,7 @@ int launch_mix(const Plan& P, const float* St, const float* X, long xTileStride,
   a.nRowTiles = (int)(rup(rowsM, 64) / 64);
   ProfScope prof(stepRole ? MATGCN_PROF_MIX : MATGCN_PROF_MIX_PRE, s);
   const dim3 grid((unsigned)(a.nRowTiles * nColTiles));
-  if (g_mix_bf16_now) {   // opt-in bf16-operand variant of the inference forward (fp32 accumulate, fp32 in / out)
+  if (bf16) {   // opt-in bf16-operand variant of the inference forward (fp32 accumulate, fp32 in / out)
     if (stepRole) hipLaunchKernelGGL(k_mix_bf16<1>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_mix_bf16<0>, grid, dim3(256), 0, s, a);
   } else if (a.nK > 64) {   // more than 1 024 reduction indices: partial sums every 256 (k_mix's FLUSH)
@@ -594,10 +575,10 @@ int launch_mix(const Plan& P, const float* St, const float* X, long xTileStride,
 
 // mix of `rows` contiguous [Np][64] slabs into the node-major buffer G [N][rows][Ks][64]
 // (nodeStride: floats between the nodes of G when the `rows` rows are a slice of a larger node-major block)
-int mix_rows(const Plan& P, const float* St, const float* X, int rows, float* G, hipStream_t s, bool stepRole = false,
+int mix_rows(const Plan& P, bool bf16, const float* St, const float* X, int rows, float* G, hipStream_t s, bool stepRole = false,
              long nodeStride = 0) {
   const long sN = nodeStride ? nodeStride : (long)rows * P.Ks * H;
-  return launch_mix(P, St, X, (long)P.Np * H, H, rows, G, sN, H, (long)P.Ks * H, P.Ks, P.Ks * P.Np, s, stepRole,
+  return launch_mix(P, bf16, St, X, (long)P.Np * H, H, rows, G, sN, H, (long)P.Ks * H, P.Ks, P.Ks * P.Np, s, stepRole,
                     (long)(P.N - 1) * sN + (long)rows * P.Ks * H);
 }
 
@@ -624,6 +605,13 @@ StackMap build_stack_map(const Plan& P, const matgcn_dims* D, const matgcn_param
   return map;
 }
 
+// Which operands of a call are bf16: `mix` - the graph mixes (transposed ones in the backward), `node` - the node-wise
+// contractions (bf16 copies of the weight streams).  The four hot entry points read their mode once, on entry
+// (matgcn_forward / matgcn_forward_series: g_mix_precision; matgcn_forward_train: g_train_precision; matgcn_backward:
+// the mode of its forward_train), and every launch helper below them reads it from the context it is handed.
+struct Precision { bool mix = false, node = false; };
+inline Precision precision_of(int mode) { return Precision{mode >= 1, mode == 2}; }   // modes of matgcn_set_*_precision
+
 struct Ctx {
   Plan P;
   const matgcn_dims* D;
@@ -636,42 +624,68 @@ struct Ctx {
   TrainPlan R;
   const float* dropMask = nullptr;   // matgcn_forward_train: (B, headT, N, H) dropout mask of the head's input, applied by the
                                      // top layer's update kernel as it writes the sequence (graph layers)
+  Precision prec;             // fp32 unless a hot entry point sets it: matgcn_prepare and the unit entry points
+                              // (matgcn_agcn_gate_fwd, matgcn_encoder_fwd, ...) deliberately leave the default
 };
 
 // dynamic LDS: k_gate16 48 KB (state chunk + two ping-pong chunks), k_update16 64 KB (+ the x_t tile of the residual
-// cell), k_px16 the whole tile; sizes above 64 KB must be opted into once per kernel
+// cell), k_px16 the whole tile
 constexpr int GATE_LDS = 3 * 64 * 64 * (int)sizeof(float);
 constexpr int UPDATE_LDS = 4 * 64 * 64 * (int)sizeof(float);
 constexpr int UPDATE_SAVE_LDS = 5 * 64 * 64 * (int)sizeof(float);   // training: + the tile saved activations pass through
+// Every instantiation of the node kernels the library launches, once: node_kernels_ready opts each into its dynamic LDS
+// and the launch sites look theirs up here (launch_node; hoist_x for k_px16).  Selectors: mode - k_update16's MODE (0 graph
+// cell alone, 1 + residual cell and blend, 2 residual cell alone; k_gate16 has none: 0), save - training keeps z, r, hc,
+// rows - of a (node, row block) work item, bf - bf16 copies of the weight streams.
+struct NodeVariant { int mode; bool save; int rows; bool bf; void (*fn)(Node16Args); int lds; };
+const NodeVariant GATE16[] = {
+    {0, false, 64, false, k_gate16<false, 64>, GATE_LDS},
+    {0, true, 64, false, k_gate16<true, 64>, GATE_LDS},
+    {0, false, 64, true, k_gate16<false, 64, true>, GATE_LDS},
+    {0, true, 64, true, k_gate16<true, 64, true>, GATE_LDS},
+    // 32-row work items (batches of at most 32 rows, graphs of at most 256 nodes: cell_phase)
+    {0, false, 32, false, k_gate16<false, 32>, GATE_LDS / 2},
+    {0, true, 32, false, k_gate16<true, 32>, GATE_LDS / 2},
+};
+const NodeVariant UPDATE16[] = {
+    {0, false, 64, false, k_update16<0, false, 64>, UPDATE_LDS},
+    {1, false, 64, false, k_update16<1, false, 64>, UPDATE_LDS},
+    {1, true, 64, false, k_update16<1, true, 64>, UPDATE_SAVE_LDS},
+    {1, false, 64, true, k_update16<1, false, 64, true>, UPDATE_LDS},
+    {1, true, 64, true, k_update16<1, true, 64, true>, UPDATE_SAVE_LDS},
+    {1, false, 32, false, k_update16<1, false, 32>, UPDATE_LDS / 2},
+    {1, true, 32, false, k_update16<1, true, 32>, UPDATE_SAVE_LDS / 2},
+    {2, false, 64, false, k_update16<2, false, 64>, UPDATE_LDS},
+    {2, true, 64, false, k_update16<2, true, 64>, UPDATE_SAVE_LDS},
+};
+struct PxVariant { int nrt; bool bf; void (*fn)(Px16Args); };   // nrt: row tiles that hold batch rows; LDS: the plan's nodeLds
+const PxVariant PX16[] = {
+    {4, false, k_px16<4, false>}, {2, false, k_px16<2, false>}, {1, false, k_px16<1, false>},
+    {4, true, k_px16<4, true>},   {2, true, k_px16<2, true>},   {1, true, k_px16<1, true>},
+};
+// launches the table's entry for the selectors; a combination without an entry is an error, never another variant
+template <size_t n>
+int launch_node(const NodeVariant (&table)[n], int mode, bool save, int rows, bool bf, const dim3& grid, hipStream_t s,
+                const Node16Args& a) {
+  for (const NodeVariant& v : table)
+    if (v.mode == mode && v.save == save && v.rows == rows && v.bf == bf) {
+      hipLaunchKernelGGL(v.fn, grid, dim3(512), v.lds, s, a);
+      return launch_ok();
+    }
+  return MATGCN_ERR_UNSUPPORTED;
+}
+
+// sizes above 64 KB must be opted into once per kernel and device
+int lds_opt_in(const void* kernel, int bytes) {
+  HIP_OK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  return MATGCN_OK;
+}
 int node_kernels_ready(int ldsBytes) {
-  static int readyOn[MAX_DEVICES] = {0};   // function attributes are per device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) dev = 0;
-  int& ready = readyOn[dev];
+  int& ready = dev_current().nodeLds;
   if (ready >= ldsBytes) return MATGCN_OK;
-  const hipFuncAttribute at = hipFuncAttributeMaxDynamicSharedMemorySize;
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<false, 64>), at, GATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<true, 64>), at, GATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<0, false, 64>), at, UPDATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, false, 64>), at, UPDATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, true, 64>), at, UPDATE_SAVE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<2, false, 64>), at, UPDATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<2, true, 64>), at, UPDATE_SAVE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<false, 64, true>), at, GATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, false, 64, true>), at, UPDATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<true, 64, true>), at, GATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, true, 64, true>), at, UPDATE_SAVE_LDS));
-  // 32-row work items (batches of at most 32 rows, graphs of at most 256 nodes: cell_phase)
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<false, 32>), at, GATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, false, 32>), at, UPDATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gate16<true, 32>), at, GATE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_update16<1, true, 32>), at, UPDATE_SAVE_LDS));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_px16<4, false>), at, ldsBytes));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_px16<2, false>), at, ldsBytes));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_px16<1, false>), at, ldsBytes));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_px16<4, true>), at, ldsBytes));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_px16<2, true>), at, ldsBytes));
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_px16<1, true>), at, ldsBytes));
+  for (const NodeVariant& v : GATE16) RETURN_IF(lds_opt_in(reinterpret_cast<const void*>(v.fn), v.lds));
+  for (const NodeVariant& v : UPDATE16) RETURN_IF(lds_opt_in(reinterpret_cast<const void*>(v.fn), v.lds));
+  for (const PxVariant& v : PX16) RETURN_IF(lds_opt_in(reinterpret_cast<const void*>(v.fn), ldsBytes));
   ready = ldsBytes;
   return MATGCN_OK;
 }
@@ -688,7 +702,7 @@ int fold_x0(const Ctx& c, const float* xin, int Tq, hipStream_t s) {
   hipLaunchKernelGGL(k_x0_to_matrix, dim3(blocks_for((size_t)P.Np * ld)), dim3(256), 0, s, xin, X0m, rows, P.Np, P.C0,
                      ld);
   CHECK_LAUNCH();
-  RETURN_IF(launch_mix(P, St, X0m, 64, ld, ld / 64, MX0, (long)ld, (long)P.Np * ld, 64, P.Ks, P.Ks * P.Np, s));
+  RETURN_IF(launch_mix(P, c.prec.mix, St, X0m, 64, ld, ld / 64, MX0, (long)ld, (long)P.Np * ld, 64, P.Ks, P.Ks * P.Np, s));
   hipLaunchKernelGGL(k_build_xa0, dim3(blocks_for((size_t)Tq * P.N * P.B * P.Kx)), dim3(256), 0, s, xin, MX0,
                      c.ws + P.oXA0, P.B, Tq, P.N, P.Np, P.C0, P.Ks, P.Kx, ld);
   return launch_ok();
@@ -713,7 +727,7 @@ int hoist_x(const Ctx& c, int l, const float* xin, int t0, int nt, hipStream_t s
   float* GX = (c.train ? c.train + c.R.oGX[l] : c.ws + P.oGX[l]) + (size_t)t0 * P.N * P.B * P.Ks * H;
   if (mixedSteps < nt) {
     const int r0 = mixedSteps * P.B;
-    RETURN_IF(mix_rows(P, c.prep + P.oSt, xin + (size_t)mixedSteps * P.B * P.Np * H, rows - r0,
+    RETURN_IF(mix_rows(P, c.prec.mix, c.prep + P.oSt, xin + (size_t)mixedSteps * P.B * P.Np * H, rows - r0,
                        GX + (size_t)r0 * P.Ks * H, s, false, mixedSteps ? (long)rows * P.Ks * H : 0));
   }
   Px16Args a;
@@ -723,18 +737,15 @@ int hoist_x(const Ctx& c, int l, const float* xin, int t0, int nt, hipStream_t s
   ProfScope prof(MATGCN_PROF_PX, s);
   const dim3 grid((unsigned)(rup(P.N, 8) * nt * P.RB));
   // precision mode 2: the bf16 copy of the stream, A rows rounded on their way into LDS
-  const bool bf = g_node_bf16_now;
+  const bool bf = c.prec.node;
   if (bf) a.w = c.ws + P.oW16x[l];
-#define PX16_LAUNCH(NRT)                                                                                   \
-  do {                                                                                                     \
-    if (bf) hipLaunchKernelGGL((k_px16<NRT, true>), grid, dim3(512), P.nodeLds, s, a);                     \
-    else hipLaunchKernelGGL((k_px16<NRT, false>), grid, dim3(512), P.nodeLds, s, a);                       \
-  } while (0)
-  if (P.B <= 16) PX16_LAUNCH(1);         // row tiles that hold batch rows
-  else if (P.B <= 32) PX16_LAUNCH(2);
-  else PX16_LAUNCH(4);
-#undef PX16_LAUNCH
-  return launch_ok();
+  const int nrt = P.B <= 16 ? 1 : P.B <= 32 ? 2 : 4;   // row tiles that hold batch rows
+  for (const PxVariant& v : PX16)
+    if (v.nrt == nrt && v.bf == bf) {
+      hipLaunchKernelGGL(v.fn, grid, dim3(512), P.nodeLds, s, a);
+      return launch_ok();
+    }
+  return MATGCN_ERR_UNSUPPORTED;
 }
 
 // The recurrent mix of layer l at step t+1 (phase 0: mix of h_t) equals the x-part mix of layer l+1 at step t, so in
@@ -781,8 +792,8 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
   if (!shared && c.train && res && !(phase < 2 && sharesUp))
     G = c.train + (phase < 2 ? c.R.oGH[l] : c.R.oGZH[l]) + (size_t)t * P.N * P.B * P.Ks * H;
   float* R = c.ws + P.oR[l];
-  if (phase == 0) return mix_rows(P, St, Hx, P.B, G, s, true, gNodeStride);
-  if (phase == 2) return mix_rows(P, St, ZHx, P.B, G, s, true);
+  if (phase == 0) return mix_rows(P, c.prec.mix, St, Hx, P.B, G, s, true, gNodeStride);
+  if (phase == 2) return mix_rows(P, c.prec.mix, St, ZHx, P.B, G, s, true);
   Node16Args a;
   memset(&a, 0, sizeof(a));
   a.g = G; a.gNodeStride = phase == 1 ? gNodeStride : 0; a.rows = P.B; a.N = P.N; a.Np = P.Np; a.Ks = P.Ks;
@@ -794,7 +805,7 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
   // the chip's 512 workgroup slots empty; as (node, 32-row) items they fill 474 of them (round 3 measured the compile-time
   // variant at N = 237: gate 19.4 -> 18.5 us, update 24.4 -> 22.5 us; round 4 picks it at run time)
   // (round 4: the training instantiations too - at the shipped batch size 16 the training forward ran 64-row tiles)
-  const bool rows32 = (P.B <= 32 || P.N <= 256) && res != nullptr && !raw && !g_node_bf16_now;
+  const bool rows32 = (P.B <= 32 || P.N <= 256) && res != nullptr && !raw && !c.prec.node;
   const dim3 grid(node_items(P.N, P.B, rows32 ? 32 : 64));   // (node, row block) work items, XCD-paired per node
   if (save) {
     const size_t at = (size_t)t * P.B * P.Np * H;
@@ -802,17 +813,11 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
     a.svZ2 = c.train + c.R.oZ2[l] + at; a.svR2 = c.train + c.R.oR2[l] + at; a.svHC2 = c.train + c.R.oHC2[l] + at;
   }
   // precision mode 2 (inference forward or training forward): bf16 copies of the weight streams, made by encoder_chains
-  const bool bf = g_node_bf16_now && res != nullptr && !raw;
+  const bool bf = c.prec.node && res != nullptr && !raw;
   if (phase == 1) {
     a.s = Hx; a.w = bf ? c.ws + P.oW16g[l] : c.prep + P.oWg[l]; a.zh = ZHx; a.r = R; a.raw = raw;
     ProfScope prof(MATGCN_PROF_GATE, s);
-    if (rows32 && save) hipLaunchKernelGGL((k_gate16<true, 32>), grid, dim3(512), GATE_LDS / 2, s, a);
-    else if (rows32) hipLaunchKernelGGL((k_gate16<false, 32>), grid, dim3(512), GATE_LDS / 2, s, a);
-    else if (bf && save) hipLaunchKernelGGL((k_gate16<true, 64, true>), grid, dim3(512), GATE_LDS, s, a);
-    else if (bf) hipLaunchKernelGGL((k_gate16<false, 64, true>), grid, dim3(512), GATE_LDS, s, a);
-    else if (save) hipLaunchKernelGGL((k_gate16<true, 64>), grid, dim3(512), GATE_LDS, s, a);
-    else hipLaunchKernelGGL((k_gate16<false, 64>), grid, dim3(512), GATE_LDS, s, a);
-    return launch_ok();
+    return launch_node(GATE16, 0, save, rows32 ? 32 : 64, bf, grid, s, a);
   }
   a.s = ZHx; a.w = bf ? c.ws + P.oW16u[l] : c.prep + P.oWu[l]; a.r = R; a.h = Hx; a.hout = Hx;
   ProfScope prof(MATGCN_PROF_UPDATE, s);
@@ -825,16 +830,8 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
       a.dropRowStride = (long)P.headT * P.N * H;
       a.seqDrop = c.train + c.R.oSeqDrop + (a.seq - (c.ws + P.oSeq[l]));
     }
-    if (rows32 && save) hipLaunchKernelGGL((k_update16<1, true, 32>), grid, dim3(512), UPDATE_SAVE_LDS / 2, s, a);
-    else if (rows32) hipLaunchKernelGGL((k_update16<1, false, 32>), grid, dim3(512), UPDATE_LDS / 2, s, a);
-    else if (bf && save) hipLaunchKernelGGL((k_update16<1, true, 64, true>), grid, dim3(512), UPDATE_SAVE_LDS, s, a);
-    else if (bf) hipLaunchKernelGGL((k_update16<1, false, 64, true>), grid, dim3(512), UPDATE_LDS, s, a);
-    else if (save) hipLaunchKernelGGL((k_update16<1, true, 64>), grid, dim3(512), UPDATE_SAVE_LDS, s, a);
-    else hipLaunchKernelGGL((k_update16<1, false, 64>), grid, dim3(512), UPDATE_LDS, s, a);
-  } else {
-    hipLaunchKernelGGL((k_update16<0, false, 64>), grid, dim3(512), UPDATE_LDS, s, a);
   }
-  return launch_ok();
+  return launch_node(UPDATE16, res ? 1 : 0, save, rows32 ? 32 : 64, bf, grid, s, a);
 }
 
 // One recurrent step of layer l at step t on the layer's state Hx_l:
@@ -857,8 +854,7 @@ int res_step(const Ctx& c, int l, const float* xt, long xRowStride) {
   a.rows = P.B; a.N = P.N; a.Np = P.Np; a.Ks = P.Ks;
   fill_res_args(c, l, xt, xRowStride, nullptr, nullptr, &a);
   ProfScope prof(MATGCN_PROF_RES, c.s);
-  hipLaunchKernelGGL((k_update16<2, false, 64>), dim3(node_items(P.N, P.B, 64)), dim3(512), UPDATE_LDS, c.s, a);
-  return launch_ok();
+  return launch_node(UPDATE16, 2, false, 64, false, dim3(node_items(P.N, P.B, 64)), c.s, a);
 }
 
 int zero_async(float* p, long floats, hipStream_t s) {
@@ -867,13 +863,6 @@ int zero_async(float* p, long floats, hipStream_t s) {
 
 // the encoder over padded buffers: x0p [B][T][Np][C0] -> Seq_{L-1} (time-major [T][B][Np][64]); finalsUser
 // (L,B,N,H) optional.  Layers run as a wavefront over streams (see Wavefront).
-int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* finalsUser);
-// the encoder: its chains fork onto library streams; a failure between fork and join joins them before returning
-int encoder_padded(const Ctx& c, const float* x0p, const float* h0User, float* finalsUser) {
-  const int rc = encoder_chains(c, x0p, h0User, finalsUser);
-  if (rc != MATGCN_OK) join_library_streams(c.s);
-  return rc;
-}
 int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* finalsUser) {
   const Plan& P = c.P;
   RETURN_IF(node_kernels_ready(P.nodeLds));
@@ -882,8 +871,8 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
   const bool multi = P.L > 1 && g_wavefront_mode != 0;
   const bool lazyPrep = prep_current().pending;
   // one stream, the bf16 copies (they read every stream) and the dense-GRU ablation take everything up front
-  if (lazyPrep && (!multi || g_node_bf16_now || P.gcnOff)) RETURN_IF(prep_wait(c.s, 3));
-  if (g_node_bf16_now && !P.gcnOff) {
+  if (lazyPrep && (!multi || c.prec.node || P.gcnOff)) RETURN_IF(prep_wait(c.s, 3));
+  if (c.prec.node && !P.gcnOff) {
     if (c.wsBytes < (size_t)P.workspaceFloatsBf16 * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;   // sized without mode 2
     // precision mode 2: bf16 copies of the recurrent weight streams into the workspace, once per forward and in front
     // of the fork (every chain reads them); 240 MB of traffic, part of what the side line's time includes
@@ -955,14 +944,11 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
       else fill_res_args(c, l, below + t * stepRows, (long)P.Np * H, nullptr, seq + t * stepRows, &a);
       {
         ProfScope prof(MATGCN_PROF_RES, cs);
-        const dim3 grid(node_items(P.N, P.B, 64));
         if (c.train) {   // training keeps z, r, hc of the dense cell (slots of the residual cell)
           const size_t at = (size_t)t * P.B * P.Np * H;
           a.svZ2 = c.train + c.R.oZ2[l] + at; a.svR2 = c.train + c.R.oR2[l] + at; a.svHC2 = c.train + c.R.oHC2[l] + at;
-          hipLaunchKernelGGL((k_update16<2, true, 64>), grid, dim3(512), UPDATE_SAVE_LDS, cs, a);
-        } else {
-          hipLaunchKernelGGL((k_update16<2, false, 64>), grid, dim3(512), UPDATE_LDS, cs, a);
         }
+        RETURN_IF(launch_node(UPDATE16, 2, c.train != nullptr, 64, false, dim3(node_items(P.N, P.B, 64)), cs, a));
       }
       CHECK_LAUNCH();
       if (multi && l + 1 < P.L) HIP_OK(hipEventRecord(W.step[l][t], cs));
@@ -1022,6 +1008,13 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
   if (multi)
     for (int l = 1; l < P.L; ++l) HIP_OK(hipStreamWaitEvent(c.s, W.done[l], 0));   // join
   return MATGCN_OK;
+}
+
+// the encoder: its chains fork onto library streams; a failure between fork and join joins them before returning
+int encoder_padded(const Ctx& c, const float* x0p, const float* h0User, float* finalsUser) {
+  const int rc = encoder_chains(c, x0p, h0User, finalsUser);
+  if (rc != MATGCN_OK) join_library_streams(c.s);
+  return rc;
 }
 
 int fuse_padded(const Ctx& c, const float* X, float* x0p, const int32_t* labelStart = nullptr,
@@ -1212,7 +1205,7 @@ int matgcn_set_train_precision(int mode) {
 
 int matgcn_set_stream_pool(int own) {
   for (int d = 0; d < MAX_DEVICES; ++d)
-    if (g_wfs[d].ready) return own ? (g_stream_pool ? MATGCN_OK : MATGCN_ERR_BAD_ARG) : (g_stream_pool ? MATGCN_ERR_BAD_ARG : MATGCN_OK);
+    if (g_dev[d].wf.ready) return own ? (g_stream_pool ? MATGCN_OK : MATGCN_ERR_BAD_ARG) : (g_stream_pool ? MATGCN_ERR_BAD_ARG : MATGCN_OK);
   g_stream_pool = own ? 1 : 0;
   return MATGCN_OK;
 }
@@ -1336,7 +1329,7 @@ static int prepare_impl(const matgcn_dims* dims, const matgcn_params* params, vo
     int iPrev1 = 0, iPrev2 = -1;
     for (int k = 2; k < dims->cheb_k; ++k) {
       const int iOut = (iPrev2 < 0) ? 1 : 3 - iPrev1 - iPrev2;
-      RETURN_IF(launch_mix(P, St + col0, buf[iPrev1], 64, P.NpC, P.NpC / 64, buf[iOut], (long)P.NpC, 0, 64, 1, P.Np,
+      RETURN_IF(launch_mix(P, false, St + col0, buf[iPrev1], 64, P.NpC, P.NpC / 64, buf[iOut], (long)P.NpC, 0, 64, 1, P.Np,
                            c.s));
       hipLaunchKernelGGL(k_cheb_combine, tgrid, dim3(256), 0, c.s, buf[iOut], iPrev2 < 0 ? nullptr : buf[iPrev2],
                          iPrev2 < 0 ? 1 : 0, P.N, P.NpC, St, P.Mp, (slot0 + k - 1) * P.Np, buf[iOut]);
@@ -1470,7 +1463,7 @@ static int forward_entry(const matgcn_dims* dims, const matgcn_params* params, c
   if (!params->weight_tsg || !params->end_conv_bias) return MATGCN_ERR_NULL;
   for (int h = 0; h < dims->n_heads; ++h) if (!params->weight_ts[h]) return MATGCN_ERR_NULL;
   RETURN_IF(check_layer_params(dims, params));
-  MixPrecisionScope mixScope(g_mix_precision);
+  c.prec = precision_of(g_mix_precision);
   return forward_once(c, X, nullptr, 0, nullptr, nullptr, h0, out);
 }
 
@@ -1503,7 +1496,7 @@ static int forward_series_entry(const matgcn_dims* dims, const matgcn_params* pa
   for (int h = 0; h < dims->n_heads; ++h) if (!params->weight_ts[h]) return MATGCN_ERR_NULL;
   RETURN_IF(check_layer_params(dims, params));
   RETURN_IF(check_series(dims, series, series_steps, label_start, rel_steps));
-  MixPrecisionScope mixScope(g_mix_precision);
+  c.prec = precision_of(g_mix_precision);
   return forward_once(c, nullptr, series, series_steps, label_start, rel_steps, h0, out);
 }
 
