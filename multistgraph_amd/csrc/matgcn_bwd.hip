@@ -18,17 +18,105 @@
 
 namespace {
 
+// Every instantiation of the backward's templated kernels that the schedule launches, once, as GATE16 / UPDATE16 / PX16 of
+// the forward: the launch sites look theirs up by its selectors.  A combination without an entry is an error - or, where
+// the schedule has a batched-GEMM form of the same product, that form - never another variant.
+template <class V, size_t n, class Match>
+const V* find_variant(const V (&table)[n], Match match) {
+  for (const V& v : table)
+    if (match(v)) return &v;
+  return nullptr;
+}
+// the chain kernels (512 threads, a workgroup per node and 64 rows): launches the entry, no entry is an error
+template <class V, size_t n, class Match, class Args>
+int launch_chain(const V (&table)[n], Match match, const dim3& grid, int lds, hipStream_t s, const Args& a) {
+  const V* v = find_variant(table, match);
+  if (!v) return MATGCN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(v->fn, grid, dim3(512), lds, s, a);
+  CHECK_LAUNCH();
+  return MATGCN_OK;
+}
+// the fused chain kernels take up to this many partial transposed mixes (one per dense stack slot); larger stacks take
+// round 3's kernel pair, k_chain_res_fused + k_chain_node (bwd_chain)
+constexpr int MAX_FUSED_PARTS = 4;
+// k_chain_res_node<CARRY, HPREV = true, PARTS, BF>: carry - forms the carry of step t+1, out of `parts` partial mixes; bf -
+// bf16 copy of the weights (training precision mode 2)
+struct ChainResVariant { bool carry; int parts; bool bf; void (*fn)(ChainResNodeArgs); };
+const ChainResVariant CHAIN_RES[] = {
+    {false, 0, false, k_chain_res_node<false, true, 0>}, {false, 0, true, k_chain_res_node<false, true, 0, true>},
+    {true, 0, false, k_chain_res_node<true, true, 0>},   {true, 0, true, k_chain_res_node<true, true, 0, true>},
+    {true, 1, false, k_chain_res_node<true, true, 1>},   {true, 1, true, k_chain_res_node<true, true, 1, true>},
+    {true, 2, false, k_chain_res_node<true, true, 2>},   {true, 2, true, k_chain_res_node<true, true, 2, true>},
+    {true, 3, false, k_chain_res_node<true, true, 3>},   {true, 3, true, k_chain_res_node<true, true, 3, true>},
+    {true, MAX_FUSED_PARTS, false, k_chain_res_node<true, true, MAX_FUSED_PARTS>},
+    {true, MAX_FUSED_PARTS, true, k_chain_res_node<true, true, MAX_FUSED_PARTS, true>},
+};
+// k_chain_gate_node<PARTS, BETA, BF>: `parts` partial mixes enter the gate algebra; beta - the block already holds the
+// x-column gradient of the layer above (mergeAbove)
+struct ChainGateVariant { int parts; bool beta, bf; void (*fn)(ChainNodeArgs); };
+const ChainGateVariant CHAIN_GATE[] = {
+    {0, false, false, k_chain_gate_node<0, false>}, {0, true, false, k_chain_gate_node<0, true>},
+    {0, false, true, k_chain_gate_node<0, false, true>}, {0, true, true, k_chain_gate_node<0, true, true>},
+    {1, false, false, k_chain_gate_node<1, false>}, {1, true, false, k_chain_gate_node<1, true>},
+    {1, false, true, k_chain_gate_node<1, false, true>}, {1, true, true, k_chain_gate_node<1, true, true>},
+    {2, false, false, k_chain_gate_node<2, false>}, {2, true, false, k_chain_gate_node<2, true>},
+    {2, false, true, k_chain_gate_node<2, false, true>}, {2, true, true, k_chain_gate_node<2, true, true>},
+    {3, false, false, k_chain_gate_node<3, false>}, {3, true, false, k_chain_gate_node<3, true>},
+    {3, false, true, k_chain_gate_node<3, false, true>}, {3, true, true, k_chain_gate_node<3, true, true>},
+    {MAX_FUSED_PARTS, false, false, k_chain_gate_node<MAX_FUSED_PARTS, false>},
+    {MAX_FUSED_PARTS, true, false, k_chain_gate_node<MAX_FUSED_PARTS, true>},
+    {MAX_FUSED_PARTS, false, true, k_chain_gate_node<MAX_FUSED_PARTS, false, true>},
+    {MAX_FUSED_PARTS, true, true, k_chain_gate_node<MAX_FUSED_PARTS, true, true>},
+};
+// k_chain_node<GATE, O, BF>: one AGCN's columns (round 3's pair: 128 behind the gate algebra, 64) or both (node_contract)
+struct ChainNodeVariant { bool gate; int O; bool bf; void (*fn)(ChainNodeArgs); };
+const ChainNodeVariant CHAIN_NODE[] = {
+    {true, 128, false, k_chain_node<true, 128>},   {false, 64, false, k_chain_node<false, 64>},
+    {false, 192, false, k_chain_node<false, 192>}, {false, 192, true, k_chain_node<false, 192, true>},
+};
+// k_chain_res_fused<64>, the other half of round 3's pair: opted into its dynamic LDS once per device (node_kernels_ready)
+constexpr int CHAIN_FUSED_LDS = 128 * CF_LD * (int)sizeof(float);
+int chain_fused_ready() {
+  bool& ready = dev_current().chainFusedLds;
+  if (!ready) RETURN_IF(lds_opt_in(reinterpret_cast<const void*>(k_chain_res_fused<64>), CHAIN_FUSED_LDS));
+  ready = true;
+  return MATGCN_OK;
+}
+// k_wgrad_node<O, S, MINW>, S * O threads (512 at <128, 4, 4>, 128 registers: two workgroups per CU); else batched GEMMs
+struct WgradNodeVariant { int O, S; void (*fn)(WgradNodeArgs); };
+const WgradNodeVariant WGRAD_NODE[] = {
+    {128, 4, k_wgrad_node<128, 4, 4>}, {128, 5, k_wgrad_node<128, 5, 2>}, {128, 2, k_wgrad_node<128, 2, 3>},
+    {64, 4, k_wgrad_node<64, 4, 3>},   {64, 5, k_wgrad_node<64, 5, 3>},   {64, 2, k_wgrad_node<64, 2, 3>},
+};
+// Layer 0's narrow input, by (C0, S): x-column and x-row weight gradients, on the matrix cores where the S * C0 (slot,
+// channel) pairs fit one 16-wide tile (mfma), else on the VALU (another launch geometry); other shapes: the generic GEMMs
+struct NarrowVariant {
+  int C0, S; bool mfma;
+  void (*xcolMfma)(const float*, const float*, const float*, const float*, float*, int, int, int, int, int);   // + tiles per wave
+  void (*xcol)(const float*, const float*, const float*, const float*, float*, int, int, int, int);
+  void (*wgrad)(const float*, const float*, long, const float*, const float*, float*, float*, int, int, int, int, int);
+};
+const NarrowVariant NARROW[] = {
+    {2, 4, true, k_xcol_narrow_mfma<2, 4>, nullptr, k_wgrad_narrow_mfma<2, 4>},
+    {2, 5, true, k_xcol_narrow_mfma<2, 5>, nullptr, k_wgrad_narrow_mfma<2, 5>},
+    {2, 2, true, k_xcol_narrow_mfma<2, 2>, nullptr, k_wgrad_narrow_mfma<2, 2>},
+    {2, 1, true, k_xcol_narrow_mfma<2, 1>, nullptr, k_wgrad_narrow_mfma<2, 1>},
+    {9, 4, false, nullptr, k_xcol_narrow<9, 4>, k_wgrad_narrow<9, 4>},
+};
+const NarrowVariant* narrow_variant(int C0, int S) { return find_variant(NARROW, [&](auto& e) { return e.C0 == C0 && e.S == S; }); }
+// the residual cell's nn.Linear over a narrow input, by C0: x columns and x-column blocks of the weight gradients
+struct ResNarrowVariant { int C0; decltype(&k_res_xcol_narrow<2>) xcol; decltype(&k_res_wgrad_narrow<2>) wgrad; };
+const ResNarrowVariant RES_NARROW[] = {
+    {2, k_res_xcol_narrow<2>, k_res_wgrad_narrow<2>}, {9, k_res_xcol_narrow<9>, k_res_wgrad_narrow<9>},
+};
+const ResNarrowVariant* res_narrow_variant(int C0) { return find_variant(RES_NARROW, [&](auto& e) { return e.C0 == C0; }); }
+
 GemmArgs gemm_args(const float* A, const float* B, float* C, int M, int N, int K) {
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.K2 = 1;
   g.nb2 = 1; g.alpha = 1.f; g.beta = 0.f; g.mode = 0; g.split = 1;
   return g;
-}
-
-template <int ROLE>
-void launch_bgemm(const dim3& grid, hipStream_t s, const GemmArgs& g) {
-  hipLaunchKernelGGL(k_bgemm<ROLE>, grid, dim3(256), 0, s, g);
 }
 
 // the fast path of k_bgemm_tn: A unit-stride along M, B unit-stride along N, whole 64 x 64 tiles, 16-byte friendly
@@ -39,37 +127,26 @@ bool tn_eligible(const GemmArgs& g) {
          (reinterpret_cast<size_t>(g.A) & 15) == 0 && (reinterpret_cast<size_t>(g.B) & 15) == 0;
 }
 
-template <int ROLE>
-void launch_bgemm_tn(const dim3& grid, hipStream_t s, const GemmArgs& g) {
-  hipLaunchKernelGGL(k_bgemm_tn<ROLE>, grid, dim3(256), 0, s, g);
-}
+// Every role has an instantiation of its own (the profiler summaries tell the call sites apart by symbol name); tn: the
+// role's k_bgemm_tn, for the roles whose call sites can be tn_eligible (BG_GENERIC: matgcn_debug_gemm, the test's way in)
+struct GemmRole { int role; void (*fn)(GemmArgs); void (*tn)(GemmArgs); };
+const GemmRole BGEMM[] = {
+    {BG_GENERIC, k_bgemm<BG_GENERIC>, k_bgemm_tn<BG_GENERIC>},   // first: what an unknown role runs as
+    {BG_CHAIN_DENSE, k_bgemm<BG_CHAIN_DENSE>, nullptr}, {BG_CHAIN_NODE, k_bgemm<BG_CHAIN_NODE>, nullptr},
+    {BG_CHAIN_MIX, k_bgemm<BG_CHAIN_MIX>, nullptr},     {BG_X_NODE, k_bgemm<BG_X_NODE>, nullptr},
+    {BG_X_MIX, k_bgemm<BG_X_MIX>, nullptr},             {BG_WGRAD, k_bgemm<BG_WGRAD>, k_bgemm_tn<BG_WGRAD>},
+    {BG_ADJ, k_bgemm<BG_ADJ>, nullptr},                 {BG_LINEAR, k_bgemm<BG_LINEAR>, k_bgemm_tn<BG_LINEAR>},
+    {BG_POOL, k_bgemm<BG_POOL>, nullptr},               {BG_HEAD, k_bgemm<BG_HEAD>, nullptr},
+};
 
 int gemm(const GemmArgs& g, int nb1, hipStream_t s, int role = BG_GENERIC) {
   if (g.M <= 0 || g.N <= 0 || g.K <= 0 || g.K2 <= 0 || nb1 <= 0) return MATGCN_OK;
   const long gx = (g.N + 63) / 64, gy = (g.M + 63) / 64, gz = (long)nb1 * g.nb2 * g.split;
   if (gy > 65535 || gz > 65535 || (long)g.K2 * ((g.K + BG_KT - 1) / BG_KT) >= (1L << 30)) return MATGCN_ERR_UNSUPPORTED;
+  const GemmRole* r = find_variant(BGEMM, [&](auto& e) { return e.role == role; });
+  if (!r) r = &BGEMM[0];   // a role without an entry only names a call site: it runs as BG_GENERIC
   const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)gz);
-  if (tn_eligible(g)) {
-    switch (role) {
-      case BG_WGRAD: launch_bgemm_tn<BG_WGRAD>(grid, s, g); return launch_ok();
-      case BG_LINEAR: launch_bgemm_tn<BG_LINEAR>(grid, s, g); return launch_ok();
-      case BG_GENERIC: launch_bgemm_tn<BG_GENERIC>(grid, s, g); return launch_ok();   // matgcn_debug_gemm: the test's way in
-      default: break;
-    }
-  }
-  switch (role) {
-    case BG_CHAIN_DENSE: launch_bgemm<BG_CHAIN_DENSE>(grid, s, g); break;
-    case BG_CHAIN_NODE: launch_bgemm<BG_CHAIN_NODE>(grid, s, g); break;
-    case BG_CHAIN_MIX: launch_bgemm<BG_CHAIN_MIX>(grid, s, g); break;
-    case BG_X_NODE: launch_bgemm<BG_X_NODE>(grid, s, g); break;
-    case BG_X_MIX: launch_bgemm<BG_X_MIX>(grid, s, g); break;
-    case BG_WGRAD: launch_bgemm<BG_WGRAD>(grid, s, g); break;
-    case BG_ADJ: launch_bgemm<BG_ADJ>(grid, s, g); break;
-    case BG_LINEAR: launch_bgemm<BG_LINEAR>(grid, s, g); break;
-    case BG_POOL: launch_bgemm<BG_POOL>(grid, s, g); break;
-    case BG_HEAD: launch_bgemm<BG_HEAD>(grid, s, g); break;
-    default: launch_bgemm<BG_GENERIC>(grid, s, g); break;
-  }
+  hipLaunchKernelGGL(r->tn && tn_eligible(g) ? r->tn : r->fn, grid, dim3(256), 0, s, g);
   return launch_ok();
 }
 
@@ -94,40 +171,41 @@ StackEntries stack_entries(const StackMap& map) {
   return e;
 }
 
+// The forward's graph-mix kernel on the plain support stack (reduction over (k, n)).  `a` arrives with what differs
+// between the callers: the column tiles of X and of the result, and how many.  parts > 1 cuts the reduction by support
+// slot - that many times the workgroups, each with a K loop of the forward's length; part k's result lands `partStride`
+// floats behind part k-1's, the consumers add them up.  wide: 32-row x 128-column tiles over pairs of column tiles
+// (k_mix_n32: 3 % row padding instead of 10 %, 4.9 workgroups per CU).  Training precision mode >= 1: bf16 operands.
+int launch_mix_plain(const Bwd& b, MixArgs a, bool wide, int parts = 1, long partStride = 0) {
+  const Plan& P = b.c.P;
+  a.St = b.tr + b.c.R.oStP; a.ldS = P.NpC; a.sK = 0;
+  a.Np = P.NpC; a.N = P.N; a.Ks = 1; a.nK = P.Ks * P.Np / 16;
+  a.nRowTiles = wide ? (P.N + 31) / 32 : P.NpC / 64;
+  if (parts > 1) {
+    a.parts = parts; a.nK = P.Np / 16;
+    a.aPartStride = (long)P.Np * P.NpC; a.xPartStride = (long)P.Np * H; a.outPartStride = partStride;
+  }
+  const dim3 grid((unsigned)(a.nRowTiles * (wide ? a.nColTiles / 2 : a.nColTiles)), (unsigned)a.parts);
+  void (*fn)(MixArgs) = wide ? k_mix_n32<false> : k_mix<2>;
+  if (b.c.prec.mix) fn = wide ? k_mix_n32<true> : k_mix_bf16<2>;
+  hipLaunchKernelGGL(fn, grid, dim3(256), 0, b.c.s, a);
+  return launch_ok();
+}
+
 // dst[rows][m][i] = sum_kk StP[kk][m] * src[rows][slot 1..][kk][i]: the transposed graph mix of the dense slots of a
-// [rows][S][Np][Cc] gradient.  With 64 feature columns this is the forward's graph-mix kernel run on the plain stack
-// (reduction over (k, n), one column tile per row); narrower inputs (layer 0) take the generic GEMM.
-// split: the reduction is cut by support slot - Ks times the workgroups, each with a K loop of the forward's length -
-// and slot k's partial result lands Ks-th part k of dst (parts `partStride` floats apart; the consumers add them up).
+// [rows][S][Np][Cc] gradient.  With 64 feature columns: launch_mix_plain, one column tile per row (an even number of
+// rows: in pairs; split: by support slot); narrower inputs (layer 0) take the generic GEMM.
 int mix_transposed(const Bwd& b, const float* src, int rows, int Cc, float* dst, bool split = false, long partStride = 0) {
   const Plan& P = b.c.P;
   if (P.Ks <= 0) return MATGCN_OK;
   const int S = b.c.R.S;
   if (Cc == H) {
     MixArgs a;
-    a.St = b.tr + b.c.R.oStP; a.ldS = P.NpC;
     a.X = src + (size_t)P.Np * H; a.xTileStride = (long)S * P.Np * H; a.ldX = H;
-    a.out = dst; a.sN = H; a.sK = 0; a.sT = (long)P.Np * H;
+    a.out = dst; a.sN = H; a.sT = (long)P.Np * H; a.nColTiles = rows;
     const long outFloats = (long)rows * P.Np * H;
     a.outFloats = outFloats < (1L << 29) ? outFloats : 0;
-    a.Np = P.NpC; a.N = P.N; a.Ks = 1; a.nK = P.Ks * P.Np / 16; a.nColTiles = rows;
-    a.nRowTiles = P.NpC / 64;
-    if (split && P.Ks > 1) {
-      a.parts = P.Ks; a.nK = P.Np / 16;
-      a.aPartStride = (long)P.Np * P.NpC; a.xPartStride = (long)P.Np * H; a.outPartStride = partStride;
-    }
-    if ((rows & 1) == 0) {   // 32-row x 128-column tiles: 3 % row padding instead of 10 %, 4.9 workgroups per CU (k_mix_n32)
-      a.nRowTiles = (P.N + 31) / 32;
-      const dim3 grid((unsigned)(a.nRowTiles * (rows / 2)), (unsigned)a.parts);
-      // training precision mode >= 1 (matgcn_set_train_precision): bf16 operands, fp32 accumulation
-      if (b.c.prec.mix) hipLaunchKernelGGL(k_mix_n32<true>, grid, dim3(256), 0, b.c.s, a);
-      else hipLaunchKernelGGL(k_mix_n32<false>, grid, dim3(256), 0, b.c.s, a);
-    } else if (b.c.prec.mix) {
-      hipLaunchKernelGGL(k_mix_bf16<2>, dim3((unsigned)(a.nRowTiles * rows), (unsigned)a.parts), dim3(256), 0, b.c.s, a);
-    } else {
-      hipLaunchKernelGGL(k_mix<2>, dim3((unsigned)(a.nRowTiles * rows), (unsigned)a.parts), dim3(256), 0, b.c.s, a);
-    }
-    return launch_ok();
+    return launch_mix_plain(b, a, (rows & 1) == 0, split ? P.Ks : 1, partStride);
   }
   GemmArgs g = gemm_args(b.c.prep + P.oSt, src + (size_t)P.Np * Cc, dst, P.N, Cc, P.Ks * P.Np);
   g.sAm = P.Mp; g.sAk = 1;
@@ -166,9 +244,7 @@ int node_contract(const Bwd& b, const float* dPreG, const float* WpG, const floa
   cn.N = P.N; cn.Np = P.Np; cn.S = b.c.R.S; cn.beta = beta;
   const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)P.N);
   // bf (training precision mode 2): WpG / WpU are the bf16 copies
-  if (bf) hipLaunchKernelGGL((k_chain_node<false, 192, true>), grid, dim3(512), 0, b.c.s, cn);
-  else hipLaunchKernelGGL((k_chain_node<false, 192>), grid, dim3(512), 0, b.c.s, cn);
-  return launch_ok();
+  return launch_chain(CHAIN_NODE, [&](auto& e) { return !e.gate && e.O == 192 && e.bf == bf; }, grid, 0, b.c.s, cn);
 }
 
 // where the forward left the graph-mixed rows G[s'][n][(k2, k)][i] of a range of steps: strides in floats
@@ -237,7 +313,8 @@ bool node_wgrad_fast(const Bwd& b, const float* U, const StepBlocks& sb, const f
                      float* dWp, int* rc, float* dBias = nullptr) {
   const Plan& P = b.c.P;
   const int S = b.c.R.S;
-  if (S != P.Ks + 1 || S > 5 || S == 3 || S < 2 || P.T > MAX_STEPS || (O != 128 && O != 64)) return false;
+  const WgradNodeVariant* v = find_variant(WGRAD_NODE, [&](auto& e) { return e.O == O && e.S == S; });
+  if (!v || S != P.Ks + 1 || P.T > MAX_STEPS) return false;
   WgradNodeArgs a;
   memset(&a, 0, sizeof(a));
   a.U = U; a.dPre = dPre; a.dW = dWp + (size_t)iOfs * O; a.dBias = dBias;
@@ -249,20 +326,7 @@ bool node_wgrad_fast(const Bwd& b, const float* U, const StepBlocks& sb, const f
   a.stepsPerPart = P.T >= 8 ? (P.T + parts - 1) / parts : P.T;
   const dim3 grid((unsigned)P.N, (unsigned)((P.T + a.stepsPerPart - 1) / a.stepsPerPart));
   const size_t lds = (size_t)2 * WG_KT * ((S * 64 + 16) + (O + 16)) * sizeof(float);
-  const dim3 block((unsigned)(S * O));
-#define WGN(O_, S_, W_) hipLaunchKernelGGL((k_wgrad_node<O_, S_, W_>), grid, block, lds, b.c.s, a)
-  if (O == 128) {
-    if (S == 4) WGN(128, 4, 4);        // 512 threads, 128 registers: two workgroups per compute unit
-    else if (S == 5) WGN(128, 5, 2);
-    else if (S == 2) WGN(128, 2, 3);
-    else return false;
-  } else {
-    if (S == 4) WGN(64, 4, 3);
-    else if (S == 5) WGN(64, 5, 3);
-    else if (S == 2) WGN(64, 2, 3);
-    else return false;
-  }
-#undef WGN
+  hipLaunchKernelGGL(v->fn, grid, dim3((unsigned)(S * O)), lds, b.c.s, a);
   *rc = launch_ok();
   return true;
 }
@@ -327,7 +391,6 @@ struct Pass {
   int chunk;                 // steps per x-column chunk of the layers above the first (see bwd_x_chunk)
   bool twoStreams, adp;
   int hT, tOff;              // fnn_off: the head sees the last step only (MultiATGCN.py:412)
-  int fusedLds;
   StackMap map;
   StackEntries ent;
 };
@@ -356,7 +419,7 @@ struct LayerBufs {
   [[maybe_unused]] const int S = R.S, T = P.T, B = P.B, Np = P.Np, N = P.N;                                         \
   [[maybe_unused]] const long slab = (long)B * Np * H; [[maybe_unused]] const int rowsTB = T * B;                   \
   [[maybe_unused]] const bool twoStreams = (q).twoStreams, adp = (q).adp;                                           \
-  [[maybe_unused]] const int hT = (q).hT, tOff = (q).tOff, fusedLds = (q).fusedLds;                                 \
+  [[maybe_unused]] const int hT = (q).hT, tOff = (q).tOff;                                                             \
   [[maybe_unused]] const StackMap& map = (q).map; [[maybe_unused]] const StackEntries& ent = (q).ent;               \
   [[maybe_unused]] float* dT = tr + R.oDT
 
@@ -690,47 +753,33 @@ int bwd_chain(Pass& pass, const LayerBufs& L) {
     memset(&cn, 0, sizeof(cn));
     cn.c = a; cn.I = I; cn.iOfs = C; cn.rows = B; cn.N = N; cn.Np = Np; cn.S = S;
     const dim3 ngrid((unsigned)((B + 63) / 64), (unsigned)N);
-    const bool fused = a.mixParts <= 4;
+    const bool fused = a.mixParts <= MAX_FUSED_PARTS;   // larger stacks: round 3's pair of kernels
     if (fused && !a.hprev) { a.hprev = tr + R.oZeroSlab; cn.c.hprev = a.hprev; }
     if (fused) {
       // blend + residual cell + graph-cell output algebra of step t, the carry of step t+1, and the update block's node
-      // contraction dA_u = dpu . WpU^T (h columns), one workgroup per node (round 4; more than four partial mixes - more
-      // than four dense stack slots - take round 3's pair of kernels below)
+      // contraction dA_u = dpu . WpU^T (h columns), one workgroup per node (round 4)
       ChainResNodeArgs f;
       f.c = a;
-      f.c.dcarry = (t == T - 1) ? nullptr : DH;
       f.carryA = (t == T - 1) ? nullptr : DAg + (at + slab) * S;
       f.carryMix = (t == T - 1 || P.Ks <= 0) ? nullptr : MixOut;
       f.ruf = tr + R.oRUf[l]; f.rgf = tr + R.oRGf[l];
       f.Wp = bfn ? L.WpU16 : WpU; f.dA = DAu + at * S; f.I = I; f.iOfs = C;
       const bool carry = t != T - 1;
-      const int parts = (carry && f.carryMix) ? a.mixParts : 0;
-#define CRN_LAUNCH(C_, P_)                                                                                 \
-  do {                                                                                                     \
-    if (bfn) hipLaunchKernelGGL((k_chain_res_node<C_, true, P_, true>), ngrid, dim3(512), CRN_LDS, s, f);  \
-    else hipLaunchKernelGGL((k_chain_res_node<C_, true, P_>), ngrid, dim3(512), CRN_LDS, s, f);            \
-  } while (0)
-      if (!carry) CRN_LAUNCH(false, 0);
-      else switch (parts) {
-        case 0: CRN_LAUNCH(true, 0); break; case 1: CRN_LAUNCH(true, 1); break; case 2: CRN_LAUNCH(true, 2); break;
-        case 3: CRN_LAUNCH(true, 3); break; default: CRN_LAUNCH(true, 4); break;
-      }
-#undef CRN_LAUNCH
-      CHECK_LAUNCH();
+      const int parts = f.carryMix ? a.mixParts : 0;   // (no carry: no carryMix)
+      RETURN_IF(launch_chain(CHAIN_RES, [&](auto& e) { return e.carry == carry && e.parts == parts && e.bf == bfn; },
+                             ngrid, CRN_LDS, s, f));
     } else {
       // blend + residual cell + graph-cell output algebra of step t, and the carry of step t+1, in one kernel
       FusedResArgs f;
       f.c = a;
-      f.c.dcarry = (t == T - 1) ? nullptr : DH;
       f.carryA = (t == T - 1) ? nullptr : DAg + (at + slab) * S;
       f.carryMix = (t == T - 1 || P.Ks <= 0) ? nullptr : MixOut;
       f.ruh = RU + C; f.rgh = RG + C; f.ldW = I;
-      hipLaunchKernelGGL(k_chain_res_fused<64>, dim3((unsigned)(((long)B * Np + 63) / 64)), dim3(256), fusedLds, s, f);
+      hipLaunchKernelGGL(k_chain_res_fused<64>, dim3((unsigned)(((long)B * Np + 63) / 64)), dim3(256), CHAIN_FUSED_LDS, s, f);
       CHECK_LAUNCH();
       // update block: dA_u = dpu . WpU^T (h columns), then its transposed mix
       cn.dPre = DPU + at; cn.Wp = WpU; cn.dA = DAu + at * S; cn.beta = 0.f;
-      hipLaunchKernelGGL((k_chain_node<false, 64>), ngrid, dim3(512), 0, s, cn);
-      CHECK_LAUNCH();
+      RETURN_IF(launch_chain(CHAIN_NODE, [](auto& e) { return !e.gate && e.O == 64 && !e.bf; }, ngrid, 0, s, cn));
     }
     RETURN_IF(mix_transposed(b, DAu + at * S, B, H, MixOut, true, slab));
     // gate block: the gate algebra (prologue) and dA_g = dpg . WpG^T in one kernel, then its transposed mix
@@ -740,22 +789,11 @@ int bwd_chain(Pass& pass, const LayerBufs& L) {
     if (fused) {
       const int parts = P.Ks > 0 ? a.mixParts : 0;
       if (bfn) cn.Wp = L.WpG16;
-#define CGN_LAUNCH(P_)                                                                                     \
-  do {                                                                                                     \
-    if (bfn && mergeAbove) hipLaunchKernelGGL((k_chain_gate_node<P_, true, true>), ngrid, dim3(512), 0, s, cn); \
-    else if (bfn) hipLaunchKernelGGL((k_chain_gate_node<P_, false, true>), ngrid, dim3(512), 0, s, cn);    \
-    else if (mergeAbove) hipLaunchKernelGGL((k_chain_gate_node<P_, true>), ngrid, dim3(512), 0, s, cn);    \
-    else hipLaunchKernelGGL((k_chain_gate_node<P_, false>), ngrid, dim3(512), 0, s, cn);                   \
-  } while (0)
-      switch (parts) {
-        case 0: CGN_LAUNCH(0); break; case 1: CGN_LAUNCH(1); break; case 2: CGN_LAUNCH(2); break;
-        case 3: CGN_LAUNCH(3); break; default: CGN_LAUNCH(4); break;
-      }
-#undef CGN_LAUNCH
+      RETURN_IF(launch_chain(CHAIN_GATE, [&](auto& e) { return e.parts == parts && e.beta == mergeAbove && e.bf == bfn; },
+                             ngrid, 0, s, cn));
     } else {
-      hipLaunchKernelGGL((k_chain_node<true, 128>), ngrid, dim3(512), 0, s, cn);
+      RETURN_IF(launch_chain(CHAIN_NODE, [](auto& e) { return e.gate && e.O == 128 && !e.bf; }, ngrid, 0, s, cn));
     }
-    CHECK_LAUNCH();
     RETURN_IF(mix_transposed(b, DAg + at * S, B, H, MixOut, true, slab));   // the carry itself is formed by the next step's kernel
     if (l > 0 && t % pass.chunk == 0) {   // a chunk of steps is through: its x columns start beside the rest of the chain
       const int t1 = t + pass.chunk < T ? t + pass.chunk : T;
@@ -791,24 +829,11 @@ int bwd_x_columns(Pass& pass, const LayerBufs& L) {
   if (narrow) {
     // node-major [s][n][rows][C]: the transposed mix is one GEMM with rows*C columns
     RETURN_IF(zero_async(DAx, (long)rowsTB * S * Np * C, s));
-    bool narrowDone = true;     // the same (C0, S) set as k_wgrad_narrow; any other shape takes the generic GEMM
-#define XN_LAUNCH(C0_, S_)                                                                                               \
-  hipLaunchKernelGGL((k_xcol_narrow<C0_, S_>), dim3((unsigned)((rowsTB + 255) / 256), (unsigned)N), dim3(256), 0, s, DPG, \
-                     DPU, WpG, WpU, DAx, rowsTB, N, Np, I)
-    const int xnTpw = 6;   // 16-row tiles per wave of the matrix-core kernel
-#define XNM_LAUNCH(C0_, S_)                                                                                              \
-  hipLaunchKernelGGL((k_xcol_narrow_mfma<C0_, S_>),                                                                      \
-                     dim3((unsigned)(((rowsTB + 15) / 16 + 4 * xnTpw - 1) / (4 * xnTpw)), (unsigned)N), dim3(256), 0, s,  \
-                     DPG, DPU, WpG, WpU, DAx, rowsTB, N, Np, I, xnTpw)
-    if (C == 2 && S == 4) XNM_LAUNCH(2, 4);
-    else if (C == 2 && S == 5) XNM_LAUNCH(2, 5);
-    else if (C == 2 && S == 2) XNM_LAUNCH(2, 2);
-    else if (C == 2 && S == 1) XNM_LAUNCH(2, 1);
-    else if (C == 9 && S == 4) XN_LAUNCH(9, 4);
-    else narrowDone = false;
-#undef XN_LAUNCH
-#undef XNM_LAUNCH
-    if (narrowDone) {
+    if (const NarrowVariant* v = narrow_variant(C, S)) {   // any other shape takes the generic GEMM
+      const int tpw = 6;   // 16-row tiles per wave of the matrix-core kernel (four waves); the VALU kernel: a row per thread
+      const dim3 grid((unsigned)(v->mfma ? ((rowsTB + 15) / 16 + 4 * tpw - 1) / (4 * tpw) : (rowsTB + 255) / 256), (unsigned)N);
+      if (v->mfma) hipLaunchKernelGGL(v->xcolMfma, grid, dim3(256), 0, s, DPG, DPU, WpG, WpU, DAx, rowsTB, N, Np, I, tpw);
+      else hipLaunchKernelGGL(v->xcol, grid, dim3(256), 0, s, DPG, DPU, WpG, WpU, DAx, rowsTB, N, Np, I);
       CHECK_LAUNCH();
     } else {
       RETURN_IF(node_gemm_transposed(b, DPG, 128, WpG, I, 0, C, rowsTB, DAx, 0.f, true));
@@ -820,15 +845,9 @@ int bwd_x_columns(Pass& pass, const LayerBufs& L) {
       // the graph-mix kernel on the plain stack, 64 of the rows*C columns per tile (as the forward folds x0): the generic
       // GEMM ran this 3 GFLOP product at 13 TFLOP/s - in the tail of the backward, where nothing hides it
       MixArgs a;
-      a.St = tr + R.oStP; a.ldS = P.NpC;
       a.X = DAx + (size_t)Np * cols; a.xTileStride = 64; a.ldX = (int)cols;
-      a.out = MixN; a.sN = cols; a.sK = 0; a.sT = 64;
-      a.outFloats = (long)N * cols;
-      a.Np = P.NpC; a.N = N; a.Ks = 1; a.nK = P.Ks * Np / 16; a.nColTiles = (int)(cols / 64);
-      a.nRowTiles = P.NpC / 64;
-      if (c.prec.mix) hipLaunchKernelGGL(k_mix_bf16<2>, dim3((unsigned)(a.nRowTiles * a.nColTiles), 1u), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL(k_mix<2>, dim3((unsigned)(a.nRowTiles * a.nColTiles), 1u), dim3(256), 0, s, a);
-      CHECK_LAUNCH();
+      a.out = MixN; a.sN = cols; a.sT = 64; a.nColTiles = (int)(cols / 64); a.outFloats = (long)N * cols;
+      RETURN_IF(launch_mix_plain(b, a, false));
     } else if (P.Ks > 0) {
       GemmArgs q = gemm_args(c.prep + P.oSt, DAx + (size_t)Np * cols, MixN, N, (int)cols, P.Ks * Np);
       q.sAm = P.Mp; q.sAk = 1; q.sBk = cols; q.sBn = 1; q.sCm = cols; q.sCn = 1;
@@ -861,10 +880,9 @@ int bwd_x_columns(Pass& pass, const LayerBufs& L) {
     const dim3 grid((unsigned)((rrows + 15) / 16 < 2048 ? (rrows + 15) / 16 : 2048));
     hipLaunchKernelGGL(k_res_narrow2, grid, dim3(256), 0, s, DPU2, DPG2, RU, RG, Xall, I, dXall, gu.weight, gg.weight, rrows);
     CHECK_LAUNCH();
-  } else if (narrow && (C == 2 || C == 9)) {   // residual cell x columns of a narrow input: one pass over the 192 gradients per row
+  } else if (const ResNarrowVariant* v = res_narrow_variant(C)) {   // of a narrow input: one pass over the 192 gradients per row
     const dim3 grid((unsigned)((rrows + 15) / 16 < 4096 ? (rrows + 15) / 16 : 4096));
-    if (C == 2) hipLaunchKernelGGL(k_res_xcol_narrow<2>, grid, dim3(256), 0, s, DPU2, DPG2, RU, RG, I, dXall, rrows);
-    else hipLaunchKernelGGL(k_res_xcol_narrow<9>, grid, dim3(256), 0, s, DPU2, DPG2, RU, RG, I, dXall, rrows);
+    hipLaunchKernelGGL(v->xcol, grid, dim3(256), 0, s, DPU2, DPG2, RU, RG, I, dXall, rrows);
     CHECK_LAUNCH();
   } else {  // residual cell x columns
     GemmArgs q = gemm_args(DPU2, RU, dXall, rowsTB * Np, C, H);
@@ -909,10 +927,9 @@ int bwd_layer_other_grads(Pass& pass, const LayerBufs& L, const Bwd& bx, const f
   bool biasG = false, biasU = false;   // the h-column GEMMs (64 input channels: fast kernel) take the bias sums along
   if (resNarrowFused) {
     // (done by k_res_narrow2 in bwd_x_columns)
-  } else if (narrow && (C == 2 || C == 9)) {   // both x-column blocks in one pass over the residual cell's gradients
+  } else if (const ResNarrowVariant* v = res_narrow_variant(C)) {   // both x-column blocks in one pass over the residual cell's gradients
     const dim3 grid((unsigned)((rows + 15) / 16 < 1024 ? (rows + 15) / 16 : 1024));
-    if (C == 2) hipLaunchKernelGGL(k_res_wgrad_narrow<2>, grid, dim3(256), 0, xs, DPU2, DPG2, Xall, I, gu.weight, gg.weight, rows);
-    else hipLaunchKernelGGL(k_res_wgrad_narrow<9>, grid, dim3(256), 0, xs, DPU2, DPG2, Xall, I, gu.weight, gg.weight, rows);
+    hipLaunchKernelGGL(v->wgrad, grid, dim3(256), 0, xs, DPU2, DPG2, Xall, I, gu.weight, gg.weight, rows);
     CHECK_LAUNCH();
   } else {
     RETURN_IF(linear_weight_grad(bx, DPG2, 128, Xall, C, rows, I, 0, gg.weight));
@@ -972,33 +989,19 @@ int bwd_layer_weights(Pass& pass, const LayerBufs& L, bool tailOnMain) {
   // node-adaptive weight gradients (plain folded layout) and biases; the graph-mixed rows are the forward's
   float* dWpG = tr + R.oDWp[l][0];
   float* dWpU = tr + R.oDWp[l][1];
-  // x rows of layer 0 with a dedicated narrow kernel (see below): returns false when the shape has none
   const long ldx = rup((long)rowsTB * P.C0, 64);
-  auto narrow_wgrad = [&](hipStream_t on) -> bool {
-#define WN_LAUNCH(C0_, S_)                                                                                               \
-  hipLaunchKernelGGL((k_wgrad_narrow<C0_, S_>), dim3((unsigned)N, WN_PARTS), dim3(192 * WN_GROUPS), 0, on, Xall,          \
-                     c.ws + P.oMX0, ldx, DPG, DPU, dWpG, dWpU, T, B, N, Np, I)
-#define WNM_LAUNCH(C0_, S_)                                                                                              \
-  hipLaunchKernelGGL((k_wgrad_narrow_mfma<C0_, S_>), dim3((unsigned)N, WNM_PARTS), dim3(256), 0, on, Xall, c.ws + P.oMX0,  \
-                     ldx, DPG, DPU, dWpG, dWpU, T, B, N, Np, I)
-    if (P.C0 == 2 && S == 4) WNM_LAUNCH(2, 4);
-    else if (P.C0 == 2 && S == 5) WNM_LAUNCH(2, 5);
-    else if (P.C0 == 2 && S == 2) WNM_LAUNCH(2, 2);
-    else if (P.C0 == 2 && S == 1) WNM_LAUNCH(2, 1);
-    else if (P.C0 == 9 && S == 4) WN_LAUNCH(9, 4);
-    else return false;
-#undef WN_LAUNCH
-#undef WNM_LAUNCH
-    return true;
+  const NarrowVariant* nv = l == 0 ? narrow_variant(P.C0, S) : nullptr;   // x rows of layer 0: a dedicated kernel (see below)
+  auto narrow_wgrad = [&](hipStream_t on) {
+    const dim3 grid((unsigned)N, nv->mfma ? WNM_PARTS : WN_PARTS), block(nv->mfma ? 256 : 192 * WN_GROUPS);
+    hipLaunchKernelGGL(nv->wgrad, grid, block, 0, on, Xall, c.ws + P.oMX0, ldx, DPG, DPU, dWpG, dWpU, T, B, N, Np, I);
   };
-  const bool narrowShape = l == 0 && ((P.C0 == 2 && (S == 4 || S == 5 || S == 2 || S == 1)) || (P.C0 == 9 && S == 4));
   bool narrowOnMain = false;
   if (twoStreams && tailOnMain) {   // the main stream takes the other gradients once these operands exist
     HIP_OK(hipEventRecord(g_wf.xdone[0][l], ws));
     HIP_OK(hipStreamWaitEvent(s, g_wf.xdone[0][l], 0));
     // (behind that event the accumulators are cleared too.)  The narrow x-row gradients go FIRST on the main stream: the
     // weight-gradient stream is the longer of the two in the tail, and its pools need them last
-    if (narrowShape) {
+    if (nv) {
       narrow_wgrad(s);
       CHECK_LAUNCH();
       HIP_OK(hipEventRecord(g_wf.bfork, s));      // (bfork: recorded once at the start of the pass, free again by now)
@@ -1058,7 +1061,8 @@ int bwd_layer_weights(Pass& pass, const LayerBufs& L, bool tailOnMain) {
     // (multi-graph: identity + 3 or 4 dense slots, single graph: + 1) have a dedicated kernel (k_wgrad_narrow)
     if (narrowOnMain) {
       HIP_OK(hipStreamWaitEvent(ws, g_wf.bfork, 0));   // launched on the main stream above: the pools below read them
-    } else if (narrow_wgrad(ws)) {
+    } else if (nv) {
+      narrow_wgrad(ws);
       CHECK_LAUNCH();
     } else {
       MixedRows mx = {c.ws + P.oMX0, ldx, (long)Np * ldx, P.C0, (long)T * P.C0, T, B};
@@ -1283,11 +1287,7 @@ int backward_impl(Bwd& b, const float* dOut) {
   // the weight gradients of a layer (big GEMMs) run on a library stream while the caller's stream already walks the
   // chain of the layer below (small dependent launches); matgcn_set_wavefront(0) keeps everything on one stream
   RETURN_IF(wavefront_ready());
-  q.fusedLds = 128 * CF_LD * (int)sizeof(float);
-  if (DeviceState& dev = dev_current(); !dev.chainFusedLds) {
-    RETURN_IF(lds_opt_in(reinterpret_cast<const void*>(k_chain_res_fused<64>), q.fusedLds));
-    dev.chainFusedLds = true;
-  }
+  RETURN_IF(chain_fused_ready());
   q.twoStreams = g_wavefront_mode != 0 && P.L > 1 && !P.gcnOff;
   q.ws = q.twoStreams ? g_wf.chain[1] : q.s;
   q.bw = b;

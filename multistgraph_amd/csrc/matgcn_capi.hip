@@ -368,7 +368,7 @@ struct DeviceState {
   PrepEvents prep;
   int nodeLds = 0;           // node_kernels_ready: dynamic LDS bytes the node kernels are opted into (function
                              // attributes are per device)
-  bool chainFusedLds = false;   // backward_impl: k_chain_res_fused<64> is opted into its dynamic LDS
+  bool chainFusedLds = false;   // chain_fused_ready: k_chain_res_fused<64> is opted into its dynamic LDS
 };
 DeviceState g_dev[MAX_DEVICES];
 inline int current_device() {

@@ -772,7 +772,7 @@ __global__ __launch_bounds__(256) void k_mix(MixArgs a) {
 // workgroups (2.5 per CU, five waves per CU on average as before, but the longest CU holds 3 halves instead of 2 wholes).
 // Same pipeline as k_mix (K-step 16 through LDS, two K-tiles ahead in registers, rotated rows); a wave owns 32 rows x 16
 // columns = 2 x 1 accumulators, the B tile uses columns 0..31 of its 64-wide LDS rows (both halves of the workgroup request
-// it - duplicate stores of equal values).  Launched for at most 32 column tiles (B <= 32).
+// it - duplicate stores of equal values).  Launched for at most 16 column tiles (B <= 16: launch_mix).
 template <int ROLE>
 __global__ __launch_bounds__(256) void k_mix_c32(MixArgs a) {
   __shared__ __attribute__((aligned(16))) float As[2][16 * 64];
