@@ -636,27 +636,36 @@ constexpr int UPDATE_SAVE_LDS = 5 * 64 * 64 * (int)sizeof(float);   // training:
 // Every instantiation of the node kernels the library launches, once: node_kernels_ready opts each into its dynamic LDS
 // and the launch sites look theirs up here (launch_node; hoist_x for k_px16).  Selectors: mode - k_update16's MODE (0 graph
 // cell alone, 1 + residual cell and blend, 2 residual cell alone; k_gate16 has none: 0), save - training keeps z, r, hc,
-// rows - of a (node, row block) work item, bf - bf16 copies of the weight streams.
-struct NodeVariant { int mode; bool save; int rows; bool bf; void (*fn)(Node16Args); int lds; };
+// rows - of a (node, row block) work item, bf - bf16 copies of the weight streams, zero - the step from the all-zero
+// initial state (step 0 of an inference forward without h0: encoder_chains).
+struct NodeVariant { int mode; bool save; int rows; bool bf; bool zero; void (*fn)(Node16Args); int lds; };
 const NodeVariant GATE16[] = {
-    {0, false, 64, false, k_gate16<false, 64>, GATE_LDS},
-    {0, true, 64, false, k_gate16<true, 64>, GATE_LDS},
-    {0, false, 64, true, k_gate16<false, 64, true>, GATE_LDS},
-    {0, true, 64, true, k_gate16<true, 64, true>, GATE_LDS},
+    {0, false, 64, false, false, k_gate16<false, 64>, GATE_LDS},
+    {0, true, 64, false, false, k_gate16<true, 64>, GATE_LDS},
+    {0, false, 64, true, false, k_gate16<false, 64, true>, GATE_LDS},
+    {0, true, 64, true, false, k_gate16<true, 64, true>, GATE_LDS},
     // 32-row work items (batches of at most 32 rows, graphs of at most 256 nodes: cell_phase)
-    {0, false, 32, false, k_gate16<false, 32>, GATE_LDS / 2},
-    {0, true, 32, false, k_gate16<true, 32>, GATE_LDS / 2},
+    {0, false, 32, false, false, k_gate16<false, 32>, GATE_LDS / 2},
+    {0, true, 32, false, false, k_gate16<true, 32>, GATE_LDS / 2},
+    // zero initial state (inference only): no state rows, no mixed slots, no LDS
+    {0, false, 64, false, true, k_gate16<false, 64, false, true>, 0},
+    {0, false, 64, true, true, k_gate16<false, 64, true, true>, 0},
+    {0, false, 32, false, true, k_gate16<false, 32, false, true>, 0},
 };
 const NodeVariant UPDATE16[] = {
-    {0, false, 64, false, k_update16<0, false, 64>, UPDATE_LDS},
-    {1, false, 64, false, k_update16<1, false, 64>, UPDATE_LDS},
-    {1, true, 64, false, k_update16<1, true, 64>, UPDATE_SAVE_LDS},
-    {1, false, 64, true, k_update16<1, false, 64, true>, UPDATE_LDS},
-    {1, true, 64, true, k_update16<1, true, 64, true>, UPDATE_SAVE_LDS},
-    {1, false, 32, false, k_update16<1, false, 32>, UPDATE_LDS / 2},
-    {1, true, 32, false, k_update16<1, true, 32>, UPDATE_SAVE_LDS / 2},
-    {2, false, 64, false, k_update16<2, false, 64>, UPDATE_LDS},
-    {2, true, 64, false, k_update16<2, true, 64>, UPDATE_SAVE_LDS},
+    {0, false, 64, false, false, k_update16<0, false, 64>, UPDATE_LDS},
+    {1, false, 64, false, false, k_update16<1, false, 64>, UPDATE_LDS},
+    {1, true, 64, false, false, k_update16<1, true, 64>, UPDATE_SAVE_LDS},
+    {1, false, 64, true, false, k_update16<1, false, 64, true>, UPDATE_LDS},
+    {1, true, 64, true, false, k_update16<1, true, 64, true>, UPDATE_SAVE_LDS},
+    {1, false, 32, false, false, k_update16<1, false, 32>, UPDATE_LDS / 2},
+    {1, true, 32, false, false, k_update16<1, true, 32>, UPDATE_SAVE_LDS / 2},
+    {2, false, 64, false, false, k_update16<2, false, 64>, UPDATE_LDS},
+    {2, true, 64, false, false, k_update16<2, true, 64>, UPDATE_SAVE_LDS},
+    // zero initial state (inference only): no K loop of the update GEMM; the residual cell's tiles keep their LDS
+    {1, false, 64, false, true, k_update16<1, false, 64, false, true>, UPDATE_LDS},
+    {1, false, 64, true, true, k_update16<1, false, 64, true, true>, UPDATE_LDS},
+    {1, false, 32, false, true, k_update16<1, false, 32, false, true>, UPDATE_LDS / 2},
 };
 struct PxVariant { int nrt; bool bf; void (*fn)(Px16Args); };   // nrt: row tiles that hold batch rows; LDS: the plan's nodeLds
 const PxVariant PX16[] = {
@@ -665,10 +674,10 @@ const PxVariant PX16[] = {
 };
 // launches the table's entry for the selectors; a combination without an entry is an error, never another variant
 template <size_t n>
-int launch_node(const NodeVariant (&table)[n], int mode, bool save, int rows, bool bf, const dim3& grid, hipStream_t s,
-                const Node16Args& a) {
+int launch_node(const NodeVariant (&table)[n], int mode, bool save, int rows, bool bf, bool zero, const dim3& grid,
+                hipStream_t s, const Node16Args& a) {
   for (const NodeVariant& v : table)
-    if (v.mode == mode && v.save == save && v.rows == rows && v.bf == bf) {
+    if (v.mode == mode && v.save == save && v.rows == rows && v.bf == bf && v.zero == zero) {
       hipLaunchKernelGGL(v.fn, grid, dim3(512), v.lds, s, a);
       return launch_ok();
     }
@@ -776,7 +785,10 @@ void fill_res_args(const Ctx& c, int l, const float* xt, long xRowStride, const 
 
 
 // phase 0: mix(h) -> G;  1: gate;  2: mix(z*h) -> G;  3: update [+ residual cell + blend when `res` is set]
-int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Args* res, hipStream_t s) {
+// zeroState (phases 1 and 3): the state of this step is the all-zero initial state and phases 0 and 2 were not launched
+// (encoder_chains) - the zero-state instantiations, which read neither the state, nor G, nor the recurrent weight groups
+int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Args* res, hipStream_t s,
+               bool zeroState = false) {
   const Plan& P = c.P;
   const float* St = c.prep + P.oSt;
   float* Hx = c.ws + P.oHx[l];
@@ -817,7 +829,7 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
   if (phase == 1) {
     a.s = Hx; a.w = bf ? c.ws + P.oW16g[l] : c.prep + P.oWg[l]; a.zh = ZHx; a.r = R; a.raw = raw;
     ProfScope prof(MATGCN_PROF_GATE, s);
-    return launch_node(GATE16, 0, save, rows32 ? 32 : 64, bf, grid, s, a);
+    return launch_node(GATE16, 0, save, rows32 ? 32 : 64, bf, zeroState, grid, s, a);
   }
   a.s = ZHx; a.w = bf ? c.ws + P.oW16u[l] : c.prep + P.oWu[l]; a.r = R; a.h = Hx; a.hout = Hx;
   ProfScope prof(MATGCN_PROF_UPDATE, s);
@@ -831,7 +843,7 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
       a.seqDrop = c.train + c.R.oSeqDrop + (a.seq - (c.ws + P.oSeq[l]));
     }
   }
-  return launch_node(UPDATE16, res ? 1 : 0, save, rows32 ? 32 : 64, bf, grid, s, a);
+  return launch_node(UPDATE16, res ? 1 : 0, save, rows32 ? 32 : 64, bf, zeroState, grid, s, a);
 }
 
 // One recurrent step of layer l at step t on the layer's state Hx_l:
@@ -854,7 +866,7 @@ int res_step(const Ctx& c, int l, const float* xt, long xRowStride) {
   a.rows = P.B; a.N = P.N; a.Np = P.Np; a.Ks = P.Ks;
   fill_res_args(c, l, xt, xRowStride, nullptr, nullptr, &a);
   ProfScope prof(MATGCN_PROF_RES, c.s);
-  return launch_node(UPDATE16, 2, false, 64, false, dim3(node_items(P.N, P.B, 64)), c.s, a);
+  return launch_node(UPDATE16, 2, false, 64, false, false, dim3(node_items(P.N, P.B, 64)), c.s, a);
 }
 
 int zero_async(float* p, long floats, hipStream_t s) {
@@ -870,6 +882,11 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
   Wavefront& W = g_wf;
   const bool multi = P.L > 1 && g_wavefront_mode != 0;
   const bool lazyPrep = prep_current().pending;
+  // Without h0 every layer's step 0 starts from the all-zero state: mix(h) and mix(z*h) of that step are products with a
+  // zero matrix and the recurrent K loops of its gate and update run over zeros.  The inference forwards skip both mixes
+  // and launch the zero-state instantiations of the node kernels.  An explicit h0 (all-zero or not) takes the general
+  // path; so does training, whose backward reads the per-step mixed rows and z / r / hc that the general step 0 saves.
+  const bool zeroStart = !h0User && !c.train && !P.gcnOff;
   // one stream, the bf16 copies (they read every stream) and the dense-GRU ablation take everything up front
   if (lazyPrep && (!multi || c.prec.node || P.gcnOff)) RETURN_IF(prep_wait(c.s, 3));
   if (c.prec.node && !P.gcnOff) {
@@ -948,7 +965,7 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
           const size_t at = (size_t)t * P.B * P.Np * H;
           a.svZ2 = c.train + c.R.oZ2[l] + at; a.svR2 = c.train + c.R.oR2[l] + at; a.svHC2 = c.train + c.R.oHC2[l] + at;
         }
-        RETURN_IF(launch_node(UPDATE16, 2, c.train != nullptr, 64, false, dim3(node_items(P.N, P.B, 64)), cs, a));
+        RETURN_IF(launch_node(UPDATE16, 2, c.train != nullptr, 64, false, false, dim3(node_items(P.N, P.B, 64)), cs, a));
       }
       CHECK_LAUNCH();
       if (multi && l + 1 < P.L) HIP_OK(hipEventRecord(W.step[l][t], cs));
@@ -981,14 +998,15 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
     else
       fill_res_args(c, l, below + t * stepRows, (long)P.Np * H, c.prm->weights_gru + (size_t)l * P.T + t,
                     seq + t * stepRows, &res);
-    RETURN_IF(cell_phase(c, l, t, 0, nullptr, &res, cs));
+    const bool zs = zeroStart && t == 0;   // (nothing is shared through shared_mix_slot at t = 0: no reader misses phase 0)
+    if (!zs) RETURN_IF(cell_phase(c, l, t, 0, nullptr, &res, cs));
     if (multi && l + 1 < P.L) HIP_OK(hipEventRecord(W.mixed[l][t], cs));
     // layer 0's weight streams are first read here: head fusion, the fold of x0 and the first mix ran beside their
     // preparation (lazy prepare)
     if (lazyPrep && multi && l == 0 && t == 0) RETURN_IF(prep_wait(cs, 1));
-    RETURN_IF(cell_phase(c, l, t, 1, nullptr, &res, cs));
-    RETURN_IF(cell_phase(c, l, t, 2, nullptr, &res, cs));
-    RETURN_IF(cell_phase(c, l, t, 3, nullptr, &res, cs));
+    RETURN_IF(cell_phase(c, l, t, 1, nullptr, &res, cs, zs));
+    if (!zs) RETURN_IF(cell_phase(c, l, t, 2, nullptr, &res, cs));
+    RETURN_IF(cell_phase(c, l, t, 3, nullptr, &res, cs, zs));
     if (multi && l + 1 < P.L) HIP_OK(hipEventRecord(W.step[l][t], cs));
     return MATGCN_OK;
   };

@@ -344,8 +344,15 @@ inline unsigned node_items(int N, int rows, int blockRows) {
 
 // ---- gate AGCN + sigmoid + z*h (MultiATGCN.py:122-125) -----------------------------------------------------
 // wave w = column tile w of 8 (0..3: z, 4..7: r), all ROWS/16 row tiles.  LDS 3 chunks of ROWS x 64 floats: Hs | Gb[2]
-template <bool SAVE, int ROWS, bool BF = false>
+//
+// ZERO: the step whose state is the all-zero initial state (step 0 of an inference forward without h0).  The state rows, the
+// mixed slots and the recurrent weight groups are not read: every fma(0, w, acc) they would feed leaves acc as it is (for
+// finite weights), so the accumulators take the x part and the bias alone, in the order of the general instantiation.
+// Only r is produced: z*h = 0 is what the forward's memset left in ZHx, and inference never reads z again - the four z
+// waves leave at once.  No LDS, no barrier.
+template <bool SAVE, int ROWS, bool BF = false, bool ZERO = false>
 __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_gate16(Node16Args a) {
+  static_assert(!ZERO || !SAVE, "training keeps z of every step: it runs the general instantiation");
   typedef typename NodeOp<BF>::T Op;
   constexpr int NRT = ROWS / 16, CH = ROWS * 64;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -362,8 +369,8 @@ __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_gate16(Node16Args a) {
   f32x4 acc[NRT];
   float4 pxv[NRT];               // hoisted pre-activation (x rows + bias) in fragment order, added in the epilogue
   float hz[BF ? NRT : 1][4];     // BF: the fp32 state values of z*h (the LDS copy is rounded to bf16), requested late
-  node_k_loop<ROWS, NRT, BF>(a, n, rowBase, Hs, Gb, 0, j, kq, wp, gStride, acc, [&]() {
-    if constexpr (BF) {
+  auto late = [&]() {
+    if constexpr (BF && !ZERO) {
       if (w < 4) {
 #pragma unroll
         for (int rt = 0; rt < NRT; ++rt)
@@ -381,7 +388,15 @@ __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_gate16(Node16Args a) {
       for (int rt = 0; rt < NRT; ++rt) pxv[rt] = make_float4(0.f, 0.f, 0.f, 0.f);
       x_groups<NRT, BF>(a, n, rowBase, 0, wp + (size_t)nG * gStride, gStride, j, kq, acc);
     }
-  });
+  };
+  if constexpr (ZERO) {
+    if (w < 4) return;
+#pragma unroll
+    for (int q = 0; q < NRT; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    late();
+  } else {
+    node_k_loop<ROWS, NRT, BF>(a, n, rowBase, Hs, Gb, 0, j, kq, wp, gStride, acc, late);
+  }
 #pragma unroll
   for (int rt = 0; rt < NRT; ++rt) {
     acc[rt][0] += pxv[rt].x; acc[rt][1] += pxv[rt].y; acc[rt][2] += pxv[rt].z; acc[rt][3] += pxv[rt].w;
@@ -394,12 +409,12 @@ __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_gate16(Node16Args a) {
   // index - one exposed LDS round trip per element; the wave index is now provably uniform, the 16 sigmoids of a lane
   // are independent, and the LDS sees 16 scalar writes and 2 wide reads per thread.  The training instantiation keeps
   // an r tile too and saves z and r as float4 rows instead of 64-byte pieces.)
-  __syncthreads();
+  if constexpr (!ZERO) __syncthreads();
   float* Zt = Gb;                // z tile (BF: z*h, the LDS state copy is bf16 there)
   float* Rt = Gb + CH;           // SAVE: r tile
   float* Zs = BF ? Hs : Zt;      // SAVE: z tile (BF: in the state chunk, dead after the K loop - z*h took h from memory)
   const int o = 16 * w + j;
-  if (a.raw) {                   // unit entry point: pre-activation dump
+  if (!ZERO && a.raw) {          // unit entry point: pre-activation dump
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
@@ -412,7 +427,7 @@ __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_gate16(Node16Args a) {
   for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[rt][e] = sigmoid16(acc[rt][e]);
-  if (w < 4) {
+  if (!ZERO && w < 4) {
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
@@ -437,6 +452,7 @@ __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_gate16(Node16Args a) {
         for (int e = 0; e < 4; ++e) Rt[swz(rt * 16 + 4 * kq + e, o - 64, 16)] = acc[rt][e];
     }
   }
+  if constexpr (ZERO) return;    // r is all this step produces
   __syncthreads();
 #pragma unroll
   for (int it = 0; it < ROWS / 32; ++it) {          // ROWS rows x 16 slots float4 over 512 threads
@@ -606,8 +622,15 @@ __global__ __launch_bounds__(512, 4) void k_px16(Px16Args p) {
 // two waves of a column tile request the same weight fragments: the second request is an L1 / L2 hit, HBM sees each
 // byte once).  The residual cell then runs two small GEMMs on tiles that never leave LDS.
 // LDS 4 chunks of ROWS x 64 floats: Hs | Gb[2] | X
-template <int MODE, bool SAVE, int ROWS, bool BF = false>
+//
+// ZERO (MODE 1, inference): the step whose state is the all-zero initial state, after k_gate16<.., ZERO>.  z*h and its
+// mixed slots are zero, so the update GEMM has no K loop: the candidate is tanh(x part + bias), and with h = 0 the blend
+// r*h + (1 - r)*hc is (1 - r)*hc.  Both agree in value with the general instantiation for finite weights (every skipped
+// fma(0, w, acc) leaves acc as it is, r*0 is a zero); the previous state is not read.  The residual cell runs on
+// [x_t | h'] of the NEW state h', as in every step: nothing of it is skipped.
+template <int MODE, bool SAVE, int ROWS, bool BF = false, bool ZERO = false>
 __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_update16(Node16Args a) {
+  static_assert(!ZERO || (MODE == 1 && !SAVE), "the zero-state step exists for the inference forward's fused update only");
   typedef typename NodeOp<BF>::T Op;
   constexpr int NRT = ROWS / 16, NR2 = ROWS / 32, NS = ROWS / 32, CH = ROWS * 64;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -660,7 +683,7 @@ __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_update16(Node16Args a) 
     // the previous state row-major
     float4 pxv[NR2], rv[NR2];
     float hv[NR2][4];
-    node_k_loop<ROWS, NR2, BF>(a, n, rowBase, Hs, Gb, NR2 * rh, j, kq, wp, gStride, acc, [&]() {
+    auto late = [&]() {
       if (a.px) {
         const float4* pf = reinterpret_cast<const float4*>(a.px) +
                            ((((size_t)n * RB + rb) * 12 + 8 + ct) * 4 + rtb + NR2 * rh) * 64 + lane;
@@ -674,20 +697,30 @@ __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_update16(Node16Args a) 
       const float4* rf = reinterpret_cast<const float4*>(a.r) + ((((size_t)n * RB + rb) * 4 + ct) * 4 + rtb + NR2 * rh) * 64 + lane;
 #pragma unroll
       for (int q = 0; q < NR2; ++q) rv[q] = rf[q * 64];
+      if constexpr (!ZERO) {
 #pragma unroll
-      for (int q = 0; q < NR2; ++q)
+        for (int q = 0; q < NR2; ++q)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int b = min(rowBase + (NR2 * rh + q) * 16 + 4 * kq + e, a.rows - 1);
-          hv[q][e] = a.h[((size_t)b * a.Np + n) * 64 + o4];
-        }
+          for (int e = 0; e < 4; ++e) {
+            const int b = min(rowBase + (NR2 * rh + q) * 16 + 4 * kq + e, a.rows - 1);
+            hv[q][e] = a.h[((size_t)b * a.Np + n) * 64 + o4];
+          }
+      }
       if (MODE == 1) request_xt();
-    });
+    };
+    if constexpr (ZERO) {
+#pragma unroll
+      for (int q = 0; q < NR2; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+      late();
+    } else {
+      node_k_loop<ROWS, NR2, BF>(a, n, rowBase, Hs, Gb, NR2 * rh, j, kq, wp, gStride, acc, late);
+    }
 #pragma unroll
     for (int q = 0; q < NR2; ++q) {
       acc[q][0] += pxv[q].x; acc[q][1] += pxv[q].y; acc[q][2] += pxv[q].z; acc[q][3] += pxv[q].w;
     }
-    __syncthreads();   // every wave is out of the K loop: Hs (z*h) may be overwritten by h'
+    // every wave is out of the K loop: Hs (z*h) may be overwritten by h'   (ZERO: nothing has used the LDS yet)
+    if constexpr (!ZERO) __syncthreads();
 #pragma unroll
     for (int q = 0; q < NR2; ++q)
 #pragma unroll
@@ -695,7 +728,9 @@ __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_update16(Node16Args a) 
         const int lb = (NR2 * rh + q) * 16 + 4 * kq + e, b = rowBase + lb;
         const float hc = tanh16(acc[q][e]);
         const float rr = e == 0 ? rv[q].x : e == 1 ? rv[q].y : e == 2 ? rv[q].z : rv[q].w;
-        float hn = rr * hv[q][e] + (1.0f - rr) * hc;   // (MultiATGCN.py:127: r blends, z gated the candidate)
+        float hn;                                      // (MultiATGCN.py:127: r blends, z gated the candidate)
+        if constexpr (ZERO) hn = (1.0f - rr) * hc;
+        else hn = rr * hv[q][e] + (1.0f - rr) * hc;
         if constexpr (SAVE) SV[swz(lb, o4, 16)] = hc;   // saved as float4 rows behind the next barrier
         if (b >= a.rows) hn = 0.f;
         if (MODE == 0) { if (b < a.rows) a.hout[((size_t)b * a.Np + n) * 64 + o4] = hn; }
