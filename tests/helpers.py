@@ -69,6 +69,66 @@ class Case:
                 abs(ps - float(self.gold["param_checksum"])) <= 1e-9 * max(1.0, abs(ps)))
 
 
+with open(os.path.join(GOLDEN_DIR, "edge_index.json")) as fh:
+    EDGE_INDEX = json.load(fh)     # shape-edge cases (make_edge_golden.py): an index of their own, not part of FULL
+EDGE = sorted(EDGE_INDEX)
+EDGE_GRAD = sorted(k for k in EDGE if EDGE_INDEX[k]["grad"])
+
+
+class EdgeCase:
+    """One shape-edge case, rebuilt the way tests/golden/make_edge_golden.py built it: synthetic data feature, the host
+    graph prep's static supports, closed-form parameters, synthetic inputs.  gold = edge_<case>.npz (float64 prediction
+    of the oracle), grad_gold = edge_grad_<case>.npz (its float64 autograd) for the gradient cases."""
+
+    def __init__(self, name):
+        from multistgraph_amd import graph_prep
+        self.name = name
+        m = self.meta = EDGE_INDEX[name]
+        self.n, self.b, self.out, self.feat, self.seed = m["nodes"], m["batch"], m["out"], m["feat"], m["seed"]
+        self.adjtype, self.adpadj, self.cheb = m["adjtype"], m["adpadj"], m["cheb"]
+        self.gold = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
+        self.grad_gold = np.load(os.path.join(GOLDEN_DIR, "edge_grad_%s.npz" % name[5:])) if m["grad"] else None
+        self.data_feature = syn.make_data_feature(self.n, self.seed, m["city"], ext_dim=self.feat - 1)
+        self.mats = np.stack(graph_prep.build_static_supports(self.data_feature["adj_mx"], self.data_feature["coordinate"],
+                                                              None, self.adjtype), 0)
+        self.shapes = syn.param_shapes(self.n, out_steps=self.out, feat_in=self.feat,
+                                       k_total=syn.k_total_for(self.adjtype, self.adpadj, self.cheb))
+        self.state = syn.closed_form_state(self.shapes, self.seed)
+        self.x, self.y = syn.make_batch_arrays(self.b, self.n, self.out, self.seed, feat=self.feat)
+
+    def config(self, device="cpu"):
+        return dict(input_window=24, output_window=self.out, add_time_in_day=True, add_day_in_week=False,
+                    load_dynamic=False, adjtype=self.adjtype, adpadj=self.adpadj, cheb_order=self.cheb, embed_dim_node=20,
+                    embed_dim_adj=20, rnn_units=64, num_layers=2, device=torch.device(device), batch_size=self.b,
+                    start_dim=0, end_dim=1)
+
+    def oracle_cfg(self):
+        return dict(adjtype=self.adjtype, adpadj=self.adpadj, cheb_order=self.cheb, num_layers=2, rnn_units=64,
+                    len_closeness=48, len_period=24, len_trend=24, output_window=self.out, input_window=24,
+                    add_time_in_day=True, add_day_in_week=False, load_dynamic=False, start_dim=0, end_dim=1)
+
+    def d_out(self):
+        return np.random.default_rng(9).standard_normal((self.b, self.out, self.n, 1)).astype(np.float32)
+
+    def checksum_errors(self, gold=None):
+        """what of the regenerated inputs, parameters and static supports misses the fixture's checksums (static_sums
+        within 1e-5 of their largest, as the N = 4096 case holds the host graph prep)"""
+        gold = self.gold if gold is None else gold
+        xs = float(self.x.astype(np.float64).sum())
+        ps = sum(float(np.abs(v.astype(np.float64)).sum()) for v in self.state.values())
+        m64 = self.mats.astype(np.float64)
+        sums = np.stack([m64.sum((1, 2)), np.abs(m64).sum((1, 2))], 1)
+        bad = []
+        if abs(xs - float(gold["x_checksum"])) > 1e-9 * max(1.0, abs(xs)):
+            bad.append("x")
+        if abs(ps - float(gold["param_checksum"])) > 1e-9 * max(1.0, abs(ps)):
+            bad.append("parameters")
+        if sums.shape != gold["static_sums"].shape or \
+                np.abs(sums - gold["static_sums"]).max() > 1e-5 * np.abs(gold["static_sums"]).max():
+            bad.append("static supports")
+        return bad
+
+
 def max_norm_err(a, b):
     """max |a-b| / max |b| - the 'rel fp32' measure the north star quotes (1e-4)."""
     a = np.asarray(a, dtype=np.float64)

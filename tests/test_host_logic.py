@@ -150,6 +150,13 @@ def test_size_queries_and_argument_checks(lib_built):
     d = spec.dims(0)
     assert lib.matgcn_prepared_bytes(C.byref(d), C.byref(nb)) == -2     # bad arg
     assert lib.matgcn_prepared_bytes(None, C.byref(nb)) == -1           # null
+    # the one shape limit of the plan (plan_from_dims): a step's state slab [B][Np][64] stays below 2^29 floats, the
+    # range of the 32-bit byte offsets of the node kernels' row stores - at N = 4096, B = 2047 is the last batch size
+    big = Case("synth4096_out24")
+    spec = spec_from_config(big.config(), big.data_feature, big.n, 20, 3)
+    assert 2048 * 4096 * 64 == 1 << 29
+    assert lib.matgcn_workspace_bytes(C.byref(spec.dims(2047)), C.byref(nb)) == 0
+    assert lib.matgcn_workspace_bytes(C.byref(spec.dims(2048)), C.byref(nb)) == -3
 
 
 def test_diagonal_supports_are_detected_on_the_host():

@@ -117,6 +117,37 @@ def test_fp64_gap_is_small():
     assert max_norm_err(a.numpy(), b.numpy()) <= 2e-5
 
 
+EDGE_FILES = sorted(f[:-4] for f in os.listdir(GOLDEN_DIR) if f.startswith("edge_") and f.endswith(".npz"))
+
+
+@pytest.mark.parametrize("stem", EDGE_FILES)
+def test_edge_fixtures_match_their_regenerated_inputs(stem):
+    """every edge_*.npz (tests/golden/make_edge_golden.py; edge_grad_<case>.npz holds the gradients of edge_<case>) carries
+    the checksums of the inputs, parameters and static supports it was computed from"""
+    from helpers import EDGE_INDEX, EdgeCase
+    name = "edge_" + stem[len("edge_grad_"):] if stem.startswith("edge_grad_") else stem
+    assert name in EDGE_INDEX and (EDGE_INDEX[name]["grad"] or stem == name)
+    c = EdgeCase(name)
+    assert c.checksum_errors(np.load(os.path.join(GOLDEN_DIR, stem + ".npz"))) == []
+    assert c.gold["pred64"].dtype == np.float64 and c.gold["pred64"].shape == (c.b, c.out, c.n, 1)
+
+
+def test_every_edge_case_has_its_files():
+    from helpers import EDGE_INDEX
+    want = set(EDGE_INDEX) | {"edge_grad_" + k[5:] for k, m in EDGE_INDEX.items() if m["grad"]}
+    assert set(EDGE_FILES) == want
+
+
+@pytest.mark.parametrize("name", ["edge_n48_b3", "edge_n65_b16"])
+def test_edge_fixtures_are_in_sync_with_the_oracle(name):
+    """the fp32 oracle forward against the stored float64 prediction (the fixtures hold its gap as gap32_pred)"""
+    from helpers import EdgeCase
+    c = EdgeCase(name)
+    pred = O.forward(torch.from_numpy(c.x), O.to_tensors(c.state), O.supports_as_tensors(c.mats), c.oracle_cfg(),
+                     faithful=False)
+    assert max_norm_err(pred.numpy(), c.gold["pred64"]) <= TOL
+
+
 GRAD_CASES = sorted(f[5:-4] for f in os.listdir(GOLDEN_DIR) if f.startswith("grad_"))
 
 
