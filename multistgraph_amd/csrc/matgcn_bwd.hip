@@ -18,15 +18,9 @@
 
 namespace {
 
-// Every instantiation of the backward's templated kernels that the schedule launches, once, as GATE16 / UPDATE16 / PX16 of
-// the forward: the launch sites look theirs up by its selectors.  A combination without an entry is an error - or, where
-// the schedule has a batched-GEMM form of the same product, that form - never another variant.
-template <class V, size_t n, class Match>
-const V* find_variant(const V (&table)[n], Match match) {
-  for (const V& v : table)
-    if (match(v)) return &v;
-  return nullptr;
-}
+// Every instantiation of the backward's templated kernels that the schedule launches, once, as GATE16 / UPDATE16 / PX16 / MIX
+// of the forward: the launch sites look theirs up by its selectors (find_variant).  A combination without an entry is an
+// error - or, where the schedule has a batched-GEMM form of the same product, that form - never another variant.
 // the chain kernels (512 threads, a workgroup per node and 64 rows): launches the entry, no entry is an error
 template <class V, size_t n, class Match, class Args>
 int launch_chain(const V (&table)[n], Match match, const dim3& grid, int lds, hipStream_t s, const Args& a) {
@@ -174,23 +168,21 @@ StackEntries stack_entries(const StackMap& map) {
 // The forward's graph-mix kernel on the plain support stack (reduction over (k, n)).  `a` arrives with what differs
 // between the callers: the column tiles of X and of the result, and how many.  parts > 1 cuts the reduction by support
 // slot - that many times the workgroups, each with a K loop of the forward's length; part k's result lands `partStride`
-// floats behind part k-1's, the consumers add them up.  wide: 32-row x 128-column tiles over pairs of column tiles
-// (k_mix_n32: 3 % row padding instead of 10 %, 4.9 workgroups per CU).  Training precision mode >= 1: bf16 operands.
-int launch_mix_plain(const Bwd& b, MixArgs a, bool wide, int parts = 1, long partStride = 0) {
+// floats behind part k-1's, the consumers add them up.  tile: MIX_64x64 over the NpC padded rows, or MIX_32x128 over the
+// N rows (mix_backward_tile).  Training precision mode >= 1: bf16 operands.
+int launch_mix_plain(const Bwd& b, MixArgs a, MixTile tile, int parts = 1, long partStride = 0) {
   const Plan& P = b.c.P;
   a.St = b.tr + b.c.R.oStP; a.ldS = P.NpC; a.sK = 0;
   a.Np = P.NpC; a.N = P.N; a.Ks = 1; a.nK = P.Ks * P.Np / 16;
-  a.nRowTiles = wide ? (P.N + 31) / 32 : P.NpC / 64;
   if (parts > 1) {
     a.parts = parts; a.nK = P.Np / 16;
     a.aPartStride = (long)P.Np * P.NpC; a.xPartStride = (long)P.Np * H; a.outPartStride = partStride;
   }
-  const dim3 grid((unsigned)(a.nRowTiles * (wide ? a.nColTiles / 2 : a.nColTiles)), (unsigned)a.parts);
-  void (*fn)(MixArgs) = wide ? k_mix_n32<false> : k_mix<2>;
-  if (b.c.prec.mix) fn = wide ? k_mix_n32<true> : k_mix_bf16<2>;
-  hipLaunchKernelGGL(fn, grid, dim3(256), 0, b.c.s, a);
-  return launch_ok();
+  return launch_mix_variant(tile, b.c.prec.mix, false, 2, a, tile.rows == 32 ? P.N : P.NpC, b.c.s);
 }
+// the transposed mix of `rows` column tiles: in pairs on 32-row x 128-column tiles when their number is even (k_mix_n32:
+// 3 % row padding instead of 10 %, 4.9 workgroups per CU), else on the forward's 64 x 64 tiles
+inline MixTile mix_backward_tile(int rows) { return (rows & 1) == 0 ? MIX_32x128 : MIX_64x64; }
 
 // dst[rows][m][i] = sum_kk StP[kk][m] * src[rows][slot 1..][kk][i]: the transposed graph mix of the dense slots of a
 // [rows][S][Np][Cc] gradient.  With 64 feature columns: launch_mix_plain, one column tile per row (an even number of
@@ -205,7 +197,7 @@ int mix_transposed(const Bwd& b, const float* src, int rows, int Cc, float* dst,
     a.out = dst; a.sN = H; a.sT = (long)P.Np * H; a.nColTiles = rows;
     const long outFloats = (long)rows * P.Np * H;
     a.outFloats = outFloats < (1L << 29) ? outFloats : 0;
-    return launch_mix_plain(b, a, (rows & 1) == 0, split ? P.Ks : 1, partStride);
+    return launch_mix_plain(b, a, mix_backward_tile(rows), split ? P.Ks : 1, partStride);
   }
   GemmArgs g = gemm_args(b.c.prep + P.oSt, src + (size_t)P.Np * Cc, dst, P.N, Cc, P.Ks * P.Np);
   g.sAm = P.Mp; g.sAk = 1;
@@ -847,7 +839,7 @@ int bwd_x_columns(Pass& pass, const LayerBufs& L) {
       MixArgs a;
       a.X = DAx + (size_t)Np * cols; a.xTileStride = 64; a.ldX = (int)cols;
       a.out = MixN; a.sN = cols; a.sT = 64; a.nColTiles = (int)(cols / 64); a.outFloats = (long)N * cols;
-      RETURN_IF(launch_mix_plain(b, a, false));
+      RETURN_IF(launch_mix_plain(b, a, MIX_64x64));
     } else if (P.Ks > 0) {
       GemmArgs q = gemm_args(c.prep + P.oSt, DAx + (size_t)Np * cols, MixN, N, (int)cols, P.Ks * Np);
       q.sAm = P.Mp; q.sAk = 1; q.sBk = cols; q.sBn = 1; q.sCm = cols; q.sCn = 1;

@@ -540,48 +540,6 @@ int on_main_stream(void* callerStream, Body&& body) {
   return rc;
 }
 
-// out[(k,n)][col] = sum_m S_k[n][m] X[m][col]; see k_mix.  bf16: the call's Precision::mix
-int launch_mix(const Plan& P, bool bf16, const float* St, const float* X, long xTileStride, int ldX, int nColTiles,
-               float* out, long sN, long sK, long sT, int Ks, int rowsM, hipStream_t s, bool stepRole = false,
-               long outFloats = 0) {
-  if (Ks <= 0 || rowsM <= 0) return MATGCN_OK;   // every support folded away: nothing to mix
-  MixArgs a;
-  a.St = St; a.ldS = P.Mp; a.X = X; a.xTileStride = xTileStride; a.ldX = ldX;
-  a.out = out; a.sN = sN; a.sK = sK; a.sT = sT; a.outFloats = outFloats;
-  a.Np = P.Np; a.N = P.N; a.Ks = Ks; a.nK = P.Np / 16; a.nColTiles = nColTiles;
-  a.nRowTiles = (int)(rup(rowsM, 64) / 64);
-  ProfScope prof(stepRole ? MATGCN_PROF_MIX : MATGCN_PROF_MIX_PRE, s);
-  const dim3 grid((unsigned)(a.nRowTiles * nColTiles));
-  if (bf16) {   // opt-in bf16-operand variant of the inference forward (fp32 accumulate, fp32 in / out)
-    if (stepRole) hipLaunchKernelGGL(k_mix_bf16<1>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_mix_bf16<0>, grid, dim3(256), 0, s, a);
-  } else if (a.nK > 64) {   // more than 1 024 reduction indices: partial sums every 256 (k_mix's FLUSH)
-    if (stepRole) hipLaunchKernelGGL((k_mix<1, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_mix<0, true>), grid, dim3(256), 0, s, a);
-  } else if (nColTiles <= 16 && xTileStride % 4 == 0 && ldX >= 64) {
-    // small batches (the reference ships batch_size 16): twice the workgroups of half the width, up to 16 column tiles
-    // (batch rows of a step mix) - round 4, BM 403: B = 16 20.8 -> 18.1 us per launch, forward 3.69 -> 3.56 ms; B = 32 no
-    // gain per launch and the forward 2 % SLOWER; DC 237 at B = 16 unchanged: profiles/r04_small_batch_lab.log
-    const dim3 g2((unsigned)(a.nRowTiles * nColTiles * 2));
-    if (stepRole) hipLaunchKernelGGL(k_mix_c32<1>, g2, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_mix_c32<0>, g2, dim3(256), 0, s, a);
-  } else if (stepRole) {
-    hipLaunchKernelGGL(k_mix<1>, grid, dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL(k_mix<0>, grid, dim3(256), 0, s, a);
-  }
-  return launch_ok();
-}
-
-// mix of `rows` contiguous [Np][64] slabs into the node-major buffer G [N][rows][Ks][64]
-// (nodeStride: floats between the nodes of G when the `rows` rows are a slice of a larger node-major block)
-int mix_rows(const Plan& P, bool bf16, const float* St, const float* X, int rows, float* G, hipStream_t s, bool stepRole = false,
-             long nodeStride = 0) {
-  const long sN = nodeStride ? nodeStride : (long)rows * P.Ks * H;
-  return launch_mix(P, bf16, St, X, (long)P.Np * H, H, rows, G, sN, H, (long)P.Ks * H, P.Ks, P.Ks * P.Np, s, stepRole,
-                    (long)(P.N - 1) * sN + (long)rows * P.Ks * H);
-}
-
 // the stack entries the kernels see (StackMap): kept slots (identity + dense) and folded diagonal ones
 StackMap build_stack_map(const Plan& P, const matgcn_dims* D, const matgcn_params* params) {
   StackMap map;
@@ -627,6 +585,14 @@ struct Ctx {
   Precision prec;             // fp32 unless a hot entry point sets it: matgcn_prepare and the unit entry points
                               // (matgcn_agcn_gate_fwd, matgcn_encoder_fwd, ...) deliberately leave the default
 };
+
+// the entry of a variant table (GATE16 / UPDATE16 / PX16 / MIX here, CHAIN_RES, NARROW, BGEMM, ... in matgcn_bwd.hip) or null
+template <class V, size_t n, class Match>
+const V* find_variant(const V (&table)[n], Match match) {
+  for (const V& v : table)
+    if (match(v)) return &v;
+  return nullptr;
+}
 
 // dynamic LDS: k_gate16 48 KB (state chunk + two ping-pong chunks), k_update16 64 KB (+ the x_t tile of the residual
 // cell), k_px16 the whole tile
@@ -676,12 +642,72 @@ const PxVariant PX16[] = {
 template <size_t n>
 int launch_node(const NodeVariant (&table)[n], int mode, bool save, int rows, bool bf, bool zero, const dim3& grid,
                 hipStream_t s, const Node16Args& a) {
-  for (const NodeVariant& v : table)
-    if (v.mode == mode && v.save == save && v.rows == rows && v.bf == bf && v.zero == zero) {
-      hipLaunchKernelGGL(v.fn, grid, dim3(512), v.lds, s, a);
-      return launch_ok();
-    }
-  return MATGCN_ERR_UNSUPPORTED;
+  const NodeVariant* v = find_variant(table, [&](auto& e) {
+    return e.mode == mode && e.save == save && e.rows == rows && e.bf == bf && e.zero == zero; });
+  if (!v) return MATGCN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(v->fn, grid, dim3(512), v->lds, s, a);
+  return launch_ok();
+}
+
+// Every instantiation of the graph-mix kernels (matgcn_kernels.hip, section 5), once; every launch of one goes through
+// launch_mix_variant.  Selectors: tile - the workgroup's output tile, rows x columns (MixArgs counts column tiles of 64:
+// a 64 x 32 tile is half of one, a 32 x 128 tile a pair); bf - bf16 operands; flush - k_mix's FLUSH; role - 0 pre-passes
+// and Chebyshev products, 1 the recurrent step's mix (the roofline kernel), 2 the backward's transposed mixes.
+struct MixTile { int rows, cols; };
+constexpr MixTile MIX_64x64{64, 64}, MIX_64x32{64, 32}, MIX_32x128{32, 128};
+struct MixVariant { MixTile tile; bool bf, flush; int role; void (*fn)(MixArgs); };
+const MixVariant MIX[] = {
+    {MIX_64x64, false, false, 0, k_mix<0>},          {MIX_64x64, false, false, 1, k_mix<1>},
+    {MIX_64x64, false, false, 2, k_mix<2>},          {MIX_64x64, false, true, 0, k_mix<0, true>},
+    {MIX_64x64, false, true, 1, k_mix<1, true>},     {MIX_64x32, false, false, 0, k_mix_c32<0>},
+    {MIX_64x32, false, false, 1, k_mix_c32<1>},      {MIX_32x128, false, false, 2, k_mix_n32<false>},
+    {MIX_32x128, true, false, 2, k_mix_n32<true>},   {MIX_64x64, true, false, 0, k_mix_bf16<0>},
+    {MIX_64x64, true, false, 1, k_mix_bf16<1>},      {MIX_64x64, true, false, 2, k_mix_bf16<2>},
+};
+// launches the table's entry for the selectors over `rows` output rows: grid.x = row tiles x column units of the entry's
+// tile shape, grid.y = a.parts; a combination without an entry is an error, never another variant
+int launch_mix_variant(MixTile tile, bool bf, bool flush, int role, MixArgs a, int rows, hipStream_t s) {
+  const MixVariant* v = find_variant(MIX, [&](auto& e) {
+    return e.tile.rows == tile.rows && e.tile.cols == tile.cols && e.bf == bf && e.flush == flush && e.role == role; });
+  if (!v) return MATGCN_ERR_UNSUPPORTED;
+  a.nRowTiles = (rows + tile.rows - 1) / tile.rows;
+  const dim3 grid((unsigned)(a.nRowTiles * (a.nColTiles * 64 / tile.cols)), (unsigned)a.parts);
+  hipLaunchKernelGGL(v->fn, grid, dim3(256), 0, s, a);
+  return launch_ok();
+}
+
+// The forward's shape rules.  The opt-in bf16-operand variant of the inference forward (fp32 accumulate, fp32 in / out)
+// wins over both: there is no FLUSH and no 64 x 32 tile in bf16, past 1 024 nodes included.
+// more than 1 024 reduction indices: partial sums every 256 (k_mix's FLUSH)
+inline bool mix_flush(bool bf16, const MixArgs& a) { return !bf16 && a.nK > 64; }
+// small batches (the reference ships batch_size 16): twice the workgroups of half the width, up to 16 column tiles
+// (batch rows of a step mix) - round 4, BM 403: B = 16 20.8 -> 18.1 us per launch, forward 3.69 -> 3.56 ms; B = 32 no
+// gain per launch and the forward 2 % SLOWER; DC 237 at B = 16 unchanged: profiles/r04_small_batch_lab.log
+inline bool mix_half_tiles(bool bf16, const MixArgs& a) {
+  return !bf16 && !mix_flush(bf16, a) && a.nColTiles <= 16 && a.xTileStride % 4 == 0 && a.ldX >= 64;
+}
+
+// out[(k,n)][col] = sum_m S_k[n][m] X[m][col]; see k_mix.  bf16: the call's Precision::mix
+int launch_mix(const Plan& P, bool bf16, const float* St, const float* X, long xTileStride, int ldX, int nColTiles,
+               float* out, long sN, long sK, long sT, int Ks, int rowsM, hipStream_t s, bool stepRole = false,
+               long outFloats = 0) {
+  if (Ks <= 0 || rowsM <= 0) return MATGCN_OK;   // every support folded away: nothing to mix
+  MixArgs a;
+  a.St = St; a.ldS = P.Mp; a.X = X; a.xTileStride = xTileStride; a.ldX = ldX;
+  a.out = out; a.sN = sN; a.sK = sK; a.sT = sT; a.outFloats = outFloats;
+  a.Np = P.Np; a.N = P.N; a.Ks = Ks; a.nK = P.Np / 16; a.nColTiles = nColTiles;
+  ProfScope prof(stepRole ? MATGCN_PROF_MIX : MATGCN_PROF_MIX_PRE, s);
+  return launch_mix_variant(mix_half_tiles(bf16, a) ? MIX_64x32 : MIX_64x64, bf16, mix_flush(bf16, a), stepRole ? 1 : 0, a,
+                            rowsM, s);
+}
+
+// mix of `rows` contiguous [Np][64] slabs into the node-major buffer G [N][rows][Ks][64]
+// (nodeStride: floats between the nodes of G when the `rows` rows are a slice of a larger node-major block)
+int mix_rows(const Plan& P, bool bf16, const float* St, const float* X, int rows, float* G, hipStream_t s, bool stepRole = false,
+             long nodeStride = 0) {
+  const long sN = nodeStride ? nodeStride : (long)rows * P.Ks * H;
+  return launch_mix(P, bf16, St, X, (long)P.Np * H, H, rows, G, sN, H, (long)P.Ks * H, P.Ks, P.Ks * P.Np, s, stepRole,
+                    (long)(P.N - 1) * sN + (long)rows * P.Ks * H);
 }
 
 // sizes above 64 KB must be opted into once per kernel and device
@@ -749,12 +775,10 @@ int hoist_x(const Ctx& c, int l, const float* xin, int t0, int nt, hipStream_t s
   const bool bf = c.prec.node;
   if (bf) a.w = c.ws + P.oW16x[l];
   const int nrt = P.B <= 16 ? 1 : P.B <= 32 ? 2 : 4;   // row tiles that hold batch rows
-  for (const PxVariant& v : PX16)
-    if (v.nrt == nrt && v.bf == bf) {
-      hipLaunchKernelGGL(v.fn, grid, dim3(512), P.nodeLds, s, a);
-      return launch_ok();
-    }
-  return MATGCN_ERR_UNSUPPORTED;
+  const PxVariant* v = find_variant(PX16, [&](auto& e) { return e.nrt == nrt && e.bf == bf; });
+  if (!v) return MATGCN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(v->fn, grid, dim3(512), P.nodeLds, s, a);
+  return launch_ok();
 }
 
 // The recurrent mix of layer l at step t+1 (phase 0: mix of h_t) equals the x-part mix of layer l+1 at step t, so in

@@ -70,15 +70,15 @@ struct FuseArgs {
 };
 
 struct MixArgs {
-  const float* St;
-  int ldS;
-  const float* X;
-  long xTileStride;
-  int ldX;
-  float* out;
-  long sN, sK, sT;
-  long outFloats;        // extent of `out` (bounds the write-through buffer descriptor; 0: plain stores)
-  int Np, N, Ks, nK, nColTiles, nRowTiles;
+  const float* St = nullptr;
+  int ldS = 0;
+  const float* X = nullptr;
+  long xTileStride = 0;
+  int ldX = 0;
+  float* out = nullptr;
+  long sN = 0, sK = 0, sT = 0;
+  long outFloats = 0;    // extent of `out` (bounds the write-through buffer descriptor; 0: plain stores)
+  int Np = 0, N = 0, Ks = 0, nK = 0, nColTiles = 0, nRowTiles = 0;   // nRowTiles: launch_mix_variant, from the tile shape
   // split reduction (blockIdx.y = part): part p multiplies reduction rows [p*nK*16, ..) of St with the matching rows
   // of X and writes its own partial result - the transposed mix of the backward splits by support slot
   int parts = 1;

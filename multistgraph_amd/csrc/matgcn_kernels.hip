@@ -597,8 +597,7 @@ __global__ __launch_bounds__(256) void k_build_xa0(const float* __restrict__ x0p
 // =================================================================================================
 // 64 x 64 output tile per workgroup, 4 waves, each a 32x32 tile as 2x2 accumulators of the 16x16x4 MFMA; K-step 16 staged through
 // LDS (double buffer, fed from registers that run two tiles ahead of the MFMAs; one barrier per step).  A = St (k-major, so the tile is 16 rows of
-// 256 contiguous bytes), B = 64 feature columns of one state row (256-byte lines).  Workgroups that share an
-// XCD (id % 8) sweep the row tiles of one column tile back to back, so St and that X slice stay in its L2.
+// 256 contiguous bytes), B = 64 feature columns of one state row (256-byte lines).
 // ROLE only names the instantiation (0: pre-passes and Chebyshev products, 1: the recurrent step's mix of h / z*h),
 // so that profilers list the roofline kernel - the per-step launch - on its own line.
 // FLUSH (round 4): the accumulators are one fp32 fma chain over the WHOLE reduction - 4 096 links at N = 4 096, where the
@@ -609,22 +608,29 @@ __global__ __launch_bounds__(256) void k_build_xa0(const float* __restrict__ x0p
 // (round 4, measured and rejected: rotating the wave priority with the K-tile index by dispatch round so that the five
 //  workgroups of a CU leave together - they do, and every one is slower: 43.0 vs 41.3 us, profiles/r04_mix_stamps_lab.log)
 constexpr int MIX_FLUSH_TILES = 16;
+
+// Tile order of every mix kernel: workgroups that share an XCD (id % 8) sweep the row tiles of one column unit back to
+// back, so St and that X slice stay in its L2.  A column unit is a column tile (k_mix, k_mix_bf16), half a tile
+// (k_mix_c32) or a pair of tiles (k_mix_n32).
+__device__ __forceinline__ void mix_tile_order(int id, int nColUnits, int nRowTiles, int& rowTile, int& colUnit) {
+  if ((nColUnits & 7) == 0) {
+    const int xcd = id & 7, j = id >> 3, cpx = nColUnits >> 3;
+    rowTile = j % nRowTiles;
+    colUnit = xcd * cpx + j / nRowTiles;
+  } else {
+    rowTile = id % nRowTiles;
+    colUnit = id / nRowTiles;
+  }
+}
+
 template <int ROLE, bool FLUSH = false>
 __global__ __launch_bounds__(256) void k_mix(MixArgs a) {
   // (FLUSH costs 16 registers, 72 in all: seven workgroups per CU instead of eight, +3.7 % per launch at N = 4 096; forced
   //  into 64 registers the compiler spilled a pointer inside the K loop, +6.5 %: profiles/r04_mix_lab.log)
   __shared__ __attribute__((aligned(16))) float As[2][16 * 64];
   __shared__ __attribute__((aligned(16))) float Bs[2][16 * 64];
-  const int id = blockIdx.x;
   int colTile, rowTile;
-  if ((a.nColTiles & 7) == 0) {
-    const int xcd = id & 7, j = id >> 3, cpx = a.nColTiles >> 3;
-    rowTile = j % a.nRowTiles;
-    colTile = xcd * cpx + j / a.nRowTiles;
-  } else {
-    rowTile = id % a.nRowTiles;
-    colTile = id / a.nRowTiles;
-  }
+  mix_tile_order(blockIdx.x, a.nColTiles, a.nRowTiles, rowTile, colTile);
   const int row0 = rowTile * 64;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1, j = lane & 15, kq = lane >> 4;
@@ -772,21 +778,13 @@ __global__ __launch_bounds__(256) void k_mix(MixArgs a) {
 // workgroups (2.5 per CU, five waves per CU on average as before, but the longest CU holds 3 halves instead of 2 wholes).
 // Same pipeline as k_mix (K-step 16 through LDS, two K-tiles ahead in registers, rotated rows); a wave owns 32 rows x 16
 // columns = 2 x 1 accumulators, the B tile uses columns 0..31 of its 64-wide LDS rows (both halves of the workgroup request
-// it - duplicate stores of equal values).  Launched for at most 16 column tiles (B <= 16: launch_mix).
+// it - duplicate stores of equal values).  Launched for at most 16 column tiles (B <= 16: mix_half_tiles).
 template <int ROLE>
 __global__ __launch_bounds__(256) void k_mix_c32(MixArgs a) {
   __shared__ __attribute__((aligned(16))) float As[2][16 * 64];
   __shared__ __attribute__((aligned(16))) float Bs[2][16 * 64];
-  const int id = blockIdx.x, nCt2 = 2 * a.nColTiles;
-  int ct2, rowTile;
-  if ((nCt2 & 7) == 0) {
-    const int xcd = id & 7, jj = id >> 3, cpx = nCt2 >> 3;
-    rowTile = jj % a.nRowTiles;
-    ct2 = xcd * cpx + jj / a.nRowTiles;
-  } else {
-    rowTile = id % a.nRowTiles;
-    ct2 = id / a.nRowTiles;
-  }
+  int ct2, rowTile;     // column unit: half a column tile
+  mix_tile_order(blockIdx.x, 2 * a.nColTiles, a.nRowTiles, rowTile, ct2);
   const int colTile = ct2 >> 1, half = ct2 & 1;
   const int row0 = rowTile * 64;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -885,7 +883,7 @@ __global__ __launch_bounds__(256) void k_mix_c32(MixArgs a) {
 // batch rows - per workgroup 13 x 32 x 3 = 1248 workgroups are 4.9 per CU.  Each of the 4 waves owns 32 of the 128 columns
 // and all 32 rows: the same 2 x 2 accumulators, K-tile 16, two tiles ahead in registers, rotated LDS rows (16 floats per odd
 // k: the two k rows a 32-lane half reads sit half a bank row apart) and write-through row-store epilogue as k_mix.
-// Needs an even number of column tiles (the launcher falls back to k_mix<2> otherwise).
+// Needs an even number of column tiles (mix_backward_tile: k_mix<2> otherwise).
 // BF (matgcn_set_train_precision(1|2), the training side line): bf16 OPERANDS, fp32 accumulation, on
 // v_mfma_f32_16x16x32_bf16 - see k_mix_n32_bf_loop below; tiles, work split and epilogue are the fp32 kernel's.
 __device__ __forceinline__ void k_mix_n32_bf_loop(const MixArgs& a, unsigned int (*As)[16 * 32], unsigned int (*Bs)[16 * 128],
@@ -894,17 +892,8 @@ template <bool BF = false>
 __global__ __launch_bounds__(256) void k_mix_n32(MixArgs a) {
   __shared__ __attribute__((aligned(16))) float As[2][16 * 32];
   __shared__ __attribute__((aligned(16))) float Bs[2][16 * 128];
-  const int id = blockIdx.x;
-  const int nPairs = a.nColTiles >> 1;
   int colPair, rowTile;
-  if ((nPairs & 7) == 0) {
-    const int xcd = id & 7, jj = id >> 3, cpx = nPairs >> 3;
-    rowTile = jj % a.nRowTiles;
-    colPair = xcd * cpx + jj / a.nRowTiles;
-  } else {
-    rowTile = id % a.nRowTiles;
-    colPair = id / a.nRowTiles;
-  }
+  mix_tile_order(blockIdx.x, a.nColTiles >> 1, a.nRowTiles, rowTile, colPair);
   const int row0 = rowTile * 32;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int j = lane & 15, kq = lane >> 4;
@@ -1043,6 +1032,17 @@ __device__ __forceinline__ uint4 pack_bf16_rows(const float4& k0, const float4& 
   return make_uint4(bf16_rne(k0.x) | (bf16_rne(k1.x) << 16), bf16_rne(k0.y) | (bf16_rne(k1.y) << 16),
                     bf16_rne(k0.z) | (bf16_rne(k1.z) << 16), bf16_rne(k0.w) | (bf16_rne(k1.w) << 16));
 }
+// The two fp32 rows behind packed row pr of K-tile t (32 reduction indices; nT tiles, kLast the last index): loads are
+// unconditional (tile and row index clamped), values past the last reduction index zeroed by a select
+__device__ __forceinline__ void mix_ld_bf16_pair(const float* base, size_t ld, int pr, int t, int nT, int kLast, float4& r0,
+                                                 float4& r1) {
+  const int k0 = 32 * min(t, nT - 1) + 2 * pr, k1 = k0 + 1;
+  const float4 v0 = *reinterpret_cast<const float4*>(base + (size_t)min(k0, kLast) * ld);
+  const float4 v1 = *reinterpret_cast<const float4*>(base + (size_t)min(k1, kLast) * ld);
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  r0 = k0 <= kLast ? v0 : z;
+  r1 = k1 <= kLast ? v1 : z;
+}
 
 // K loop of k_mix_n32<true>: K-tile 32 = 16 packed rows (word = bf16 of reduction indices 2 pr, 2 pr + 1, rounded to
 // nearest even on the way into LDS; indices past the last one read as zero).  One v_mfma_f32_16x16x32_bf16 per
@@ -1065,19 +1065,11 @@ __device__ __forceinline__ void k_mix_n32_bf_loop(const MixArgs& a, unsigned int
   const int aPos = apr * 32 + ((asg * 4 + 16 * ((apr >> 2) & 1)) & 31);
   const int bPos0 = bpr * 128 + ((bsg * 4 + 16 * ((bpr >> 2) & 1)) & 127);
   const int bPos1 = bpr * 128 + ((64 + bsg * 4 + 16 * ((bpr >> 2) & 1)) & 127);
-  auto ld = [&](const float* base, size_t ld_, int pr, int t, float4& r0, float4& r1) {
-    const int k0 = 32 * min(t, nT - 1) + 2 * pr, k1 = k0 + 1;
-    const float4 v0 = *reinterpret_cast<const float4*>(base + (size_t)min(k0, kLast) * ld_);
-    const float4 v1 = *reinterpret_cast<const float4*>(base + (size_t)min(k1, kLast) * ld_);
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    r0 = k0 <= kLast ? v0 : z;
-    r1 = k1 <= kLast ? v1 : z;
-  };
   struct Tile { float4 a0, a1, b00, b01, b10, b11; };
   auto load = [&](int t, Tile& r) {
-    ld(ap, a.ldS, apr, t, r.a0, r.a1);
-    ld(bp0, a.ldX, bpr, t, r.b00, r.b01);
-    ld(bp1, a.ldX, bpr, t, r.b10, r.b11);
+    mix_ld_bf16_pair(ap, a.ldS, apr, t, nT, kLast, r.a0, r.a1);
+    mix_ld_bf16_pair(bp0, a.ldX, bpr, t, nT, kLast, r.b00, r.b01);
+    mix_ld_bf16_pair(bp1, a.ldX, bpr, t, nT, kLast, r.b10, r.b11);
   };
   auto store = [&](int buf, const Tile& r) {
     *reinterpret_cast<uint4*>(&As[buf][aPos]) = pack_bf16_rows(r.a0, r.a1);
@@ -1124,20 +1116,57 @@ __device__ __forceinline__ void k_mix_n32_bf_loop(const MixArgs& a, unsigned int
   }
 }
 
+// k_mix's store epilogue (see there for its measured reasons) as a function: the wave's 32 x 32 accumulator tile - rows
+// row0 .., columns col0 .. of column tile colTile - through its 4 KB of LDS at stg into write-through row stores.  The fp32
+// kernels keep theirs inline: behind a call the compiler requests the epilogue's kernel arguments in front of the K loop,
+// 9 more scalar registers and another schedule for kernels whose code is pinned (variant tables).
+__device__ __forceinline__ void mix_store_tile(const MixArgs& a, int part, float* stg, const f32x4 (&acc)[2][2], int row0,
+                                               int colTile, int col0) {
+  const int lane = threadIdx.x & 63, j = lane & 15, kq = lane >> 4;
+  const int jq = j >> 2, jr = j & 3, kb = kq & 1;
+  int xe[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) xe[e] = e * 32 + ((jq ^ e) << 2) + jr;
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int base = (p * 16 + 4 * kq) * 32 + ((q ^ kb) << 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) stg[base + xe[e]] = acc[p][q][e];
+    }
+  const bool wt = a.outFloats > 0 && a.outFloats < (1L << 29);   // 32-bit byte offsets
+  float* outp = a.out + (size_t)part * a.outPartStride;
+  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(outp, 0, wt ? (int)(a.outFloats * 4) : 0, 0x00020000);
+  float4 v4[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int lrow = u * 8 + (lane >> 3), q = lane & 7;
+    v4[u] = *reinterpret_cast<const float4*>(&stg[lrow * 32 + ((q ^ (lrow & 7)) << 2)]);
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int lrow = u * 8 + (lane >> 3), q = lane & 7;
+    const float4 v = v4[u];
+    const int row = row0 + lrow;
+    const int k = row / a.Np, n = row - k * a.Np;
+    const bool ok = k < a.Ks && n < a.N;
+    const size_t off = (size_t)colTile * a.sT + (size_t)n * a.sN + (size_t)k * a.sK + col0 + q * 4;
+    if (wt) {
+      const u32x4 bits = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+      __builtin_amdgcn_raw_buffer_store_b128(bits, rsrc, ok ? (int)(off * 4) : (int)0x7ffffff0, 0, 16);   // sc1; dropped when out of range
+    } else if (ok) {
+      *reinterpret_cast<float4*>(outp + off) = v;
+    }
+  }
+}
+
 template <int ROLE>
 __global__ __launch_bounds__(256) void k_mix_bf16(MixArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned int As[2][16 * 64];
   __shared__ __attribute__((aligned(16))) unsigned int Bs[2][16 * 64];
-  const int id = blockIdx.x;
   int colTile, rowTile;
-  if ((a.nColTiles & 7) == 0) {
-    const int xcd = id & 7, jj = id >> 3, cpx = a.nColTiles >> 3;
-    rowTile = jj % a.nRowTiles;
-    colTile = xcd * cpx + jj / a.nRowTiles;
-  } else {
-    rowTile = id % a.nRowTiles;
-    colTile = id / a.nRowTiles;
-  }
+  mix_tile_order(blockIdx.x, a.nColTiles, a.nRowTiles, rowTile, colTile);
   const int row0 = rowTile * 64;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1, j = lane & 15, kq = lane >> 4;
@@ -1149,15 +1178,7 @@ __global__ __launch_bounds__(256) void k_mix_bf16(MixArgs a) {
   const int part = ROLE == 2 ? (int)blockIdx.y : 0;
   const float* ap = a.St + (size_t)part * a.aPartStride + row0 + sg * 4;
   const float* bp = a.X + (size_t)part * a.xPartStride + (size_t)colTile * a.xTileStride + sg * 4;
-  // loads are unconditional (row index clamped, values past the last reduction index zeroed by a select)
-  auto ld = [&](const float* base, size_t ld_, int t, float4& r0, float4& r1) {
-    const int k0 = 32 * min(t, nT - 1) + 2 * pr, k1 = k0 + 1;
-    const float4 v0 = *reinterpret_cast<const float4*>(base + (size_t)min(k0, kLast) * ld_);
-    const float4 v1 = *reinterpret_cast<const float4*>(base + (size_t)min(k1, kLast) * ld_);
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    r0 = k0 <= kLast ? v0 : z;
-    r1 = k1 <= kLast ? v1 : z;
-  };
+  auto ld = [&](const float* base, size_t ld_, int t, float4& r0, float4& r1) { mix_ld_bf16_pair(base, ld_, pr, t, nT, kLast, r0, r1); };
   float4 a0, a1, b0, b1, a2, a3, b2, b3;
   ld(ap, a.ldS, 0, a0, a1); ld(bp, a.ldX, 0, b0, b1);
   *reinterpret_cast<uint4*>(&As[0][stPos]) = pack_bf16_rows(a0, a1);
@@ -1204,36 +1225,8 @@ __global__ __launch_bounds__(256) void k_mix_bf16(MixArgs a) {
       __syncthreads();
     }
   }
-  // epilogue: as k_mix (accumulator tile turned through LDS into 16-byte write-through row stores)
-  float* stg = reinterpret_cast<float*>(w < 2 ? &As[0][0] : &Bs[0][0]) + (w & 1) * 1024;
-#pragma unroll
-  for (int p = 0; p < 2; ++p)
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int lrow = p * 16 + 4 * kq + e, lcol = q * 16 + j;
-        stg[lrow * 32 + (((lcol >> 2) ^ (lrow & 7)) << 2) + (lcol & 3)] = acc[p][q][e];
-      }
-  const bool wt = a.outFloats > 0 && a.outFloats < (1L << 29);   // 32-bit byte offsets
-  float* outp = a.out + (size_t)part * a.outPartStride;
-  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(outp, 0, wt ? (int)(a.outFloats * 4) : 0, 0x00020000);
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int lrow = u * 8 + (lane >> 3), q = lane & 7;
-    const float4 v = *reinterpret_cast<const float4*>(&stg[lrow * 32 + ((q ^ (lrow & 7)) << 2)]);
-    const int row = row0 + wr * 32 + lrow;
-    const int k = row / a.Np, n = row - k * a.Np;
-    if (k < a.Ks && n < a.N) {
-      const size_t off = (size_t)colTile * a.sT + (size_t)n * a.sN + (size_t)k * a.sK + wc * 32 + q * 4;
-      if (wt) {
-        const u32x4 bits = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-        __builtin_amdgcn_raw_buffer_store_b128(bits, rsrc, (int)(off * 4), 0, 16);   // aux 16 = sc1
-      } else {
-        *reinterpret_cast<float4*>(outp + off) = v;
-      }
-    }
-  }
+  mix_store_tile(a, part, reinterpret_cast<float*>(w < 2 ? &As[0][0] : &Bs[0][0]) + (w & 1) * 1024, acc, row0 + wr * 32,
+                 colTile, wc * 32);
 }
 
 // =================================================================================================

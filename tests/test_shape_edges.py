@@ -5,17 +5,17 @@ truth is the CPU oracle in float64 (tests/golden/make_edge_golden.py -> edge_*.n
 by test_oracle_golden.py).  Whoever moves a threshold moves the shape with it:
 
   case            - rule                                                                   - where the rule lives
-  edge_n48_b3     - Np 48 != NpC 64, Ks*Np = 144 (ragged 64-row mix tile), odd rows        - matgcn_bwd.hip:launch_mix_plain / mix_transposed
-  edge_n64_b17    - N = Np = NpC (no padding row); first B past k_mix_c32 and NRT 1        - matgcn_capi.hip:launch_mix (nColTiles <= 16), hoist_x (nrt)
-  edge_n65_b16    - one node past a tile: Np 80, NpC 128; last B of k_mix_c32 and NRT 1    - matgcn_capi.hip:plan_from_dims, launch_mix, hoist_x
+  edge_n48_b3     - Np 48 != NpC 64, Ks*Np = 144 (ragged 64-row mix tile), odd rows        - matgcn_bwd.hip:launch_mix_plain / mix_backward_tile
+  edge_n64_b17    - N = Np = NpC (no padding row); first B past k_mix_c32 and NRT 1        - matgcn_capi.hip:mix_half_tiles (nColTiles <= 16), hoist_x (nrt)
+  edge_n65_b16    - one node past a tile: Np 80, NpC 128; last B of k_mix_c32 and NRT 1    - matgcn_capi.hip:plan_from_dims, mix_half_tiles, hoist_x
   edge_n256_b33   - last N of the 32-row items at B > 32; first B of NRT 4; 2 blocks of 32 - matgcn_capi.hip:cell_phase (rows32), hoist_x (nrt)
   edge_n257_b33   - first shape on 64-row items by both criteria; Np 272, NpC 320          - matgcn_capi.hip:cell_phase (rows32)
   edge_n257_b65   - 64-row items, two row blocks per node (RB = 2): rb / rtb of PX and R   - matgcn_node16.hip:node_item, k_gate16 / k_update16 (RB, rb, rtb)
   edge_n256_b65   - three 32-row blocks per node, the last with one real row               - matgcn_node16.hip:node_item / node_items
   edge_n263_b8    - N % 8 = 7 (grids round N up to 8); nColTiles % 8 == 0 swizzle in c32   - matgcn_node16.hip:node_items, matgcn_kernels.hip:k_mix_c32
-  edge_n1024_b2   - nK = 64: the longest reduction chain without FLUSH, even rows          - matgcn_capi.hip:launch_mix (a.nK > 64)
-  edge_n1039_b3   - Np 1040, nK = 65: FLUSH, odd nK, last group of one tile; odd rows      - matgcn_capi.hip:launch_mix, matgcn_kernels.hip:k_mix<., true>
-  edge_n1039_b2   - the same N with even rows (forward only)                               - matgcn_bwd.hip:mix_transposed ((rows & 1) == 0)
+  edge_n1024_b2   - nK = 64: the longest reduction chain without FLUSH, even rows          - matgcn_capi.hip:mix_flush (a.nK > 64)
+  edge_n1039_b3   - Np 1040, nK = 65: FLUSH, odd nK, last group of one tile; odd rows      - matgcn_capi.hip:mix_flush, matgcn_kernels.hip:k_mix<., true>
+  edge_n1039_b2   - the same N with even rows (forward only)                               - matgcn_bwd.hip:mix_backward_tile ((rows & 1) == 0)
   edge_n21_b129   - RB = 3; carrier of precision mode 2 (always 64-row items) at B > 64    - matgcn_capi.hip:cell_phase (!c.prec.node)
 
 Tolerances are the project's own and do not depend on what the kernels give: 1e-4 max-normalised and element-wise
