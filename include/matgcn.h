@@ -27,6 +27,8 @@
  * half-batch plans and the bf16 copies of the weight streams.  No signature of ABI 9 changed.
  * ABI 12 over ABI 11: the batch-split forward switch and the lab schedule matgcn_set_wavefront(2) are removed (any
  * non-zero value now selects the wavefront); matgcn_workspace_bytes no longer counts two half-batch plans.
+ * Still ABI 12: matgcn_set_mix_precision(3) (three bf16 pieces per operand of the graph mixes) is one more value of an
+ * existing argument - no symbol, signature or struct changed, and every value ABI 12 defined keeps its meaning and bits.
  */
 #ifndef MATGCN_H
 #define MATGCN_H
@@ -122,7 +124,9 @@ const char* matgcn_error_string(int status);
 /* Bytes of the two caller-owned device buffers for `dims`.  matgcn_workspace_bytes depends on two library settings: while
  * matgcn_set_mix_precision(2) or matgcn_set_train_precision(2) is in force it also counts the bf16 copies of the recurrent
  * weight streams (half the bytes of the fp32 streams, behind everything else); a mode-2 forward on a workspace sized
- * without them returns MATGCN_ERR_SMALL_BUFFER (ask again and re-allocate).  The fp32 paths never pay for them. */
+ * without them returns MATGCN_ERR_SMALL_BUFFER (ask again and re-allocate).  While matgcn_set_mix_precision(3) is in force
+ * it counts the three bf16 planes of the support stack instead (6 bytes per element of the [Np up to 32][Ks*Np up to 64]
+ * stack), under the same contract.  The fp32 paths never pay for either. */
 int matgcn_prepared_bytes(const matgcn_dims* dims, size_t* bytes);
 int matgcn_workspace_bytes(const matgcn_dims* dims, size_t* bytes);
 
@@ -393,12 +397,30 @@ int matgcn_prepare_join(void* stream);
  * Both are NARROWER than the reference's fp32 arithmetic: measured max-normalised deviation from the fp32 path <= 3e-3
  * (mode 1) at N = 403 (tests/test_hip_parity.py::test_bf16_mix_variant holds both modes to 5e-3).  Governs
  * matgcn_forward / matgcn_forward_series only: matgcn_prepare and the unit entry points always use fp32 operands, the
- * training entry points follow matgcn_set_train_precision.  Returns the previous setting; 0 (default) = fp32; any other
- * value means 0. */
+ * training entry points follow matgcn_set_train_precision.
+ * matgcn_set_mix_precision(3) ("bf16x3"): fp32 ACCURACY on the bf16 matrix instruction.  Every graph mix of
+ * matgcn_forward / matgcn_forward_series - the recurrent step's two, the layer-0 fold, the hoisted x-part chunks - splits
+ * both operands into three bf16 pieces, x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid),
+ * and accumulates the six leading piece products (hi.lo, lo.hi, mid.mid, hi.mid, mid.hi, hi.hi, smallest first) in fp32 on
+ * v_mfma_f32_16x16x32_bf16, with partial sums every 256 reduction indices past 1 024 nodes like the fp32 kernel.  Dropped:
+ * mid.lo, lo.mid and lo.lo, each at most about 2^-24 relative.  The support stack is split once per forward into three
+ * planes in the workspace (see matgcn_workspace_bytes), the state rows on their way into LDS.  Inputs, outputs, the
+ * recurrent state, the node-wise contractions, the residual cell, matgcn_prepare, the unit entry points and everything in
+ * memory stay fp32; modes 0, 1 and 2 keep their kernels and their bits.  Every mix of the two forwards has a mode-3
+ * kernel (one 64 x 128 tile shape at every batch and graph size, odd batch sizes and the small batches of the fp32 path's
+ * 64 x 32 tiles included), so no shape of the forwards falls back to an fp32 mix.  Training is out of scope:
+ * matgcn_set_train_precision(3) means 0, so the backward's 32 x 128 and 64 x 64 transposed-mix tiles never see the mode.
+ * Measured gap to the reference's float64 prediction (MI355X, tests/test_bf16x3.py, the bound is twice the reference's
+ * own fp32-vs-float64 gap): bm403_out24 (N = 403, B = 4) worst element 3.87e-7, r.m.s. 4.91e-8 - the reference's own
+ * fp32 run 4.45e-7 / 6.15e-8; synth4096_out24 (N = 4096, B = 2, partial sums) 2.66e-7 / 4.19e-8 - reference 4.69e-7 /
+ * 5.83e-8.  At the seven shape-edge fixtures 4.1e-7 .. 6.4e-7 max-normalised from the float64 oracle (the fp32 path:
+ * 4.0e-7 .. 8.2e-7; tolerance 1e-4).  Measured speed at Baltimore 403 / B = 64: step mix 33.0 us against 38.8 of the
+ * fp32 kernel, forward 5.61 ms against 6.38.
+ * Returns the previous setting; 0 (default) = fp32; any value other than 1, 2, 3 means 0. */
 int matgcn_set_mix_precision(int mode);
 
-/* The same modes for the training entry points (matgcn_forward_train, matgcn_backward); 0 (default) = fp32, any other
- * value means 0; returns the previous setting.  The two settings are independent (a model can train in bf16 and
+/* Modes 1 and 2 for the training entry points (matgcn_forward_train, matgcn_backward); 0 (default) = fp32, any other
+ * value - 3 included: the three-piece mode is inference only - means 0; returns the previous setting.  The two settings are independent (a model can train in bf16 and
  * evaluate in fp32).
  *   matgcn_forward_train runs the kernels of the inference forward of that mode - mode >= 1: bf16 operands for the
  *   graph mixes (the mixed rows it saves for the weight gradients are their fp32 outputs); mode 2: also for the

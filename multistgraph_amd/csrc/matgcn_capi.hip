@@ -54,6 +54,13 @@ struct Plan {
   long oSeq[MATGCN_MAX_LAYERS], oGX[MATGCN_MAX_LAYERS], oPX[MATGCN_MAX_LAYERS];
   long workspaceFloats;
   long workspaceFloatsBf16;   // with the bf16 weight-stream copies of precision mode 2 behind everything else
+  // precision mode 3: the three bf16 planes of the support stack (k_split_bf16x3), behind workspaceFloats as well - no
+  // call runs in two modes, so the two tails may share their floats.  INVARIANT: nothing behind workspaceFloats outlives
+  // the call that wrote it - a mode-2 forward / forward_train rebuilds its W16 copies before it reads them, a mode-3
+  // forward its planes.  A change that keeps either across calls must give the two tails floats of their own.
+  int nKg;                    // k-groups of 8 reduction indices, Np rounded up to 32
+  long oPlanes, planeWords;   // first float of the planes; 16-byte words per plane
+  long workspaceFloatsX3;
 };
 
 int make_plan(const matgcn_dims* D, Plan* P) {
@@ -164,6 +171,10 @@ int make_plan(const matgcn_dims* D, Plan* P) {
     P->oW16x[l] = (l > 0 && !P->gcnOff) ? take(((long)P->N * P->wxStride + 1) / 2) : 0;
   }
   P->workspaceFloatsBf16 = o;
+  P->nKg = (int)(rup(P->Np, 32) / 8);
+  P->planeWords = (long)P->nKg * P->Mp;
+  P->oPlanes = P->workspaceFloats;
+  P->workspaceFloatsX3 = P->workspaceFloats + rup(3 * 4 * P->planeWords, 64);
   return MATGCN_OK;
 }
 
@@ -405,7 +416,8 @@ int prep_wait(hipStream_t s, int which) {
 #define g_wf (wf_current())
 int g_wavefront_mode = 1;     // matgcn_set_wavefront: 0 serial, 1 free-running chains
 int g_mix_precision = 0;      // matgcn_set_mix_precision: 0 fp32 operands, 1 bf16 operands for the inference graph mixes,
-                              // 2 bf16 operands for the graph mixes AND the node-wise contractions (bf16 weight streams)
+                              // 2 bf16 operands for the graph mixes AND the node-wise contractions (bf16 weight streams),
+                              // 3 three bf16 pieces per operand of the graph mixes (fp32 accuracy on the bf16 pipe)
 int g_train_precision = 0;    // matgcn_set_train_precision: the same values for matgcn_forward_train / matgcn_backward
 // The backward follows the mode its forward_train ran with: forward_train notes (device, train buffer) -> mode here and
 // matgcn_backward looks its train buffer up (a buffer without an entry runs with the current setting).  The last
@@ -563,12 +575,16 @@ StackMap build_stack_map(const Plan& P, const matgcn_dims* D, const matgcn_param
   return map;
 }
 
-// Which operands of a call are bf16: `mix` - the graph mixes (transposed ones in the backward), `node` - the node-wise
+// The operands of a call: `mix` - of the graph mixes (transposed ones in the backward): fp32, rounded to bf16, or split
+// into three bf16 pieces (inference forwards only: the training setting never holds 3); `node` - bf16 for the node-wise
 // contractions (bf16 copies of the weight streams).  The four hot entry points read their mode once, on entry
 // (matgcn_forward / matgcn_forward_series: g_mix_precision; matgcn_forward_train: g_train_precision; matgcn_backward:
 // the mode of its forward_train), and every launch helper below them reads it from the context it is handed.
-struct Precision { bool mix = false, node = false; };
-inline Precision precision_of(int mode) { return Precision{mode >= 1, mode == 2}; }   // modes of matgcn_set_*_precision
+enum MixPrec { MIX_F32 = 0, MIX_BF16 = 1, MIX_BF16X3 = 3 };
+struct Precision { MixPrec mix = MIX_F32; bool node = false; };
+inline Precision precision_of(int mode) {   // modes of matgcn_set_*_precision
+  return Precision{mode == 3 ? MIX_BF16X3 : mode >= 1 ? MIX_BF16 : MIX_F32, mode == 2};
+}
 
 struct Ctx {
   Plan P;
@@ -651,62 +667,82 @@ int launch_node(const NodeVariant (&table)[n], int mode, bool save, int rows, bo
 
 // Every instantiation of the graph-mix kernels (matgcn_kernels.hip, section 5), once; every launch of one goes through
 // launch_mix_variant.  Selectors: tile - the workgroup's output tile, rows x columns (MixArgs counts column tiles of 64:
-// a 64 x 32 tile is half of one, a 32 x 128 tile a pair); bf - bf16 operands; flush - k_mix's FLUSH; role - 0 pre-passes
-// and Chebyshev products, 1 the recurrent step's mix (the roofline kernel), 2 the backward's transposed mixes.
+// a 64 x 32 tile is half of one, a 32 x 128 or 64 x 128 tile a pair); prec - the operands (MixPrec); flush - partial sums
+// every 256 reduction indices; role - 0 pre-passes and Chebyshev products, 1 the recurrent step's mix (the roofline
+// kernel), 2 the backward's transposed mixes.
 struct MixTile { int rows, cols; };
-constexpr MixTile MIX_64x64{64, 64}, MIX_64x32{64, 32}, MIX_32x128{32, 128};
-struct MixVariant { MixTile tile; bool bf, flush; int role; void (*fn)(MixArgs); };
+constexpr MixTile MIX_64x64{64, 64}, MIX_64x32{64, 32}, MIX_32x128{32, 128}, MIX_64x128{64, 128};
+struct MixVariant { MixTile tile; MixPrec prec; bool flush; int role; void (*fn)(MixArgs); };
 const MixVariant MIX[] = {
-    {MIX_64x64, false, false, 0, k_mix<0>},          {MIX_64x64, false, false, 1, k_mix<1>},
-    {MIX_64x64, false, false, 2, k_mix<2>},          {MIX_64x64, false, true, 0, k_mix<0, true>},
-    {MIX_64x64, false, true, 1, k_mix<1, true>},     {MIX_64x32, false, false, 0, k_mix_c32<0>},
-    {MIX_64x32, false, false, 1, k_mix_c32<1>},      {MIX_32x128, false, false, 2, k_mix_n32<false>},
-    {MIX_32x128, true, false, 2, k_mix_n32<true>},   {MIX_64x64, true, false, 0, k_mix_bf16<0>},
-    {MIX_64x64, true, false, 1, k_mix_bf16<1>},      {MIX_64x64, true, false, 2, k_mix_bf16<2>},
+    {MIX_64x64, MIX_F32, false, 0, k_mix<0>},            {MIX_64x64, MIX_F32, false, 1, k_mix<1>},
+    {MIX_64x64, MIX_F32, false, 2, k_mix<2>},            {MIX_64x64, MIX_F32, true, 0, k_mix<0, true>},
+    {MIX_64x64, MIX_F32, true, 1, k_mix<1, true>},       {MIX_64x32, MIX_F32, false, 0, k_mix_c32<0>},
+    {MIX_64x32, MIX_F32, false, 1, k_mix_c32<1>},        {MIX_32x128, MIX_F32, false, 2, k_mix_n32<false>},
+    {MIX_32x128, MIX_BF16, false, 2, k_mix_n32<true>},   {MIX_64x64, MIX_BF16, false, 0, k_mix_bf16<0>},
+    {MIX_64x64, MIX_BF16, false, 1, k_mix_bf16<1>},      {MIX_64x64, MIX_BF16, false, 2, k_mix_bf16<2>},
+    // three bf16 pieces per operand: the inference forward's mixes (roles 0 and 1), every batch size and graph size
+    {MIX_64x128, MIX_BF16X3, false, 0, k_mix_bf16x3<0>}, {MIX_64x128, MIX_BF16X3, false, 1, k_mix_bf16x3<1>},
+    {MIX_64x128, MIX_BF16X3, true, 0, k_mix_bf16x3<0, true>},
+    {MIX_64x128, MIX_BF16X3, true, 1, k_mix_bf16x3<1, true>},
 };
 // launches the table's entry for the selectors over `rows` output rows: grid.x = row tiles x column units of the entry's
-// tile shape, grid.y = a.parts; a combination without an entry is an error, never another variant
-int launch_mix_variant(MixTile tile, bool bf, bool flush, int role, MixArgs a, int rows, hipStream_t s) {
+// tile shape (k_mix_bf16x3 alone takes an odd number of column tiles in pairs: rounded up), grid.y = a.parts; a
+// combination without an entry is an error, never another variant
+int launch_mix_variant(MixTile tile, MixPrec prec, bool flush, int role, MixArgs a, int rows, hipStream_t s) {
   const MixVariant* v = find_variant(MIX, [&](auto& e) {
-    return e.tile.rows == tile.rows && e.tile.cols == tile.cols && e.bf == bf && e.flush == flush && e.role == role; });
+    return e.tile.rows == tile.rows && e.tile.cols == tile.cols && e.prec == prec && e.flush == flush && e.role == role; });
   if (!v) return MATGCN_ERR_UNSUPPORTED;
   a.nRowTiles = (rows + tile.rows - 1) / tile.rows;
-  const dim3 grid((unsigned)(a.nRowTiles * (a.nColTiles * 64 / tile.cols)), (unsigned)a.parts);
+  const dim3 grid((unsigned)(a.nRowTiles * ((a.nColTiles * 64 + tile.cols - 1) / tile.cols)), (unsigned)a.parts);
   hipLaunchKernelGGL(v->fn, grid, dim3(256), 0, s, a);
   return launch_ok();
 }
 
 // The forward's shape rules.  The opt-in bf16-operand variant of the inference forward (fp32 accumulate, fp32 in / out)
-// wins over both: there is no FLUSH and no 64 x 32 tile in bf16, past 1 024 nodes included.
+// wins over both: there is no FLUSH and no 64 x 32 tile in bf16, past 1 024 nodes included.  The three-piece variant
+// claims fp32 accuracy and keeps the partial sums; its one tile is 64 x 128 at every batch size.
 // more than 1 024 reduction indices: partial sums every 256 (k_mix's FLUSH)
-inline bool mix_flush(bool bf16, const MixArgs& a) { return !bf16 && a.nK > 64; }
+inline bool mix_flush(MixPrec prec, const MixArgs& a) { return prec != MIX_BF16 && a.nK > 64; }
 // small batches (the reference ships batch_size 16): twice the workgroups of half the width, up to 16 column tiles
 // (batch rows of a step mix) - round 4, BM 403: B = 16 20.8 -> 18.1 us per launch, forward 3.69 -> 3.56 ms; B = 32 no
 // gain per launch and the forward 2 % SLOWER; DC 237 at B = 16 unchanged: profiles/r04_small_batch_lab.log
-inline bool mix_half_tiles(bool bf16, const MixArgs& a) {
-  return !bf16 && !mix_flush(bf16, a) && a.nColTiles <= 16 && a.xTileStride % 4 == 0 && a.ldX >= 64;
+inline bool mix_half_tiles(MixPrec prec, const MixArgs& a) {
+  return prec == MIX_F32 && !mix_flush(prec, a) && a.nColTiles <= 16 && a.xTileStride % 4 == 0 && a.ldX >= 64;
+}
+// the three-piece kernel reads St from its planes and fetches the state rows two columns at a time (8-byte loads): every
+// mix of the forward has even strides, and one that had not is an error, never another kernel
+inline bool mix_x3_ok(const MixArgs& a) { return a.Apl != nullptr && a.xTileStride % 2 == 0 && a.ldX % 2 == 0; }
+
+// the graph-mix operands of a forward: the call's Precision::mix, the support stack St [Np][Mp] and, in MIX_BF16X3, its
+// three bf16 planes in the workspace (split_supports)
+struct MixOps { MixPrec prec; const float* St; const void* planes; };
+inline MixOps mix_ops(const Ctx& c) {
+  return MixOps{c.prec.mix, c.prep + c.P.oSt, c.prec.mix == MIX_BF16X3 ? c.ws + c.P.oPlanes : nullptr};
 }
 
-// out[(k,n)][col] = sum_m S_k[n][m] X[m][col]; see k_mix.  bf16: the call's Precision::mix
-int launch_mix(const Plan& P, bool bf16, const float* St, const float* X, long xTileStride, int ldX, int nColTiles,
+// out[(k,n)][col] = sum_m S_k[n][m] X[m][col]; see k_mix
+int launch_mix(const Plan& P, const MixOps& m, const float* X, long xTileStride, int ldX, int nColTiles,
                float* out, long sN, long sK, long sT, int Ks, int rowsM, hipStream_t s, bool stepRole = false,
                long outFloats = 0) {
   if (Ks <= 0 || rowsM <= 0) return MATGCN_OK;   // every support folded away: nothing to mix
   MixArgs a;
-  a.St = St; a.ldS = P.Mp; a.X = X; a.xTileStride = xTileStride; a.ldX = ldX;
+  a.St = m.St; a.ldS = P.Mp; a.X = X; a.xTileStride = xTileStride; a.ldX = ldX;
+  a.Apl = m.planes; a.plStride = P.planeWords;
   a.out = out; a.sN = sN; a.sK = sK; a.sT = sT; a.outFloats = outFloats;
   a.Np = P.Np; a.N = P.N; a.Ks = Ks; a.nK = P.Np / 16; a.nColTiles = nColTiles;
   ProfScope prof(stepRole ? MATGCN_PROF_MIX : MATGCN_PROF_MIX_PRE, s);
-  return launch_mix_variant(mix_half_tiles(bf16, a) ? MIX_64x32 : MIX_64x64, bf16, mix_flush(bf16, a), stepRole ? 1 : 0, a,
-                            rowsM, s);
+  const MixPrec prec = m.prec;
+  if (prec == MIX_BF16X3 && !mix_x3_ok(a)) return MATGCN_ERR_UNSUPPORTED;
+  const MixTile tile = prec == MIX_BF16X3 ? MIX_64x128 : mix_half_tiles(prec, a) ? MIX_64x32 : MIX_64x64;
+  return launch_mix_variant(tile, prec, mix_flush(prec, a), stepRole ? 1 : 0, a, rowsM, s);
 }
 
 // mix of `rows` contiguous [Np][64] slabs into the node-major buffer G [N][rows][Ks][64]
 // (nodeStride: floats between the nodes of G when the `rows` rows are a slice of a larger node-major block)
-int mix_rows(const Plan& P, bool bf16, const float* St, const float* X, int rows, float* G, hipStream_t s, bool stepRole = false,
+int mix_rows(const Plan& P, const MixOps& m, const float* X, int rows, float* G, hipStream_t s, bool stepRole = false,
              long nodeStride = 0) {
   const long sN = nodeStride ? nodeStride : (long)rows * P.Ks * H;
-  return launch_mix(P, bf16, St, X, (long)P.Np * H, H, rows, G, sN, H, (long)P.Ks * H, P.Ks, P.Ks * P.Np, s, stepRole,
+  return launch_mix(P, m, X, (long)P.Np * H, H, rows, G, sN, H, (long)P.Ks * H, P.Ks, P.Ks * P.Np, s, stepRole,
                     (long)(P.N - 1) * sN + (long)rows * P.Ks * H);
 }
 
@@ -730,14 +766,13 @@ int node_kernels_ready(int ldsBytes) {
 int fold_x0(const Ctx& c, const float* xin, int Tq, hipStream_t s) {
   const Plan& P = c.P;
   const int rows = P.B * Tq;
-  const float* St = c.prep + P.oSt;
   const int ld = (int)rup((long)rows * P.C0, 64);
   float* X0m = c.ws + P.oX0m;
   float* MX0 = c.ws + P.oMX0;
   hipLaunchKernelGGL(k_x0_to_matrix, dim3(blocks_for((size_t)P.Np * ld)), dim3(256), 0, s, xin, X0m, rows, P.Np, P.C0,
                      ld);
   CHECK_LAUNCH();
-  RETURN_IF(launch_mix(P, c.prec.mix, St, X0m, 64, ld, ld / 64, MX0, (long)ld, (long)P.Np * ld, 64, P.Ks, P.Ks * P.Np, s));
+  RETURN_IF(launch_mix(P, mix_ops(c), X0m, 64, ld, ld / 64, MX0, (long)ld, (long)P.Np * ld, 64, P.Ks, P.Ks * P.Np, s));
   hipLaunchKernelGGL(k_build_xa0, dim3(blocks_for((size_t)Tq * P.N * P.B * P.Kx)), dim3(256), 0, s, xin, MX0,
                      c.ws + P.oXA0, P.B, Tq, P.N, P.Np, P.C0, P.Ks, P.Kx, ld);
   return launch_ok();
@@ -762,7 +797,7 @@ int hoist_x(const Ctx& c, int l, const float* xin, int t0, int nt, hipStream_t s
   float* GX = (c.train ? c.train + c.R.oGX[l] : c.ws + P.oGX[l]) + (size_t)t0 * P.N * P.B * P.Ks * H;
   if (mixedSteps < nt) {
     const int r0 = mixedSteps * P.B;
-    RETURN_IF(mix_rows(P, c.prec.mix, c.prep + P.oSt, xin + (size_t)mixedSteps * P.B * P.Np * H, rows - r0,
+    RETURN_IF(mix_rows(P, mix_ops(c), xin + (size_t)mixedSteps * P.B * P.Np * H, rows - r0,
                        GX + (size_t)r0 * P.Ks * H, s, false, mixedSteps ? (long)rows * P.Ks * H : 0));
   }
   Px16Args a;
@@ -814,7 +849,6 @@ void fill_res_args(const Ctx& c, int l, const float* xt, long xRowStride, const 
 int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Args* res, hipStream_t s,
                bool zeroState = false) {
   const Plan& P = c.P;
-  const float* St = c.prep + P.oSt;
   float* Hx = c.ws + P.oHx[l];
   float* ZHx = c.ws + P.oZHx[l];
   float* G = c.ws + P.oG[l];
@@ -828,8 +862,8 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
   if (!shared && c.train && res && !(phase < 2 && sharesUp))
     G = c.train + (phase < 2 ? c.R.oGH[l] : c.R.oGZH[l]) + (size_t)t * P.N * P.B * P.Ks * H;
   float* R = c.ws + P.oR[l];
-  if (phase == 0) return mix_rows(P, c.prec.mix, St, Hx, P.B, G, s, true, gNodeStride);
-  if (phase == 2) return mix_rows(P, c.prec.mix, St, ZHx, P.B, G, s, true);
+  if (phase == 0) return mix_rows(P, mix_ops(c), Hx, P.B, G, s, true, gNodeStride);
+  if (phase == 2) return mix_rows(P, mix_ops(c), ZHx, P.B, G, s, true);
   Node16Args a;
   memset(&a, 0, sizeof(a));
   a.g = G; a.gNodeStride = phase == 1 ? gNodeStride : 0; a.rows = P.B; a.N = P.N; a.Np = P.Np; a.Ks = P.Ks;
@@ -932,6 +966,14 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
         CHECK_LAUNCH();
       }
     }
+  }
+  if (c.prec.mix == MIX_BF16X3 && P.Ks > 0) {
+    if (c.wsBytes < (size_t)P.workspaceFloatsX3 * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;   // sized without mode 3
+    // precision mode 3: the support stack into its three bf16 planes, once per forward and in front of the fork (every
+    // chain's mixes read them; matgcn_prepare has finished St before it returns, lazy or not)
+    hipLaunchKernelGGL(k_split_bf16x3, dim3(blocks_for((size_t)P.planeWords)), dim3(256), 0, c.s, c.prep + P.oSt, P.Mp, P.Np,
+                       P.nKg, reinterpret_cast<uint4*>(c.ws + P.oPlanes), P.planeWords);
+    CHECK_LAUNCH();
   }
   if (multi) {
     HIP_OK(hipEventRecord(W.fork, c.s));
@@ -1235,7 +1277,7 @@ int matgcn_series_violations(int64_t* count, int reset) {
 
 int matgcn_set_mix_precision(int mode) {
   const int prev = g_mix_precision;
-  g_mix_precision = (mode == 1 || mode == 2) ? mode : 0;
+  g_mix_precision = (mode == 1 || mode == 2 || mode == 3) ? mode : 0;
   return prev;
 }
 
@@ -1283,7 +1325,9 @@ int matgcn_workspace_bytes(const matgcn_dims* dims, size_t* bytes) {
   Plan P;
   RETURN_IF(make_plan(dims, &P));
   const bool bf16Streams = g_mix_precision == 2 || g_train_precision == 2;
-  *bytes = (size_t)(bf16Streams ? P.workspaceFloatsBf16 : P.workspaceFloats) * sizeof(float);
+  long floats = bf16Streams ? P.workspaceFloatsBf16 : P.workspaceFloats;
+  if (g_mix_precision == 3 && P.workspaceFloatsX3 > floats) floats = P.workspaceFloatsX3;   // the planes of mode 3
+  *bytes = (size_t)floats * sizeof(float);
   return MATGCN_OK;
 }
 
@@ -1371,7 +1415,7 @@ static int prepare_impl(const matgcn_dims* dims, const matgcn_params* params, vo
     int iPrev1 = 0, iPrev2 = -1;
     for (int k = 2; k < dims->cheb_k; ++k) {
       const int iOut = (iPrev2 < 0) ? 1 : 3 - iPrev1 - iPrev2;
-      RETURN_IF(launch_mix(P, false, St + col0, buf[iPrev1], 64, P.NpC, P.NpC / 64, buf[iOut], (long)P.NpC, 0, 64, 1, P.Np,
+      RETURN_IF(launch_mix(P, MixOps{MIX_F32, St + col0, nullptr}, buf[iPrev1], 64, P.NpC, P.NpC / 64, buf[iOut], (long)P.NpC, 0, 64, 1, P.Np,
                            c.s));
       hipLaunchKernelGGL(k_cheb_combine, tgrid, dim3(256), 0, c.s, buf[iOut], iPrev2 < 0 ? nullptr : buf[iPrev2],
                          iPrev2 < 0 ? 1 : 0, P.N, P.NpC, St, P.Mp, (slot0 + k - 1) * P.Np, buf[iOut]);

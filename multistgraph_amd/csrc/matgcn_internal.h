@@ -83,6 +83,10 @@ struct MixArgs {
   // of X and writes its own partial result - the transposed mix of the backward splits by support slot
   int parts = 1;
   long aPartStride = 0, xPartStride = 0, outPartStride = 0;
+  // k_mix_bf16x3 only (behind every field the other kernels read, whose argument offsets stay): the three bf16 planes of
+  // St, each [Np32 / 8][ldS] 16-byte words of 8 consecutive reduction indices (k_split_bf16x3), plStride words apart
+  const void* Apl = nullptr;
+  long plStride = 0;
 };
 
 struct HeadArgs {

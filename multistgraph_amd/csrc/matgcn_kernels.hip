@@ -1229,6 +1229,181 @@ __global__ __launch_bounds__(256) void k_mix_bf16(MixArgs a) {
                  colTile, wc * 32);
 }
 
+// -------------------------------------------------------------------------------------------------
+// 5c. the same graph mix as THREE bf16 pieces per operand (matgcn_set_mix_precision(3)): fp32 accuracy on the bf16 pipe
+// -------------------------------------------------------------------------------------------------
+// x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid) (both differences are exact in fp32;
+// the three pieces carry 24 significand bits).  S.X is the sum of nine piece products; the six leading ones - hi.lo,
+// lo.hi, mid.mid, hi.mid, mid.hi, hi.hi, issued in that order: smallest first - are accumulated in fp32 on
+// v_mfma_f32_16x16x32_bf16, the three dropped ones (mid.lo, lo.mid, lo.lo) are at most about 2^-24 relative each.
+// Workgroup tile 64 rows x 128 columns (a PAIR of column tiles, as k_mix_n32: half the St bytes per output of the 64-wide
+// kernels), 4 waves of 32 rows x 64 columns = 2 x 4 accumulators; K-tile 32 = 4 k-groups of 8 consecutive reduction indices,
+// one 16-byte word per (piece, k-group, row or column), which is exactly a lane's MFMA fragment: one ds_read_b128,
+// conflict-free (the 16 lanes of a read group take 16 consecutive words of one 256-byte bank row or two disjoint runs of them).
+//   A: St is split ONCE per forward by k_split_bf16x3 into three planes of such words in the workspace; staging is a copy.
+//   B: the state rows stay fp32 in memory (the node kernels and their bits are untouched); a thread fetches 8 k x 2 columns
+//      of the next K-tile into registers while the current one is multiplied and splits them on their way into LDS
+//      (v_cvt_pk_bf16_f32: 11 vector instructions per two values).
+// LDS 36 KB per workgroup, ONE buffer (two barriers per K-tile); the next tile waits in registers.  Registers, not LDS,
+// set the occupancy: 136 of 512 (164 with FLUSH) let three workgroups share a CU and cover each other's barriers, and a
+// second buffer (3 x 72 KB > 160 KB) would cost the third.  An odd number of column tiles: the last pair's second half is fetched
+// from the first (clamped) and not stored.  FLUSH as k_mix: partial sums every 8 K-tiles (256 reduction indices), N > 1024.
+// Tile order and the store epilogue are the shared ones (mix_tile_order, mix_store_tile: twice per wave, 32 columns each).
+typedef __bf16 bf16x2v_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned int pack_bf16_pair(float lo, float hi) {    // round to nearest even, lo in bits 0..15
+  const bf16x2v_t v = {(__bf16)lo, (__bf16)hi};
+  return __builtin_bit_cast(unsigned int, v);
+}
+// pieces of (x0, x1) as three packed words
+__device__ __forceinline__ void split_bf16x3(float x0, float x1, unsigned int& h, unsigned int& m, unsigned int& l) {
+  h = pack_bf16_pair(x0, x1);
+  x0 -= __uint_as_float(h << 16); x1 -= __uint_as_float(h & 0xffff0000u);
+  m = pack_bf16_pair(x0, x1);
+  x0 -= __uint_as_float(m << 16); x1 -= __uint_as_float(m & 0xffff0000u);
+  l = pack_bf16_pair(x0, x1);
+}
+
+// St [Np][ldS] -> planes[piece][Np32 / 8][ldS] words; reduction indices >= Np read as zero
+__global__ __launch_bounds__(256) void k_split_bf16x3(const float* __restrict__ St, int ldS, int Np, int nKg,
+                                                      uint4* __restrict__ planes, long plStride) {
+  const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (id >= (size_t)nKg * ldS) return;
+  const int kg = (int)(id / ldS), col = (int)(id - (size_t)kg * ldS);
+  unsigned int h[4], m[4], l[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int k0 = 8 * kg + 2 * i, k1 = k0 + 1;
+    const float x0 = k0 < Np ? St[(size_t)k0 * ldS + col] : 0.f;
+    const float x1 = k1 < Np ? St[(size_t)k1 * ldS + col] : 0.f;
+    split_bf16x3(x0, x1, h[i], m[i], l[i]);
+  }
+  planes[id] = make_uint4(h[0], h[1], h[2], h[3]);
+  planes[plStride + id] = make_uint4(m[0], m[1], m[2], m[3]);
+  planes[2 * plStride + id] = make_uint4(l[0], l[1], l[2], l[3]);
+}
+
+template <int ROLE, bool FLUSH = false>
+__global__ __launch_bounds__(256) void k_mix_bf16x3(MixArgs a) {
+  __shared__ __attribute__((aligned(16))) u32x4 As[3][4][64];     // [piece][k-group][row]
+  __shared__ __attribute__((aligned(16))) u32x4 Bs[3][4][128];    // [piece][k-group][column]
+  int colPair, rowTile;
+  mix_tile_order(blockIdx.x, (a.nColTiles + 1) >> 1, a.nRowTiles, rowTile, colPair);
+  const int row0 = rowTile * 64;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wr = w >> 1, wc = w & 1, j = lane & 15, kq = lane >> 4;
+  const int kLast = 16 * a.nK - 1;                         // reduction indices 0 .. Np-1 (a.nK = Np / 16)
+  const int nT = (a.nK + 1) >> 1;                          // K-tiles of 32
+  // staging: k-group skg of the tile; A row sr (one word per piece), B columns 2 sr, 2 sr + 1 of the 128
+  const int skg = tid >> 6, sr = tid & 63;
+  const u32x4* ap = reinterpret_cast<const u32x4*>(a.Apl) + (size_t)skg * a.ldS + row0 + sr;
+  const int bcol = 2 * sr;
+  const int bTile = min(2 * colPair + (bcol >> 6), a.nColTiles - 1);
+  const float* bp = a.X + (size_t)bTile * a.xTileStride + (bcol & 63);
+  u32x4 ra[3];
+  float2 rb[8];
+  auto load = [&](int t) {
+    const int tc = min(t, nT - 1);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) ra[p] = ap[(size_t)p * a.plStride + (size_t)tc * 4 * a.ldS];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      // (a reduction index past the last one repeats the last row: its St words are zero in every plane)
+      rb[i] = *reinterpret_cast<const float2*>(bp + (size_t)min(32 * tc + 8 * skg + i, kLast) * a.ldX);
+    }
+  };
+  auto store = [&]() {
+#pragma unroll
+    for (int p = 0; p < 3; ++p) As[p][skg][sr] = ra[p];
+    unsigned int h0[4], m0[4], l0[4], h1[4], m1[4], l1[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      split_bf16x3(rb[2 * i].x, rb[2 * i + 1].x, h0[i], m0[i], l0[i]);
+      split_bf16x3(rb[2 * i].y, rb[2 * i + 1].y, h1[i], m1[i], l1[i]);
+    }
+    Bs[0][skg][bcol] = u32x4{h0[0], h0[1], h0[2], h0[3]};
+    Bs[0][skg][bcol + 1] = u32x4{h1[0], h1[1], h1[2], h1[3]};
+    Bs[1][skg][bcol] = u32x4{m0[0], m0[1], m0[2], m0[3]};
+    Bs[1][skg][bcol + 1] = u32x4{m1[0], m1[1], m1[2], m1[3]};
+    Bs[2][skg][bcol] = u32x4{l0[0], l0[1], l0[2], l0[3]};
+    Bs[2][skg][bcol + 1] = u32x4{l1[0], l1[1], l1[2], l1[3]};
+  };
+  load(0);
+  store();
+  load(1);
+  __syncthreads();
+  f32x4 acc[2][2][2], tot[FLUSH ? 2 : 1][4];   // acc[q >> 1][p][q & 1]: a half is one call of the store epilogue
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      acc[q >> 1][p][q & 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (FLUSH) tot[p][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  auto fragA = [&](int piece, int p) { return __builtin_bit_cast(bf16x8v_t, As[piece][kq][wr * 32 + p * 16 + j]); };
+  auto fragB = [&](int piece, int q) { return __builtin_bit_cast(bf16x8v_t, Bs[piece][kq][wc * 64 + q * 16 + j]); };
+  auto mma = [&]() {
+    bf16x8v_t fa[3][2];
+#pragma unroll
+    for (int piece = 0; piece < 3; ++piece)
+#pragma unroll
+      for (int p = 0; p < 2; ++p) fa[piece][p] = fragA(piece, p);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bf16x8v_t bh = fragB(0, q), bm = fragB(1, q), bl = fragB(2, q);
+      // smallest terms first; the two row blocks alternate so that consecutive MFMAs are independent
+#pragma unroll
+      for (int p = 0; p < 2; ++p) acc[q >> 1][p][q & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0][p], bl, acc[q >> 1][p][q & 1], 0, 0, 0);
+#pragma unroll
+      for (int p = 0; p < 2; ++p) acc[q >> 1][p][q & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2][p], bh, acc[q >> 1][p][q & 1], 0, 0, 0);
+#pragma unroll
+      for (int p = 0; p < 2; ++p) acc[q >> 1][p][q & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1][p], bm, acc[q >> 1][p][q & 1], 0, 0, 0);
+#pragma unroll
+      for (int p = 0; p < 2; ++p) acc[q >> 1][p][q & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0][p], bm, acc[q >> 1][p][q & 1], 0, 0, 0);
+#pragma unroll
+      for (int p = 0; p < 2; ++p) acc[q >> 1][p][q & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1][p], bh, acc[q >> 1][p][q & 1], 0, 0, 0);
+#pragma unroll
+      for (int p = 0; p < 2; ++p) acc[q >> 1][p][q & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0][p], bh, acc[q >> 1][p][q & 1], 0, 0, 0);
+    }
+  };
+  for (int t = 0; t < nT; ++t) {
+    mma();                       // tile t
+    __syncthreads();             // every wave has read tile t
+    if (t + 1 < nT) {
+      store();                   // tile t+1
+      load(t + 2);               // (clamped past the end: unused)
+    }
+    __syncthreads();
+    if constexpr (FLUSH) {
+      if (((t + 1) & (MIX_FLUSH_TILES / 2 - 1)) == 0) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) tot[p][q][e] += acc[q >> 1][p][q & 1][e];
+            acc[q >> 1][p][q & 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+      }
+    }
+  }
+  if constexpr (FLUSH) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[q >> 1][p][q & 1][e] += tot[p][q][e];
+  }
+  // the wave's 32 x 64 tile lies in ONE column tile: two passes of the shared epilogue through the wave's 4 KB of Bs
+  // (free after the loop's last barrier)
+  const int colTile = 2 * colPair + wc;
+  if (colTile < a.nColTiles) {
+    float* stg = reinterpret_cast<float*>(&Bs[0][0][0]) + w * 1024;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) mix_store_tile(a, 0, stg, acc[half], row0 + wr * 32, colTile, half * 32);
+  }
+}
+
 // =================================================================================================
 // 8. output head (MultiATGCN.py:416-418): Conv2d(T -> out*od, (1,H)) == [B*N x T*H] . [T*H x CH]
 // =================================================================================================

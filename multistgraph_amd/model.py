@@ -113,7 +113,8 @@ def _is_series_batch(batch) -> bool:
     return isinstance(batch, dict) and "label_start" in batch and "series" in batch
 
 
-HIP_PRECISIONS = {"fp32": 0, "bf16_mix": 1, "bf16": 2}   # config['hip_precision'] -> matgcn_set_*_precision mode
+# config['hip_precision'] -> matgcn_set_*_precision mode ("bf16x3": an inference mode - the training setting reads 3 as 0)
+HIP_PRECISIONS = {"fp32": 0, "bf16_mix": 1, "bf16": 2, "bf16x3": 3}
 
 
 def _precision_mode(name) -> int:
@@ -165,9 +166,11 @@ class MultiATGCN(AbstractTrafficStateModel):
         self.fnn_off = get("fnn_off", False)
         self.gcn_off = get("gcn_off", False)
         # operand precision of the HIP kernels (not a reference key): "fp32" (default) | "bf16_mix" (bf16 operands for the
-        # graph mixes) | "bf16" (also for the node-wise contractions); fp32 accumulation and fp32 state, parameters and
-        # gradients in every mode.  Applies to this model's inference forwards and training steps; an attribute, so a
-        # model can train in bf16 and evaluate in fp32 by reassigning it.
+        # graph mixes) | "bf16" (also for the node-wise contractions) | "bf16x3" (the graph mixes of the inference forwards
+        # from three bf16 pieces per operand: fp32 accuracy on the bf16 matrix instruction; training steps of such a model
+        # run in fp32); fp32 accumulation and fp32 state, parameters and gradients in every mode.  Applies to this model's
+        # inference forwards and training steps; an attribute, so a model can train in bf16 and evaluate in fp32 by
+        # reassigning it.
         self.hip_precision = get("hip_precision", "fp32")
         _precision_mode(self.hip_precision)
         self.batch_size = get("batch_size", 64)

@@ -315,7 +315,8 @@ class HotPath:
         self._train = None
         self.train_generation = 0
         self.grad_bucket: Optional[torch.Tensor] = None   # flat buffer the gradients of the LAST backward() are views of
-        # precision mode of this binding's calls (1 bf16 graph mixes, 2 + bf16 node-wise contractions, 0 fp32): the
+        # precision mode of this binding's calls (1 bf16 graph mixes, 2 + bf16 node-wise contractions, 3 graph mixes of the
+        # inference forwards from three bf16 pieces - the training setter reads it as 0 -, 0 fp32): the
         # library settings are process-global, so every call sets the one it needs and restores the previous value
         # (matgcn_set_mix_precision for the inference forwards, matgcn_set_train_precision for the training step).
         # None (default): the calls leave the settings as they are - whatever the process set, fp32 unless it did.
@@ -332,8 +333,8 @@ class HotPath:
 
     def _with_workspace(self, call, what: str, train: bool = False) -> None:
         """Run ``call(ws_ptr, ws_bytes)``; a workspace that is too small for the CURRENT library mode - precision mode 2
-        was switched on after this binding sized it: the bf16 weight-stream copies are counted only while that mode is
-        set - is re-sized once and the call repeated (train: the train buffer too - matgcn_train_bytes counts the bf16
+        or 3 was switched on after this binding sized it: the bf16 weight-stream copies (mode 2) and the three bf16 planes
+        of the support stack (mode 3) are counted only while their mode is set - is re-sized once and the call repeated (train: the train buffer too - matgcn_train_bytes counts the bf16
         copies of the plain weights while training precision mode 2 is set)."""
         ws, wsb = self._ws()
         status = call(ws, wsb)
