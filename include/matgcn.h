@@ -29,6 +29,8 @@
  * non-zero value now selects the wavefront); matgcn_workspace_bytes no longer counts two half-batch plans.
  * Still ABI 12: matgcn_set_mix_precision(3) (three bf16 pieces per operand of the graph mixes) is one more value of an
  * existing argument - no symbol, signature or struct changed, and every value ABI 12 defined keeps its meaning and bits.
+ * Still ABI 12: matgcn_set_deterministic is one more symbol - no existing symbol, signature or struct changed, and with
+ * the setting at its default (0) matgcn_train_bytes and matgcn_backward are what ABI 12 defined.
  */
 #ifndef MATGCN_H
 #define MATGCN_H
@@ -298,7 +300,8 @@ int matgcn_metric_table(const double* sums, int out_steps, int swap_r2, double* 
  * drop_mask: NULL (eval-mode forward), or the training-mode dropout in front of end_conv (MultiATGCN.py:416,
  * F.dropout p = 0.1) as a (B, T, N, H) device tensor of multipliers 0 or 1/(1-p) drawn by the caller's RNG
  * (torch: F.dropout(torch.ones(B,T,N,H))); the same mask goes to the matching matgcn_backward.
- * Reductions that meet in one address use fp32 atomics: gradients are reproducible to rounding, not bitwise.
+ * Reductions that meet in one address: by default fp32 atomics - gradients are reproducible to rounding, not bitwise;
+ * with matgcn_set_deterministic(1) in a fixed order - gradients are bit-identical from run to run (see there).
  * With gcn_off the dense cells' nn.Linear gradients come back in res_gate / res_update (as their weights go in);
  * with fnn_off drop_mask is (B, 1, N, H). */
 typedef struct matgcn_agcn_grads {
@@ -442,6 +445,40 @@ int matgcn_set_mix_precision(int mode);
  * backward on a train buffer without them returns MATGCN_ERR_SMALL_BUFFER.  Measured gap to the reference's autograd: <= 1.4e-2 max-normalised per gradient tensor
  * (tests/test_train_precision.py holds both modes to 2.7e-2; figures in DESIGN.md section 5). */
 int matgcn_set_train_precision(int mode);
+
+/* ---- deterministic backward --------------------------------------------------------------------------------------
+ * matgcn_set_deterministic(1): every sum of matgcn_backward that several workgroups (or waves) form together is added
+ * in a fixed order, so the gradients (d_h0 included) are bit-identical from run to run for the same inputs, buffers
+ * and library settings - matgcn_set_wavefront(0) and (1) included: they give the same bits.  Returns the previous
+ * setting; 0 (default) = fp32 atomics, today's kernels and speed; any non-zero value = on.  Governs matgcn_backward
+ * only and is read when matgcn_backward is called; independent of both precision settings (training precision modes
+ * 0, 1, 2 change operands, not reductions).
+ * How each site is ordered:
+ *   slabs - each contributor stores its partial sum with plain stores into a slab of its own, indexed by its position
+ *   in the grid, and ONE kernel (k_ordered_reduce) adds the slabs in ascending index into the destination: the split
+ *   GEMMs (residual nn.Linear weights with their bias rows, head weight, adjacency fallback, pools -> embedding), the
+ *   adjacency-gradient tile kernels (at most 16 slices), the pool -> embedding product (a slab per wave), the embedding
+ *   gradient (a slab per stack entry) and its stack gains, the narrow residual weight blocks and the column sums (at
+ *   most 256 workgroups), the head-fusion gains, the blend scalars (a float per workgroup and step, one reduction per
+ *   layer behind its chain);
+ *   one contributor - the node weight-gradient kernels (dWp, dBias, the narrow row streams) and the per-node column
+ *   sums run one workgroup per node over all steps, so nothing meets in memory;
+ *   stream order - launches that accumulate one after the other (time steps, layers, beta = 1 GEMMs) were ordered
+ *   already; the accumulations that cross the library's streams (dT and node_emb over the layers) are tied by events
+ *   in both schedules, in the same layer order.  Layer 0's fused two-channel residual kernel is replaced by its two
+ *   separate kernels, which both schedules then share.
+ * Scratch: the slabs live in the caller's `train` buffer, behind everything else the call's mode uses.
+ * matgcn_train_bytes counts them while the setting is on; a deterministic matgcn_backward on a buffer sized without
+ * them returns MATGCN_ERR_SMALL_BUFFER (ask again and re-allocate).  Size, in floats, each term rounded up to 64:
+ *   2 * A + L * T * W,   W = max(ceil(B/64) * N, ceil(B*Np/64), 512) workgroups of a chain kernel,
+ *   A = max(16 N^2, 256*128*max(C0,64) + 256*128, 16*hT*CH*64, 32*E*N*d, E*N*d + 64*E*ceil(N*d/256),
+ *           256*192*max(C0,16), 256*256, 8*ceil(T*N*od/256)),   E = stack entries + 4
+ * - one arena A per stream that runs reductions (the chains' and the weight gradients'), shared by all sites of that
+ * stream and all layers: a site's slabs are reduced, in stream order, before the next site writes.  Nothing is
+ * allocated by the library.  Measured at Baltimore 403 / B = 64 (MI355X, tools/train_step.py --deterministic, DESIGN.md
+ * section 5c): 20 887 040 bytes of slabs; backward 14.3 ms against 13.8 (+3.6 %), training step 22.0 ms against 21.7
+ * (+1.7 %); the default path as fast as before the switch existed.  No single site dominates the added time. */
+int matgcn_set_deterministic(int enabled);
 
 /* ---- measurement hooks (bench.py; not on the hot path) ---------------------------------------
  * Time individual kernel launches in situ with HIP events recorded on the caller's stream.

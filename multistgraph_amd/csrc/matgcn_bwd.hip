@@ -153,7 +153,66 @@ struct Bwd {
   const matgcn_series* src = nullptr;   // series mode: X rows are gathered from the raw series
   bool hasH0 = false;     // the forward started from a caller-supplied state (its padded copy sits at tr + R.oH0)
   float* dH0 = nullptr;   // (L, B, N, H) gradient w.r.t. that state, or null
+  // deterministic mode (matgcn_set_deterministic; null = fp32 atomics): the arena of this context's stream for the
+  // partial slabs of its ordered reductions (TrainPlan::detArena floats), and the start of the deterministic tail
+  float* det = nullptr;
+  float* detTail = nullptr;
 };
+
+// dst[b][r][c] (= or +=) the `parts` compact slabs at part + p * stride, added in ascending p (k_ordered_reduce)
+int ordered_reduce(float* dst, const float* part, int parts, long stride, int nb, int rows, int cols, long ldd, long bDst,
+                   bool accumulate, hipStream_t s) {
+  const long n = (long)nb * rows * cols;
+  if (n <= 0 || parts <= 0) return MATGCN_OK;
+  ReduceArgs a;
+  a.dst = dst; a.part = part; a.stride = stride; a.ldd = ldd; a.bDst = bDst;
+  a.parts = parts; a.nb = nb; a.rows = rows; a.cols = cols; a.accumulate = accumulate ? 1 : 0;
+  a.vec = (cols & 3) == 0 && (ldd & 3) == 0 && (bDst & 3) == 0 && (stride & 3) == 0 &&
+          ((reinterpret_cast<size_t>(dst) | reinterpret_cast<size_t>(part)) & 15) == 0;
+  hipLaunchKernelGGL(k_ordered_reduce, dim3(blocks_for((size_t)(a.vec ? n / 4 : n))), dim3(256), 0, s, a);
+  return launch_ok();
+}
+// a flat vector of n floats
+int ordered_reduce(float* dst, const float* part, int parts, long stride, long n, bool accumulate, hipStream_t s) {
+  if (n >= (1L << 31)) return MATGCN_ERR_UNSUPPORTED;
+  return ordered_reduce(dst, part, parts, stride, 1, 1, (int)n, n, 0, accumulate, s);
+}
+
+// A mode-1 GEMM (sum split over workgroups that meet in C).  Default: gemm().  Deterministic mode: the parts store
+// compact slabs [part][b1][M][N] into the context's arena and k_ordered_reduce adds them into C in part order; the
+// split is narrowed until no part is empty, and to maxSplit where the caller bounds the slab count.
+int gemm_split(const Bwd& b, GemmArgs g, int nb1, int role, int maxSplit = 0) {
+  if (!b.det || g.mode != 1) return gemm(g, nb1, b.c.s, role);
+  if (g.M <= 0 || g.N <= 0 || g.K <= 0 || g.K2 <= 0 || nb1 <= 0) return MATGCN_OK;
+  if (g.nb2 != 1 || g.sCn != 1 || (g.nOff && nb1 > 8)) return MATGCN_ERR_UNSUPPORTED;
+  const long total = (long)g.K2 * ((g.K + BG_KT - 1) / BG_KT);
+  long split = g.split;
+  if (maxSplit > 0 && split > maxSplit) split = maxSplit;
+  if (split > total) split = total;
+  for (;;) {   // every part gets tiles: the empty ones of an uneven cut would leave their colsum rows unwritten
+    const long per = (total + split - 1) / split, used = (total + per - 1) / per;
+    if (used == split) break;
+    split = used;
+  }
+  g.split = (int)split;
+  const long slab = (long)nb1 * g.M * g.N, need = split * slab + (g.colsumA ? split * g.M : 0);
+  if (need > b.c.R.detArena) return MATGCN_ERR_UNSUPPORTED;
+  long bDst = g.bC1;
+  float* C = g.C;
+  if (g.nOff) {   // offset tables: equally spaced is all the reducer takes
+    bDst = nb1 > 1 ? g.offC[1] - g.offC[0] : 0;
+    for (int q = 0; q < nb1; ++q)
+      if (g.offC[q] != g.offC[0] + q * bDst) return MATGCN_ERR_UNSUPPORTED;
+    C += g.offC[0];
+  }
+  g.part = b.det;
+  float* bias = g.colsumA;
+  if (bias) g.colPart = b.det + split * slab;
+  RETURN_IF(gemm(g, nb1, b.c.s, role));
+  RETURN_IF(ordered_reduce(C, g.part, (int)split, slab, nb1, g.M, g.N, g.sCm, bDst, true, b.c.s));
+  if (bias && g.colPart) RETURN_IF(ordered_reduce(bias, g.colPart, (int)split, g.M, g.M, true, b.c.s));
+  return MATGCN_OK;
+}
 
 // the stack entries whose weights come out of the pools: kept slots first, then the folded diagonal ones (which share
 // the identity slot); with cheb_order = 1 several entries alias pool index 0 (StackMap)
@@ -316,6 +375,7 @@ bool node_wgrad_fast(const Bwd& b, const float* U, const StepBlocks& sb, const f
   // mostly empty last one - at BM (403 nodes, 24 steps): 4 x 403 = 3.1 rounds of 512, 5 x 403 = 2.6 rounds of 768
   const int parts = O == 128 ? 4 : 5;
   a.stepsPerPart = P.T >= 8 ? (P.T + parts - 1) / parts : P.T;
+  if (b.det) a.stepsPerPart = P.T;   // deterministic mode: one workgroup per node walks every step - nothing meets in dW / dBias
   const dim3 grid((unsigned)P.N, (unsigned)((P.T + a.stepsPerPart - 1) / a.stepsPerPart));
   const size_t lds = (size_t)2 * WG_KT * ((S * 64 + 16) + (O + 16)) * sizeof(float);
   hipLaunchKernelGGL(v->fn, grid, dim3((unsigned)(S * O)), lds, b.c.s, a);
@@ -339,15 +399,30 @@ int adaptive_grad(const Bwd& b, const float* dA, const float* U, int rows, int C
       int split = (int)(1280 / (tiles * tiles));
       if (split < 1) split = 1;
       if (split > rows) split = rows;
+      q.part = nullptr;
+      if (b.det) {   // slices that all hold row blocks, each into a slab of its own, added in slice order
+        if (split > DET_ADJ_SPLIT) split = DET_ADJ_SPLIT;
+        for (;;) {
+          const int per = (rows + split - 1) / split, used = (rows + per - 1) / per;
+          if (used == split) break;
+          split = used;
+        }
+        if ((long)split * P.N * P.N > b.c.R.detArena) return MATGCN_ERR_UNSUPPORTED;
+        q.part = b.det;
+      }
       hipLaunchKernelGGL(k_adj_grad, dim3(tiles, tiles, (unsigned)split), dim3(256), 0, b.c.s, q);
       CHECK_LAUNCH();
+      if (b.det) RETURN_IF(ordered_reduce(q.dT, b.det, split, (long)P.N * P.N, (long)P.N * P.N, true, b.c.s));
       continue;
     }
     if (nodeMajor && Cc == 2 && rows % 8 == 0) {   // layer 0's two-channel x part: dedicated small kernel
       const unsigned t32 = (unsigned)((P.N + 31) / 32);
+      if (b.det && 8L * P.N * P.N > b.c.R.detArena) return MATGCN_ERR_UNSUPPORTED;
       hipLaunchKernelGGL(k_adj_grad_narrow2, dim3(t32, t32, 2), dim3(256), 0, b.c.s, dA + slot, U, rows, P.N, P.Np, 2,
-                         dT + (size_t)j * P.N * P.N);
+                         dT + (size_t)j * P.N * P.N, b.det);
       CHECK_LAUNCH();
+      if (b.det)   // a slab per wave: 2 workgroup slices x 4 waves
+        RETURN_IF(ordered_reduce(dT + (size_t)j * P.N * P.N, b.det, 8, (long)P.N * P.N, (long)P.N * P.N, true, b.c.s));
       continue;
     }
     GemmArgs g = gemm_args(dA + slot, U, dT + (size_t)j * P.N * P.N, P.N, P.N, Cc);
@@ -357,7 +432,7 @@ int adaptive_grad(const Bwd& b, const float* dA, const float* U, int rows, int C
     g.sBk = 1; g.sBn = Cc; g.sBk2 = (long)P.Np * Cc;
     g.sCm = P.N; g.sCn = 1;
     g.mode = 1; g.split = 48;
-    RETURN_IF(gemm(g, 1, b.c.s, BG_ADJ));
+    RETURN_IF(gemm_split(b, g, 1, BG_ADJ, DET_ADJ_SPLIT));
   }
   return MATGCN_OK;
 }
@@ -373,7 +448,38 @@ int linear_weight_grad(const Bwd& b, const float* dPre, int O, const float* In, 
   g.sCm = I; g.sCn = 1;
   g.mode = 1; g.split = 256;
   if (bias && tn_eligible(g)) { g.colsumA = bias; *biasDone = true; }
-  return gemm(g, 1, b.c.s, BG_LINEAR);
+  return gemm_split(b, g, 1, BG_LINEAR);
+}
+
+// out[o] += column sums of src over rows and real nodes (k_colsum_all; `blocks` workgroups meet in out - in deterministic
+// mode at most DET_GRID of them, each with a row of its own that k_ordered_reduce adds in order)
+int colsum_all(const Bwd& b, int blocks, const float* src, size_t rows, int O, int Opad, float* out) {
+  const Plan& P = b.c.P;
+  if (b.det) {
+    if (blocks > DET_GRID) blocks = DET_GRID;
+    if ((long)blocks * O > b.c.R.detArena) return MATGCN_ERR_UNSUPPORTED;
+  }
+  hipLaunchKernelGGL(k_colsum_all, dim3((unsigned)blocks), dim3(256), 0, b.c.s, src, rows, P.N, P.Np, O, Opad, out, b.det);
+  CHECK_LAUNCH();
+  if (b.det) RETURN_IF(ordered_reduce(out, b.det, blocks, O, O, true, b.c.s));
+  return MATGCN_OK;
+}
+
+// the x-column blocks of the residual nn.Linear weight gradients of a narrow input (k_res_wgrad_narrow): grid-sized,
+// the workgroups meet in dRU / dRG - in deterministic mode each in a slab [192][C] of its own, added in grid order
+int res_wgrad_narrow(const Bwd& b, const ResNarrowVariant* v, int blocks, const float* dpu2, const float* dpg2,
+                     const float* x, int C, int I, float* dRU, float* dRG, long rows) {
+  if (b.det) {
+    if (blocks > DET_GRID) blocks = DET_GRID;
+    if ((long)blocks * 192 * C > b.c.R.detArena) return MATGCN_ERR_UNSUPPORTED;
+  }
+  hipLaunchKernelGGL(v->wgrad, dim3((unsigned)blocks), dim3(256), 0, b.c.s, dpu2, dpg2, x, I, dRU, dRG, rows, b.det);
+  CHECK_LAUNCH();
+  if (b.det) {
+    RETURN_IF(ordered_reduce(dRU, b.det, blocks, 192L * C, 1, 64, C, I, 0, true, b.c.s));
+    RETURN_IF(ordered_reduce(dRG, b.det + 64 * C, blocks, 192L * C, 1, 128, C, I, 0, true, b.c.s));
+  }
+  return MATGCN_OK;
 }
 
 // ---- one backward pass: what its stages share ---------------------------------------------------------------
@@ -540,9 +646,7 @@ int bwd_head(Pass& pass, const float* dOut) {
   CHECK_LAUNCH();
   auto pad_pow2 = [](int v) { int p2 = 1; while (p2 < v) p2 <<= 1; return p2; };
   RETURN_IF(zero_async(g->end_conv_bias, P.CH, s));
-  hipLaunchKernelGGL(k_colsum_all, dim3(256), dim3(256), 0, s, dOutRows, (size_t)B, N, Np, P.CH, pad_pow2(P.CH),
-                     g->end_conv_bias);
-  CHECK_LAUNCH();
+  RETURN_IF(colsum_all(b, 256, dOutRows, (size_t)B, P.CH, pad_pow2(P.CH), g->end_conv_bias));
   const float* seqTop = b.dropMask ? tr + R.oSeqDrop : c.ws + P.oSeq[P.L - 1];   // what the head convolved
   float* dSeq = tr + R.oDSeq[0];
   {
@@ -570,7 +674,7 @@ int bwd_head(Pass& pass, const float* dOut) {
     w.sBk = H; w.sBn = 1; w.sBk2 = (long)Np * H; w.bB1 = slab;
     w.sCm = (long)hT * H; w.sCn = 1; w.bC1 = H;
     w.mode = 1; w.split = 16;
-    RETURN_IF(gemm(w, hT, hs, BG_HEAD));
+    RETURN_IF(gemm_split(hs == s ? b : bw, w, hT, BG_HEAD));
   }
 
   return MATGCN_OK;
@@ -649,10 +753,8 @@ int bwd_dense_layer(Pass& pass, const LayerBufs& L) {
     RETURN_IF(linear_weight_grad(b, DPU2, 64, Z2H, H, rows, I, C, gu.weight));
     RETURN_IF(zero_async(gg.bias, 128, s));
     RETURN_IF(zero_async(gu.bias, 64, s));
-    hipLaunchKernelGGL(k_colsum_all, dim3(1024), dim3(256), 0, s, DPG2, (size_t)rowsTB, N, Np, 128, 128, gg.bias);
-    CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_colsum_all, dim3(1024), dim3(256), 0, s, DPU2, (size_t)rowsTB, N, Np, 64, 64, gu.bias);
-    CHECK_LAUNCH();
+    RETURN_IF(colsum_all(b, 1024, DPG2, (size_t)rowsTB, 128, 128, gg.bias));
+    RETURN_IF(colsum_all(b, 1024, DPU2, (size_t)rowsTB, 64, 64, gu.bias));
   }
   return MATGCN_OK;
 }
@@ -733,6 +835,7 @@ int bwd_chain(Pass& pass, const LayerBufs& L) {
     a.dh = DH; a.dr = tr + R.oDR[par];
     a.B = B; a.N = N; a.Np = Np; a.S = S;
     a.mixParts = P.Ks > 1 ? P.Ks : 1; a.mixPartStride = slab;     // the transposed mixes arrive split by slot
+    if (b.det) { a.dblendPart = b.detTail + R.oDetBlend[l] + t; a.dblendStride = T; }   // [workgroup][t], reduced below
     const dim3 eg(blocks_for((size_t)slab));
     if (twoStreams && l + 1 < P.L) {
       // step t reads the gradient of its output - x columns of the chunk of the layer above that holds t: awaited on
@@ -797,6 +900,11 @@ int bwd_chain(Pass& pass, const LayerBufs& L) {
       if (twoStreams) HIP_OK(hipEventRecord(g_wf.bxcol[l][t], pass.xs));
     }
   }
+  if (b.det) {   // the blend-scalar gradients of all T steps: the workgroups' shares in grid order
+    const long wgs = P.Ks > 1 && P.Ks > MAX_FUSED_PARTS ? ((long)B * Np + 63) / 64 : (long)((B + 63) / 64) * N;
+    if (wgs > R.detBlendWgs) return MATGCN_ERR_UNSUPPORTED;
+    RETURN_IF(ordered_reduce(g->weights_gru + (size_t)l * T, b.detTail + R.oDetBlend[l], (int)wgs, T, T, false, s));
+  }
   if (b.dH0) {   // what step 0 would carry into a step before it: dh + slot 0 of the gate AGCN's dA + its transposed mix
     hipLaunchKernelGGL(k_dh0_out, dim3(blocks_for((size_t)B * N * H)), dim3(256), 0, s, DH, DAg, P.Ks > 0 ? MixOut : nullptr,
                        P.Ks > 1 ? P.Ks : 1, (long)slab, b.dH0 + (size_t)l * B * N * H, B, N, Np, S);
@@ -809,7 +917,11 @@ inline bool prep_hoisted(const Pass& pass, int l) { return pass.twoStreams && l 
 // layer 0 with two input channels: bwd_x_columns takes the x-column blocks of the residual nn.Linear weight gradients
 // along (k_res_narrow2).  It reads the time-major input, which exists that early only when the operands were prepared at
 // the start of the backward (event auxDone on the second stream).
-inline bool res_narrow_fused(const Pass& pass, const LayerBufs& L) { return L.narrow && L.C == 2 && prep_hoisted(pass, L.l); }
+// (Not in deterministic mode: the fused kernel exists with two streams only, and its x columns add in another order than
+// k_res_xcol_narrow's - both schedules run the separate pair there, so that they agree bit for bit.)
+inline bool res_narrow_fused(const Pass& pass, const LayerBufs& L) {
+  return L.narrow && L.C == 2 && prep_hoisted(pass, L.l) && !pass.b.det;
+}
 
 // x columns of both AGCNs and of the residual cell -> gradient of the layer's input sequence
 int bwd_x_columns(Pass& pass, const LayerBufs& L) {
@@ -870,7 +982,8 @@ int bwd_x_columns(Pass& pass, const LayerBufs& L) {
     RETURN_IF(zero_async(gu.weight, 64L * I, s));
     const float* Xall = tr + R.oX0tm;
     const dim3 grid((unsigned)((rrows + 15) / 16 < 2048 ? (rrows + 15) / 16 : 2048));
-    hipLaunchKernelGGL(k_res_narrow2, grid, dim3(256), 0, s, DPU2, DPG2, RU, RG, Xall, I, dXall, gu.weight, gg.weight, rrows);
+    hipLaunchKernelGGL(k_res_narrow2, grid, dim3(256), 0, s, DPU2, DPG2, RU, RG, Xall, I, dXall, gu.weight, gg.weight, rrows,
+                       (float*)nullptr);
     CHECK_LAUNCH();
   } else if (const ResNarrowVariant* v = res_narrow_variant(C)) {   // of a narrow input: one pass over the 192 gradients per row
     const dim3 grid((unsigned)((rrows + 15) / 16 < 4096 ? (rrows + 15) / 16 : 4096));
@@ -920,9 +1033,8 @@ int bwd_layer_other_grads(Pass& pass, const LayerBufs& L, const Bwd& bx, const f
   if (resNarrowFused) {
     // (done by k_res_narrow2 in bwd_x_columns)
   } else if (const ResNarrowVariant* v = res_narrow_variant(C)) {   // both x-column blocks in one pass over the residual cell's gradients
-    const dim3 grid((unsigned)((rows + 15) / 16 < 1024 ? (rows + 15) / 16 : 1024));
-    hipLaunchKernelGGL(v->wgrad, grid, dim3(256), 0, xs, DPU2, DPG2, Xall, I, gu.weight, gg.weight, rows);
-    CHECK_LAUNCH();
+    RETURN_IF(res_wgrad_narrow(bx, v, (int)((rows + 15) / 16 < 1024 ? (rows + 15) / 16 : 1024), DPU2, DPG2, Xall, C, I,
+                               gu.weight, gg.weight, rows));
   } else {
     RETURN_IF(linear_weight_grad(bx, DPG2, 128, Xall, C, rows, I, 0, gg.weight));
     RETURN_IF(linear_weight_grad(bx, DPU2, 64, Xall, C, rows, I, 0, gu.weight));
@@ -930,12 +1042,10 @@ int bwd_layer_other_grads(Pass& pass, const LayerBufs& L, const Bwd& bx, const f
   RETURN_IF(linear_weight_grad(bx, DPG2, 128, HA, H, rows, I, C, gg.weight, gg.bias, &biasG));
   RETURN_IF(linear_weight_grad(bx, DPU2, 64, Z2HA, H, rows, I, C, gu.weight, gu.bias, &biasU));
   if (!biasG) {   // (the rows of the padding nodes are zero in DPG2 / DPU2: summing them with the operand stream is exact)
-    hipLaunchKernelGGL(k_colsum_all, dim3(1024), dim3(256), 0, xs, DPG2, (size_t)rowsTB, N, Np, 128, 128, gg.bias);
-    CHECK_LAUNCH();
+    RETURN_IF(colsum_all(bx, 1024, DPG2, (size_t)rowsTB, 128, 128, gg.bias));
   }
   if (!biasU) {
-    hipLaunchKernelGGL(k_colsum_all, dim3(1024), dim3(256), 0, xs, DPU2, (size_t)rowsTB, N, Np, 64, 64, gu.bias);
-    CHECK_LAUNCH();
+    RETURN_IF(colsum_all(bx, 1024, DPU2, (size_t)rowsTB, 64, 64, gu.bias));
   }
   return MATGCN_OK;
 }
@@ -984,7 +1094,8 @@ int bwd_layer_weights(Pass& pass, const LayerBufs& L, bool tailOnMain) {
   const long ldx = rup((long)rowsTB * P.C0, 64);
   const NarrowVariant* nv = l == 0 ? narrow_variant(P.C0, S) : nullptr;   // x rows of layer 0: a dedicated kernel (see below)
   auto narrow_wgrad = [&](hipStream_t on) {
-    const dim3 grid((unsigned)N, nv->mfma ? WNM_PARTS : WN_PARTS), block(nv->mfma ? 256 : 192 * WN_GROUPS);
+    // (deterministic mode: one workgroup per node - its row groups / waves meet in LDS in a fixed order, nothing meets in dWp)
+    const dim3 grid((unsigned)N, b.det ? 1 : (nv->mfma ? WNM_PARTS : WN_PARTS)), block(nv->mfma ? 256 : 192 * WN_GROUPS);
     hipLaunchKernelGGL(nv->wgrad, grid, block, 0, on, Xall, c.ws + P.oMX0, ldx, DPG, DPU, dWpG, dWpU, T, B, N, Np, I);
   };
   bool narrowOnMain = false;
@@ -1076,12 +1187,12 @@ int bwd_layer_weights(Pass& pass, const LayerBufs& L, bool tailOnMain) {
     }
   }
   if (!fastH) {   // (k_wgrad_node summed the columns of the rows it streamed; the GEMM path needs the extra pass)
-    hipLaunchKernelGGL(k_node_colsum, dim3(blocks_for((size_t)N * 128), 24), dim3(256), 0, ws, DPG, (size_t)rowsTB, N,
+    hipLaunchKernelGGL(k_node_colsum, dim3(blocks_for((size_t)N * 128), b.det ? 1 : 24), dim3(256), 0, ws, DPG, (size_t)rowsTB, N,
                        Np, 128, tr + R.oDBias[l][0]);
     CHECK_LAUNCH();
   }
   if (!fastZ) {
-    hipLaunchKernelGGL(k_node_colsum, dim3(blocks_for((size_t)N * 64), 24), dim3(256), 0, ws, DPU, (size_t)rowsTB, N, Np,
+    hipLaunchKernelGGL(k_node_colsum, dim3(blocks_for((size_t)N * 64), b.det ? 1 : 24), dim3(256), 0, ws, DPU, (size_t)rowsTB, N, Np,
                        64, tr + R.oDBias[l][1]);
     CHECK_LAUNCH();
   }
@@ -1113,9 +1224,14 @@ int bwd_fuse_heads(Pass& pass) {
     }
     a.B = B; a.T = T; a.N = N; a.Np = Np; a.C0 = P.C0; a.od = P.od; a.F = D->x_feat; a.xSteps = D->x_steps;
     a.startDim = D->start_dim; a.nHeads = D->n_heads; a.nTs = D->n_ts;
-    hipLaunchKernelGGL(k_fuse_heads_bwd, dim3(blocks_for((size_t)T * N * P.od), (unsigned)D->n_heads), dim3(256), 0, s,
-                       a);
+    const unsigned fblocks = blocks_for((size_t)T * N * P.od);
+    if (b.det) {
+      if ((long)fblocks * D->n_heads > R.detArena) return MATGCN_ERR_UNSUPPORTED;
+      a.dgainPart = b.det;
+    }
+    hipLaunchKernelGGL(k_fuse_heads_bwd, dim3(fblocks, (unsigned)D->n_heads), dim3(256), 0, s, a);
     CHECK_LAUNCH();
+    if (b.det) RETURN_IF(ordered_reduce(dgain, b.det, (int)fblocks, D->n_heads, D->n_heads, false, s));
     hipLaunchKernelGGL(k_softmax_bwd_small, dim3(1), dim3(64), 0, s, prm->weight_tsg, dgain, D->n_ts, g->weight_tsg);
     CHECK_LAUNCH();
   }
@@ -1131,6 +1247,8 @@ int bwd_pools_layer(Pass& pass, int l, hipStream_t onStream) {
   float* EK = tr + R.oEK; float* FK = tr + R.oFK; float* TmpK = tr + R.oTmpK; float* dgain = tr + R.oDPoolGain;
   const int Kt = P.KtotOrig;
   if (P.gcnOff) return MATGCN_OK;
+  const Bwd& bp = onStream == pass.ws ? pass.bw : pass.b;   // (deterministic mode: the arena of that stream)
+  float* det = bp.det;
   {
     hipStream_t s = onStream;   // shadows the pass's stream: every launch below goes behind the layer's weight gradients
     for (int part = 0; part < 2; ++part) {
@@ -1158,9 +1276,12 @@ int bwd_pools_layer(Pass& pass, int l, hipStream_t onStream) {
                            ent, N, P.d, IO, S, Kt, ag.weights_pool);
         CHECK_LAUNCH();
         const int splits = 4;
+        if (det && (long)splits * 4 * ent.n * N * P.d > R.detArena) return MATGCN_ERR_UNSUPPORTED;
         hipLaunchKernelGGL(k_pool_emb_mfma, dim3((unsigned)(((N + 15) / 16) * splits), (unsigned)ent.n), dim3(256), 0, s,
-                           dWp, ap.weights_pool, ent, N, P.d, IO, S, Kt, splits, TmpK);
+                           dWp, ap.weights_pool, ent, N, P.d, IO, S, Kt, splits, TmpK, det);
         CHECK_LAUNCH();
+        if (det)   // a slab [entries][N][d] per wave of a split
+          RETURN_IF(ordered_reduce(TmpK, det, splits * 4, (long)ent.n * N * P.d, (long)ent.n * N * P.d, false, s));
       } else if (distinct && ent.n > 0) {
         GemmArgs q = gemm_args(EK, dWp, ag.weights_pool, P.d, (int)IO, N);
         q.sAm = 1; q.sAk = P.d; q.sBk = (long)S * IO; q.sBn = 1; q.sCm = (long)Kt * IO; q.sCn = 1;
@@ -1173,7 +1294,7 @@ int bwd_pools_layer(Pass& pass, int l, hipStream_t onStream) {
           e.offA[e2] = (long)ent.slot[e2] * IO; e.offB[e2] = (long)ent.pool[e2] * IO; e.offC[e2] = (long)e2 * N * P.d;
         }
         RETURN_IF(gemm(q, ent.n, s, BG_POOL));
-        RETURN_IF(gemm(e, ent.n, s, BG_POOL));
+        RETURN_IF(gemm_split(bp, e, ent.n, BG_POOL));
       }
       bool written[MATGCN_MAX_STACK] = {false};
       for (int e2 = 0; e2 < ent.n && !distinct; ++e2) {
@@ -1187,11 +1308,19 @@ int bwd_pools_layer(Pass& pass, int l, hipStream_t onStream) {
         GemmArgs e = gemm_args(src, ap.weights_pool + (size_t)k * IO, TmpK + (size_t)e2 * N * P.d, N, P.d, (int)IO);
         e.sAm = (long)S * IO; e.sAk = 1; e.sBk = 1; e.sBn = (long)Kt * IO; e.sCm = P.d; e.sCn = 1;
         e.mode = 1; e.split = 32;
-        RETURN_IF(gemm(e, 1, s, BG_POOL));
+        RETURN_IF(gemm_split(bp, e, 1, BG_POOL));
       }
-      hipLaunchKernelGGL(k_emb_grad, dim3(blocks_for((size_t)N * P.d), (unsigned)ent.n), dim3(256), 0, s, TmpK, FK,
-                         prm->node_emb, wg, Kt, ent, N, P.d, g->node_emb, dgain);
+      const unsigned eblocks = blocks_for((size_t)N * P.d);
+      const long nd = (long)N * P.d;
+      float* detGain = det ? det + ent.n * nd : nullptr;   // behind the entries' slabs [entries][N][d]
+      if (det && ent.n * nd + (long)ent.n * eblocks * Kt > R.detArena) return MATGCN_ERR_UNSUPPORTED;
+      hipLaunchKernelGGL(k_emb_grad, dim3(eblocks, (unsigned)ent.n), dim3(256), 0, s, TmpK, FK,
+                         prm->node_emb, wg, Kt, ent, N, P.d, g->node_emb, dgain, det, detGain);
       CHECK_LAUNCH();
+      if (det && ent.n > 0) {   // the entries in stack order, the workgroups' gain rows in (entry, workgroup) order
+        if (g->node_emb) RETURN_IF(ordered_reduce(g->node_emb, det, ent.n, nd, nd, true, s));
+        RETURN_IF(ordered_reduce(dgain, detGain, (int)(ent.n * eblocks), Kt, Kt, false, s));
+      }
       if (D->scale_by_g) {
         hipLaunchKernelGGL(k_softmax_bwd_small, dim3(1), dim3(64), 0, s, ap.weights_g, dgain, Kt, ag.weights_g);
         CHECK_LAUNCH();
@@ -1284,8 +1413,12 @@ int backward_impl(Bwd& b, const float* dOut) {
   q.ws = q.twoStreams ? g_wf.chain[1] : q.s;
   q.bw = b;
   q.bw.c.s = q.ws;
+  if (b.detTail) {   // deterministic mode: an arena of partial slabs per stream that runs reductions (TrainPlan::detArena)
+    q.b.det = b.detTail + R.oDetArena[0];
+    q.bw.det = b.detTail + R.oDetArena[1];
+  }
   q.xs = q.twoStreams ? g_wf.xcol : q.s;
-  q.bx = b;
+  q.bx = q.b;
   q.bx.c.s = q.xs;
   // 4 x-column chunks per sequence (2 / 8 / 12 measured: 16.3-16.4 / 16.4 / 16.2 ms against 16.1)
   q.chunk = P.T >= 8 ? (P.T + 4 - 1) / 4 : P.T;
@@ -1371,7 +1504,8 @@ int matgcn_train_bytes(const matgcn_dims* dims, size_t* bytes) {
   RETURN_IF(make_plan(dims, &P));
   TrainPlan R;
   RETURN_IF(make_train_plan(P, &R));
-  *bytes = (size_t)(g_train_precision == 2 && !P.gcnOff ? R.floatsBf16 : R.floats) * sizeof(float);
+  *bytes = (size_t)((g_train_precision == 2 && !P.gcnOff ? R.floatsBf16 : R.floats) + (g_deterministic ? R.detFloats : 0)) *
+           sizeof(float);
   return MATGCN_OK;
 }
 
@@ -1480,6 +1614,11 @@ static int backward_entry(const matgcn_dims* dims, const matgcn_params* params, 
   if (mode < 0) return MATGCN_ERR_BAD_ARG;
   if (mode == 2 && !b.c.P.gcnOff && train_bytes < (size_t)b.c.R.floatsBf16 * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;
   b.c.prec = precision_of(mode);
+  if (g_deterministic) {   // the partial slabs of the ordered reductions sit behind everything this call's mode uses
+    const long base = mode == 2 && !b.c.P.gcnOff ? b.c.R.floatsBf16 : b.c.R.floats;
+    if (train_bytes < (size_t)(base + b.c.R.detFloats) * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;
+    b.detTail = b.tr + base;
+  }
   JOINED(backward_impl(b, d_out), stream);
 }
 

@@ -33,6 +33,11 @@ struct GemmArgs {
   long sSm, sSn, bS1, bS2;       // the head, applied where the gradient of the head's input is produced)
   float* colsumA;                // k_bgemm_tn only: [M] += column sums of A over the whole reduction (nn.Linear bias
                                  // gradients: A = the pre-activation gradients), added by the workgroups of column tile 0
+  // deterministic mode (mode 1 only; null = atomics): part p of batch item b1 stores its tile into the compact slab
+  // part[((p * nb1 + b1) * M + m) * N + n] (colPart[p * M + m] for colsumA) with plain stores instead of adding into C;
+  // k_ordered_reduce then adds the slabs in ascending p (nb2 == 1, checked by the launcher)
+  float* part;
+  float* colPart;
 };
 
 #define BG_LD 80   // LDS row pitch (floats): 80 = 16 mod 32, so k and k + 1 sit half a bank row apart
@@ -185,6 +190,8 @@ __global__ __launch_bounds__(256) void k_bgemm(GemmArgs g) {
       }
     }
   }
+  float* slab = (g.mode == 1 && g.part)
+                    ? g.part + ((size_t)part * (gridDim.z / (unsigned)(g.nb2 * g.split)) + b1) * g.M * g.N : nullptr;
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -196,7 +203,8 @@ __global__ __launch_bounds__(256) void k_bgemm(GemmArgs g) {
         float* dst = C + (size_t)m * g.sCm + (size_t)n * g.sCn;
         float v = g.alpha * acc[a][b][e];
         if (g.scaleC) v *= g.scaleC[(size_t)b1 * g.bS1 + (size_t)b2 * g.bS2 + (size_t)m * g.sSm + (size_t)n * g.sSn];
-        if (g.mode == 1) unsafeAtomicAdd(dst, v);
+        if (slab) slab[(size_t)m * g.N + n] = v;
+        else if (g.mode == 1) unsafeAtomicAdd(dst, v);
         else *dst = (g.beta != 0.f) ? v + g.beta * *dst : v;
       }
 }
@@ -297,10 +305,13 @@ __global__ __launch_bounds__(256) void k_bgemm_tn(GemmArgs g) {
         float v = 0.f;
 #pragma unroll
         for (int q = 0; q < 16; ++q) v += As[0][q * 64 + tid];
-        unsafeAtomicAdd(g.colsumA + m0 + tid, v);
+        if (g.colPart) g.colPart[(size_t)part * g.M + m0 + tid] = v;
+        else unsafeAtomicAdd(g.colsumA + m0 + tid, v);
       }
     }
   }
+  float* slab = (g.mode == 1 && g.part)
+                    ? g.part + ((size_t)part * (gridDim.z / (unsigned)(g.nb2 * g.split)) + b1) * g.M * g.N : nullptr;
 #pragma unroll
   for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -310,7 +321,8 @@ __global__ __launch_bounds__(256) void k_bgemm_tn(GemmArgs g) {
         const int m = m0 + wr * 32 + p * 16 + 4 * kq + e, n = n0 + wc * 32 + q * 16 + j;
         float* dst = C + (size_t)m * g.sCm + (size_t)n * g.sCn;
         const float v = g.alpha * acc[p][q][e];
-        if (g.mode == 1) unsafeAtomicAdd(dst, v);
+        if (slab) slab[(size_t)m * g.N + n] = v;
+        else if (g.mode == 1) unsafeAtomicAdd(dst, v);
         else *dst = (g.beta != 0.f) ? v + g.beta * *dst : v;
       }
 }
@@ -570,10 +582,11 @@ __global__ __launch_bounds__(256) void k_pool_grad_mfma(const float* __restrict_
 
 // (2) TmpK[e][n][dd] += sum_io dWp[n][slot(e)][io] * Wpool[dd][pool(e)][io]
 //     A = dWp (rows n, reduction io), B = Wpool^T: both lie K-contiguous, so a lane's float4 is four MFMA steps of its
-//     row (the node kernels' operand trick).  One wave per (entry, 16 nodes, 1/splits of the io range), fp32 atomics.
+//     row (the node kernels' operand trick).  One wave per (entry, 16 nodes, 1/splits of the io range), fp32 atomics
+//     (detPart: one slab per wave instead, added in order by k_ordered_reduce).
 __global__ __launch_bounds__(256) void k_pool_emb_mfma(const float* __restrict__ dWp, const float* __restrict__ wpool,
                                                        StackEntries ent, int N, int d, long IO, int S, int Kt, int splits,
-                                                       float* __restrict__ TmpK) {
+                                                       float* __restrict__ TmpK, float* __restrict__ detPart) {
   const int lane = threadIdx.x & 63, kq = lane >> 4, j = lane & 15;
   const int e = blockIdx.y;
   const int tile = blockIdx.x / splits, part = (blockIdx.x - tile * splits) * 4 + (threadIdx.x >> 6), parts = splits * 4;
@@ -602,14 +615,18 @@ __global__ __launch_bounds__(256) void k_pool_emb_mfma(const float* __restrict__
     acc[0] = MFMA16(a1.z, q0.z, acc[0]); acc[1] = MFMA16(a1.z, q1.z, acc[1]);
     acc[0] = MFMA16(a1.w, q0.w, acc[0]); acc[1] = MFMA16(a1.w, q1.w, acc[1]);
   }
-  if (g0 >= g1) return;
-  float* dst = TmpK + (size_t)e * N * d;
+  if (g0 >= g1 && !detPart) return;
+  // deterministic mode: every part - an empty one too - stores its sums into slab `part` of [parts][entries][N][d]
+  float* dst = detPart ? detPart + ((size_t)part * gridDim.y + e) * N * d : TmpK + (size_t)e * N * d;
 #pragma unroll
   for (int r = 0; r < 2; ++r)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int n = tile * 16 + 4 * kq + q, dd = 16 * r + j;
-      if (n < N && dd < d) unsafeAtomicAdd(dst + (size_t)n * d + dd, acc[r][q]);
+      if (n < N && dd < d) {
+        if (detPart) dst[(size_t)n * d + dd] = acc[r][q];
+        else unsafeAtomicAdd(dst + (size_t)n * d + dd, acc[r][q]);
+      }
     }
 }
 
@@ -650,7 +667,8 @@ __global__ __launch_bounds__(256) void k_bias_pool_grad(const float* __restrict_
 __global__ __launch_bounds__(256) void k_emb_grad(const float* __restrict__ TmpK, const float* __restrict__ FK,
                                                   const float* __restrict__ E, const float* __restrict__ wg, int Kt,
                                                   StackEntries ent, int N, int d, float* __restrict__ dE,
-                                                  float* __restrict__ dgain) {
+                                                  float* __restrict__ dgain, float* __restrict__ detE,
+                                                  float* __restrict__ detGain) {
   __shared__ float red[256];
   const int idx = blockIdx.x * 256 + threadIdx.x;
   const int e = blockIdx.y, k = ent.pool[e];
@@ -658,7 +676,8 @@ __global__ __launch_bounds__(256) void k_emb_grad(const float* __restrict__ TmpK
   if (idx < N * d) {
     const int n = idx / d;
     const float f = FK[(size_t)e * N + n], v = TmpK[(size_t)e * N * d + idx];
-    if (dE) unsafeAtomicAdd(&dE[idx], stack_gain(wg, Kt, k) * f * v);
+    if (detE) detE[(size_t)e * N * d + idx] = stack_gain(wg, Kt, k) * f * v;   // deterministic mode: a slab per entry
+    else if (dE) unsafeAtomicAdd(&dE[idx], stack_gain(wg, Kt, k) * f * v);
     part = f * E[idx] * v;
   }
   red[threadIdx.x] = part;
@@ -666,6 +685,10 @@ __global__ __launch_bounds__(256) void k_emb_grad(const float* __restrict__ TmpK
   for (int s = 128; s > 0; s >>= 1) {
     if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
     __syncthreads();
+  }
+  if (detGain) {   // deterministic mode: a row of Kt floats per (entry, workgroup), zero but for the entry's pool index
+    if ((int)threadIdx.x < Kt) detGain[((size_t)e * gridDim.x + blockIdx.x) * Kt + threadIdx.x] = (int)threadIdx.x == k ? red[0] : 0.f;
+    return;
   }
   if (threadIdx.x == 0 && dgain) unsafeAtomicAdd(&dgain[k], red[0]);
 }
@@ -753,7 +776,13 @@ struct ChainArgs {
   long mixPartStride;    // ... this many floats apart: whoever reads dzhMix / dhMix / carryMix adds them up
   int B, N, Np, S;
   int dense;             // gcn_off: the layer IS a dense GRU cell on (x, h): "ha" is h_{t-1}, no blend (blend == null)
+  float* dblendPart;     // deterministic mode (null = atomics into dblend): workgroup w of the grid's linear order stores
+  long dblendStride;     // its share at dblendPart[w * dblendStride]; k_ordered_reduce adds them in order after the chain
 };
+__device__ __forceinline__ void blend_grad_out(const ChainArgs& a, unsigned wg, float v) {
+  if (a.dblendPart) a.dblendPart[(size_t)wg * a.dblendStride] = v;
+  else unsafeAtomicAdd(a.dblend, v);
+}
 
 __device__ __forceinline__ float ha_of(const ChainArgs& a, size_t idx) {
   const float h = a.hprev ? a.hprev[idx] : 0.f;
@@ -784,7 +813,7 @@ __global__ __launch_bounds__(256) void k_chain_res_out(ChainArgs a) {
     if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
     __syncthreads();
   }
-  if (threadIdx.x == 0 && a.dblend) unsafeAtomicAdd(a.dblend, red[0] * g * (1.f - g));
+  if (threadIdx.x == 0 && a.dblend) blend_grad_out(a, blockIdx.x, red[0] * g * (1.f - g));
 }
 
 // ---- parts 1-3 (and the carry of the step before) in one kernel -------------------------------------------------
@@ -895,7 +924,7 @@ __global__ __launch_bounds__(256) void k_chain_res_fused(FusedResArgs f) {
     if (tid < s) red[tid] += red[tid + s];
     __syncthreads();
   }
-  if (tid == 0) unsafeAtomicAdd(a.dblend, red[0] * g * (1.f - g));
+  if (tid == 0) blend_grad_out(a, blockIdx.x, red[0] * g * (1.f - g));
   // phase 2: d(z2*ha) = dpu2 . RU[:, C:]
   f32x4 acc[NP][2];
 #pragma unroll
@@ -1149,7 +1178,7 @@ __global__ __launch_bounds__(512, 4) void k_chain_res_node(ChainResNodeArgs f) {
     float sum = 0.f;
 #pragma unroll
     for (int q = 0; q < 8; ++q) sum += red[q];
-    unsafeAtomicAdd(a.dblend, sum * g * (1.f - g));
+    blend_grad_out(a, blockIdx.y * gridDim.x + blockIdx.x, sum * g * (1.f - g));
   }
   // ---- phase 2: d(z2 ha) = dpu2 . RU[:, C:]  (wave = column tile ct x row half rh) ----
   f32x4 acc[2];
@@ -1731,6 +1760,7 @@ struct AdjGradArgs {
   long aStride, bStride;
   int R, N, Np;          // row blocks, nodes, padded nodes (rows of a block that exist)
   float* dT;             // [N][N]
+  float* part;           // deterministic mode (null = atomics): slice z stores into slab z of [gridDim.z][N][N] instead
 };
 
 __global__ __launch_bounds__(256) void k_adj_grad(AdjGradArgs g) {
@@ -1812,7 +1842,9 @@ __global__ __launch_bounds__(256) void k_adj_grad(AdjGradArgs g) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int m = m0 + wr * 32 + 16 * p + 4 * kq + e, n = n0 + wc * 32 + 16 * q + j;
-        if (m < g.N && n < g.N) unsafeAtomicAdd(g.dT + (size_t)m * g.N + n, acc[p][q][e]);
+        if (m >= g.N || n >= g.N) continue;
+        if (g.part) g.part[((size_t)blockIdx.z * g.N + m) * g.N + n] = acc[p][q][e];
+        else unsafeAtomicAdd(g.dT + (size_t)m * g.N + n, acc[p][q][e]);
       }
 }
 
@@ -1822,7 +1854,8 @@ __global__ __launch_bounds__(256) void k_adj_grad(AdjGradArgs g) {
 // GEMM (K = 2 per batch item, 1 536 batch items) took 154 us for it; 32 x 32 output tiles per wave, K cut over waves and
 // workgroups, fp32 atomics.
 __global__ __launch_bounds__(256) void k_adj_grad_narrow2(const float* __restrict__ dA, const float* __restrict__ x,
-                                                          int rows, int N, int Np, int splits, float* __restrict__ dT) {
+                                                          int rows, int N, int Np, int splits, float* __restrict__ dT,
+                                                          float* __restrict__ detPart) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, j = lane & 15, kq = lane >> 4;
   const int n0 = blockIdx.y * 32, m0 = blockIdx.x * 32;
   const int K = rows * 2, groups = K >> 4, parts = splits * 4, part = blockIdx.z * 4 + w;
@@ -1849,7 +1882,7 @@ __global__ __launch_bounds__(256) void k_adj_grad_narrow2(const float* __restric
     acc[0][0] = MFMA16(av0.w, b01.y, acc[0][0]); acc[0][1] = MFMA16(av0.w, b11.y, acc[0][1]);
     acc[1][0] = MFMA16(av1.w, b01.y, acc[1][0]); acc[1][1] = MFMA16(av1.w, b11.y, acc[1][1]);
   }
-  if (g0 >= g1) return;
+  if (g0 >= g1 && !detPart) return;   // deterministic mode: every wave - an idle one too - stores slab `part` of [parts][N][N]
 #pragma unroll
   for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -1857,7 +1890,9 @@ __global__ __launch_bounds__(256) void k_adj_grad_narrow2(const float* __restric
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int n = n0 + 16 * p + 4 * kq + e, m = m0 + 16 * q + j;
-        if (n < N && m < N) unsafeAtomicAdd(dT + (size_t)n * N + m, acc[p][q][e]);
+        if (n >= N || m >= N) continue;
+        if (detPart) detPart[((size_t)part * N + n) * N + m] = acc[p][q][e];
+        else unsafeAtomicAdd(dT + (size_t)n * N + m, acc[p][q][e]);
       }
 }
 
@@ -1868,7 +1903,7 @@ __global__ __launch_bounds__(256) void k_adj_grad_narrow2(const float* __restric
 // on it, at the exposed tail of the backward).  One thread per (node, output column o of gate | update (192), row
 // stream), S*C0 accumulators each; the pre-activation gradients stream through once, coalesced.
 #define WN_MAXACC 36
-#define WN_PARTS 8        // workgroups per node (blockIdx.y), each with WN_GROUPS row groups of 192 threads
+#define WN_PARTS 8        // workgroups per node (gridDim.y; 1 in deterministic mode), each with WN_GROUPS row groups of 192 threads
 #define WN_GROUPS 4
 template <int C0, int S>
 __global__ __launch_bounds__(192 * WN_GROUPS) void k_wgrad_narrow(const float* __restrict__ x0tm, const float* __restrict__ mx0,
@@ -1889,7 +1924,7 @@ __global__ __launch_bounds__(192 * WN_GROUPS) void k_wgrad_narrow(const float* _
   // the T*B rows are dealt out round robin over (workgroup part, row group): 32 independent streams per node keep
   // enough loads in flight (one stream per node - 1536 dependent iterations - took 1.06 ms)
   const int rows = T * B;
-  for (int r = blockIdx.y * WN_GROUPS + rg; r < rows; r += WN_PARTS * WN_GROUPS) {
+  for (int r = blockIdx.y * WN_GROUPS + rg; r < rows; r += gridDim.y * WN_GROUPS) {
     const int t = r / B, b = r - t * B;
     const float d = dp[((size_t)r * Np + n) * O + oc];
     const float* xs = x0tm + ((size_t)r * Np + n) * C0;
@@ -1936,7 +1971,7 @@ __global__ __launch_bounds__(256) void k_wgrad_narrow_mfma(const float* __restri
   static_assert(S * C0 <= 16, "one MFMA row tile");
   __shared__ float part[3][S * C0][192];
   const int n = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6, kq = lane >> 4, j = lane & 15;
-  const int rows = T * B, stream = blockIdx.y * 4 + w, streams = WNM_PARTS * 4;
+  const int rows = T * B, stream = blockIdx.y * 4 + w, streams = gridDim.y * 4;
   const int steps = (rows + 3) >> 2, per = (steps + streams - 1) / streams;
   const int st0 = stream * per, st1 = min(st0 + per, steps);
   const int sl = j / C0, ch = j - sl * C0;          // this lane's A row: (slot, channel)
@@ -2102,7 +2137,7 @@ __global__ __launch_bounds__(256) void k_res_xcol_narrow(const float* __restrict
 template <int C0>
 __global__ __launch_bounds__(256) void k_res_wgrad_narrow(const float* __restrict__ dpu2, const float* __restrict__ dpg2,
                                                           const float* __restrict__ x, int I, float* __restrict__ dRU,
-                                                          float* __restrict__ dRG, long rows) {
+                                                          float* __restrict__ dRG, long rows, float* __restrict__ detPart) {
   __shared__ float part[4][192 * C0];
   const int lane = threadIdx.x & 63, sub = lane & 15, rw = lane >> 4, w = threadIdx.x >> 6;
   float acc[12][C0];
@@ -2147,7 +2182,8 @@ __global__ __launch_bounds__(256) void k_res_wgrad_narrow(const float* __restric
   for (int e = threadIdx.x; e < 192 * C0; e += 256) {
     const float v = part[0][e] + part[1][e] + part[2][e] + part[3][e];
     const int o = e / C0, c = e - o * C0;
-    if (o < 64) unsafeAtomicAdd(dRU + (size_t)o * I + c, v);
+    if (detPart) detPart[(size_t)blockIdx.x * (192 * C0) + e] = v;   // deterministic mode: a slab [192][C0] per workgroup
+    else if (o < 64) unsafeAtomicAdd(dRU + (size_t)o * I + c, v);
     else unsafeAtomicAdd(dRG + (size_t)(o - 64) * I + c, v);
   }
 }
@@ -2215,7 +2251,8 @@ __global__ __launch_bounds__(256) void k_xcol_narrow_mfma(const float* __restric
 __global__ __launch_bounds__(256) void k_res_narrow2(const float* __restrict__ dpu2, const float* __restrict__ dpg2,
                                                      const float* __restrict__ RU, const float* __restrict__ RG,
                                                      const float* __restrict__ x, int I, float* __restrict__ dX,
-                                                     float* __restrict__ dRU, float* __restrict__ dRG, long rows) {
+                                                     float* __restrict__ dRU, float* __restrict__ dRG, long rows,
+                                                     float* __restrict__ detPart) {
   __shared__ float part[4][192 * 2];
   const int lane = threadIdx.x & 63, sub = lane & 15, rw = lane >> 4, w = threadIdx.x >> 6;
   float wt[12][2], acc[12][2];
@@ -2272,7 +2309,8 @@ __global__ __launch_bounds__(256) void k_res_narrow2(const float* __restrict__ d
   for (int e = threadIdx.x; e < 192 * 2; e += 256) {
     const float v = part[0][e] + part[1][e] + part[2][e] + part[3][e];
     const int o = e >> 1, c = e & 1;
-    if (o < 64) unsafeAtomicAdd(dRU + (size_t)o * I + c, v);
+    if (detPart) detPart[(size_t)blockIdx.x * (192 * 2) + e] = v;   // deterministic mode: a slab [192][2] per workgroup
+    else if (o < 64) unsafeAtomicAdd(dRU + (size_t)o * I + c, v);
     else unsafeAtomicAdd(dRG + (size_t)(o - 64) * I + c, v);
   }
 }
@@ -2445,7 +2483,7 @@ __global__ __launch_bounds__(256) void k_node_colsum(const float* __restrict__ s
 // A workgroup walks items (row, n) with 256/Opad of them in flight, lanes along o (coalesced); partial sums meet in
 // LDS and then in `out` with one atomic per column and workgroup (out holds its initial value beforehand).
 __global__ __launch_bounds__(256) void k_colsum_all(const float* __restrict__ src, size_t rows, int N, int Np, int O,
-                                                    int Opad, float* __restrict__ out) {
+                                                    int Opad, float* __restrict__ out, float* __restrict__ detPart) {
   __shared__ float red[256];
   const int o = threadIdx.x % Opad, item = threadIdx.x / Opad, per = 256 / Opad;
   const size_t total = rows * N;
@@ -2459,7 +2497,8 @@ __global__ __launch_bounds__(256) void k_colsum_all(const float* __restrict__ sr
   __syncthreads();
   if (item == 0 && o < O) {
     for (int q = 1; q < per; ++q) s += red[q * Opad + o];
-    unsafeAtomicAdd(&out[o], s);
+    if (detPart) detPart[(size_t)blockIdx.x * O + o] = s;   // deterministic mode: a row [O] per workgroup
+    else unsafeAtomicAdd(&out[o], s);
   }
 }
 
@@ -2502,6 +2541,7 @@ struct FuseBwdArgs {
   const float* ts[8];
   float* dts[8];
   float* dgain;          // [nTs] accumulators (zeroed by the caller)
+  float* dgainPart;      // deterministic mode (null = atomics): workgroup x of head h stores dgainPart[x * nHeads + h]
   int B, T, N, Np, C0, od, F, xSteps, startDim, nHeads, nTs;
   int headBegin[8];
 };
@@ -2531,7 +2571,45 @@ __global__ __launch_bounds__(256) void k_fuse_heads_bwd(FuseBwdArgs a) {
     if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
     __syncthreads();
   }
-  if (threadIdx.x == 0) unsafeAtomicAdd(&a.dgain[h], red[0]);
+  if (threadIdx.x == 0) {
+    if (a.dgainPart) a.dgainPart[(size_t)blockIdx.x * a.nHeads + h] = red[0];
+    else unsafeAtomicAdd(&a.dgain[h], red[0]);
+  }
+}
+
+// ---- deterministic mode: the one ordered reduction behind every site above that splits a sum over workgroups ------
+//   dst[b][r][c] (= or +=) sum_{p < parts, ascending} part[p * stride + (b * rows + r) * cols + c]
+// The partial slabs are compact; dst is strided (batch bDst, row ldd).  HBM-bound and small: 16 bytes per thread
+// (vec, wave-uniform: every pointer and stride 16-byte friendly - else a float per thread), coalesced over the index,
+// the sum of a thread in a register; parts is 4 .. a few hundred, so the loop is unrolled for loads in flight, the
+// additions stay in slab order.
+struct ReduceArgs {
+  float* dst;
+  const float* part;
+  long stride, ldd, bDst;
+  int parts, nb, rows, cols, accumulate, vec;
+};
+__global__ __launch_bounds__(256) void k_ordered_reduce(ReduceArgs a) {
+  const long n = (long)a.nb * a.rows * a.cols;
+  const long i = ((long)blockIdx.x * 256 + threadIdx.x) * (a.vec ? 4 : 1);
+  if (i >= n) return;
+  const long rc = (long)a.rows * a.cols, b = i / rc, r = (i - b * rc) / a.cols, c = i - b * rc - r * a.cols;
+  float* d = a.dst + b * a.bDst + r * a.ldd + c;
+  const float* p = a.part + i;
+  if (a.vec) {
+    float4 s = a.accumulate ? *reinterpret_cast<const float4*>(d) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 8
+    for (int q = 0; q < a.parts; ++q) {
+      const float4 v = *reinterpret_cast<const float4*>(p + (size_t)q * a.stride);
+      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+    *reinterpret_cast<float4*>(d) = s;
+  } else {
+    float s = a.accumulate ? *d : 0.f;
+#pragma unroll 8
+    for (int q = 0; q < a.parts; ++q) s += p[(size_t)q * a.stride];
+    *d = s;
+  }
 }
 
 #endif

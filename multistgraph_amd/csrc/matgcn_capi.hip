@@ -213,7 +213,16 @@ struct TrainPlan {
   // backward's node-wise data-gradient contractions; matgcn_train_bytes counts it only while mode 2 is set
   long oWp16[MATGCN_MAX_LAYERS][2];
   long floatsBf16;
+  // optional tail, deterministic backward only (matgcn_set_deterministic), behind whichever of the two ends above the
+  // call uses: the partial slabs of the ordered reductions.  Two arenas of detArena floats - one for the sites on the
+  // chains' streams, one for the sites on the weight-gradient stream; within a stream every site's slabs are read by
+  // its reducer before the next site writes, so all sites of a stream share one arena sized for the largest of them -
+  // and per layer [workgroups of a chain kernel][T] blend-scalar shares.  Offsets are relative to the tail's start.
+  long detArena, detBlendWgs, oDetArena[2], oDetBlend[MATGCN_MAX_LAYERS];
+  long detFloats;
 };
+constexpr int DET_ADJ_SPLIT = 16;     // deterministic mode: at most this many slices (slabs of N x N) of an adjacency gradient
+constexpr int DET_GRID = 256;         // ... and workgroups of a grid-sized reduction (k_res_*narrow*, k_colsum_all)
 
 int make_train_plan(const Plan& P, TrainPlan* R) {
   memset(R, 0, sizeof(*R));
@@ -277,6 +286,25 @@ int make_train_plan(const Plan& P, TrainPlan* R) {
       R->oWp16[l][part] = take(((long)P.N * R->S * I * O + 1) / 2);   // bf16: two values per float slot
     }
   R->floatsBf16 = o;
+  {
+    auto mx = [](long a, long b) { return a > b ? a : b; };
+    const long NN = (long)P.N * P.N, nd = nEnt * P.N * P.d, cmax = P.C0 > H ? P.C0 : H;
+    long a = (long)DET_ADJ_SPLIT * NN;                                       // adjacency gradients: slices x [N][N]
+    a = mx(a, 256L * 128 * cmax + 256L * 128);                               // residual nn.Linear: 256 parts x [128][C] + bias rows
+    a = mx(a, 16L * P.headT * P.CH * H);                                     // head weight: 16 parts x [hT][CH][64]
+    a = mx(a, 32 * nd);                                                      // pools -> embedding: up to 32 parts x [entries][N][d]
+    a = mx(a, nd + nEnt * (((long)P.N * P.d + 255) / 256) * 64);             // embedding gradient + its gain rows
+    a = mx(a, (long)DET_GRID * 192 * (P.C0 > 16 ? P.C0 : 16));               // narrow residual weight gradients
+    a = mx(a, (long)DET_GRID * 256);                                         // column sums
+    a = mx(a, (((long)P.T * P.N * P.od + 255) / 256) * MATGCN_MAX_HEADS);    // head-fusion gains
+    R->detArena = rup(a, 64);
+    R->detBlendWgs = mx(mx((long)((P.B + 63) / 64) * P.N, ((long)P.B * P.Np + 63) / 64), 512);
+    long d = 0;
+    auto taked = [&](long n) { long at = d; d += rup(n, 64); return at; };
+    R->oDetArena[0] = taked(R->detArena); R->oDetArena[1] = taked(R->detArena);
+    for (int l = 0; l < P.L; ++l) R->oDetBlend[l] = taked(R->detBlendWgs * P.T);
+    R->detFloats = d;
+  }
   return MATGCN_OK;
 }
 
@@ -419,6 +447,7 @@ int g_mix_precision = 0;      // matgcn_set_mix_precision: 0 fp32 operands, 1 bf
                               // 2 bf16 operands for the graph mixes AND the node-wise contractions (bf16 weight streams),
                               // 3 three bf16 pieces per operand of the graph mixes (fp32 accuracy on the bf16 pipe)
 int g_train_precision = 0;    // matgcn_set_train_precision: the same values for matgcn_forward_train / matgcn_backward
+int g_deterministic = 0;      // matgcn_set_deterministic: matgcn_backward adds in a fixed order (slabs + k_ordered_reduce)
 // The backward follows the mode its forward_train ran with: forward_train notes (device, train buffer) -> mode here and
 // matgcn_backward looks its train buffer up (a buffer without an entry runs with the current setting).  The last
 // TRAIN_MODE_SLOTS buffers are remembered - far more than the one per model a training loop keeps.
@@ -1284,6 +1313,12 @@ int matgcn_set_mix_precision(int mode) {
 int matgcn_set_train_precision(int mode) {
   const int prev = g_train_precision;
   g_train_precision = (mode == 1 || mode == 2) ? mode : 0;
+  return prev;
+}
+
+int matgcn_set_deterministic(int enabled) {
+  const int prev = g_deterministic;
+  g_deterministic = enabled != 0 ? 1 : 0;
   return prev;
 }
 

@@ -123,6 +123,10 @@ def _precision_mode(name) -> int:
     return HIP_PRECISIONS[name]
 
 
+def _torch_deterministic() -> bool:
+    return bool(torch.are_deterministic_algorithms_enabled())
+
+
 class _TrainStep(torch.autograd.Function):
     """autograd node of one training-mode forward: matgcn_forward_train / matgcn_backward.
     The parameters ride along as inputs so that autograd routes their gradients; X gets none (the reference
@@ -173,6 +177,13 @@ class MultiATGCN(AbstractTrafficStateModel):
         # reassigning it.
         self.hip_precision = get("hip_precision", "fp32")
         _precision_mode(self.hip_precision)
+        # config['hip_deterministic']: bit-reproducible gradients on the HIP path (matgcn_set_deterministic: the backward's
+        # sums in a fixed order instead of fp32 atomics).  None (default) follows torch.are_deterministic_algorithms_enabled()
+        # at every training step; True / False force it.  An attribute, not a parameter: state_dict and checkpoints are
+        # unchanged.
+        self.hip_deterministic = get("hip_deterministic", None)
+        if self.hip_deterministic not in (None, True, False):
+            raise ValueError("hip_deterministic = %r: expected None, True or False" % (self.hip_deterministic,))
         self.batch_size = get("batch_size", 64)
         self.device = get("device", torch.device("cpu"))
         config["num_nodes"] = self.num_nodes  # the reference writes this back (:233)
@@ -282,6 +293,10 @@ class MultiATGCN(AbstractTrafficStateModel):
         emb = self.static_initial_gru(torch.matmul(self.static, v))
         return emb.expand(self.num_layers, batch, -1, -1)
 
+    def _deterministic(self) -> bool:
+        """config['hip_deterministic'], None following torch.use_deterministic_algorithms"""
+        return _torch_deterministic() if self.hip_deterministic is None else bool(self.hip_deterministic)
+
     def _params_key(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters())
 
@@ -303,6 +318,7 @@ class MultiATGCN(AbstractTrafficStateModel):
         # key existed); the bf16 modes are set around each of this model's library calls and restored afterwards
         mode = _precision_mode(self.hip_precision)
         hp.precision = mode if mode else None
+        hp.deterministic = self._deterministic()
         key = (id(hp),) + self._params_key()
         if key != self._prepared_key or not self.cache_prepared:
             hp.bind(self._state(), self._static_dev)

@@ -321,6 +321,10 @@ class HotPath:
         # (matgcn_set_mix_precision for the inference forwards, matgcn_set_train_precision for the training step).
         # None (default): the calls leave the settings as they are - whatever the process set, fp32 unless it did.
         self.precision: Optional[int] = None
+        # deterministic backward (matgcn_set_deterministic): True / False are set around this binding's training calls
+        # and restored afterwards - around forward_train too, which sizes the train buffer with the partial slabs of the
+        # ordered reductions -, None (default) leaves the process-wide setting as it is
+        self.deterministic: Optional[bool] = None
 
     # ---- plumbing ------------------------------------------------------------------------------
     def _stream(self):
@@ -367,6 +371,18 @@ class HotPath:
             yield
         finally:
             setter(prev)
+
+    @contextlib.contextmanager
+    def _det(self):
+        """the library's deterministic-backward setting at this binding's value for the calls inside (None: untouched)"""
+        if self.deterministic is None:
+            yield
+            return
+        prev = self.lib.matgcn_set_deterministic(1 if self.deterministic else 0)
+        try:
+            yield
+        finally:
+            self.lib.matgcn_set_deterministic(prev)
 
     def bind(self, state: Dict[str, torch.Tensor], static_supports: Optional[torch.Tensor]):
         """Point matgcn_params at the tensors of a reference-named state dict."""
@@ -497,9 +513,13 @@ class HotPath:
 
     # ---- training step ---------------------------------------------------
     def _train_buffer(self) -> torch.Tensor:
-        if self._train is None:
-            nbytes = C.c_size_t()
-            _lib.check(self.lib.matgcn_train_bytes(C.byref(self.dims), C.byref(nbytes)), "matgcn_train_bytes")
+        """The train buffer, at least as large as matgcn_train_bytes reports under the CURRENT library settings (it
+        counts the deterministic backward's partial slabs and mode 2's bf16 copies only while they are set): a buffer
+        sized before a setting was switched on is replaced.  Called in front of forward_train, never between it and
+        its backward - a new buffer has none of the saved activations."""
+        nbytes = C.c_size_t()
+        _lib.check(self.lib.matgcn_train_bytes(C.byref(self.dims), C.byref(nbytes)), "matgcn_train_bytes")
+        if self._train is None or nbytes.value > self._train.numel() * 4:
             self._train = torch.empty(nbytes.value // 4, dtype=torch.float32, device=self.device)
         return self._train
 
@@ -520,9 +540,9 @@ class HotPath:
         drop_mask = self._mask(drop_mask)
         h0 = self._h0(h0)
         self._need_prepared()
-        self._train_buffer()
         out = torch.empty(self.batch, s.out_window, s.nodes, s.out_dim, dtype=torch.float32, device=self.device)
-        with self._mode(self.lib.matgcn_set_train_precision):
+        with self._mode(self.lib.matgcn_set_train_precision), self._det():
+            self._train_buffer()
             self._with_workspace(lambda ws, wsb: self.lib.matgcn_forward_train(
                 C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
                 C.byref(src) if src is not None else None, C.c_void_p(_ptr(h0)), C.c_void_p(_ptr(drop_mask)),
@@ -600,15 +620,19 @@ class HotPath:
                 continue
             if name not in grads and (t.requires_grad or not isinstance(t, torch.nn.Parameter)):   # adaptive adjacency)
                 grads[name] = views[name].zero_()
-        tr = self._train_buffer()
-        ws, wsb = self._ws()   # (the workspace as forward_train left it: no re-sizing here)
-        _lib.check(self.lib.matgcn_backward(C.byref(self.dims), C.byref(self.params),
+        tr = self._train
+        if tr is None:
+            raise _lib.MatgcnError("backward() without a forward_train() before it")
+        ws, wsb = self._ws()   # (the workspace and the train buffer as forward_train left them: no re-sizing here - a
+        # deterministic backward behind a forward_train that ran without the setting reports MATGCN_ERR_SMALL_BUFFER)
+        with self._det():
+            status = self.lib.matgcn_backward(C.byref(self.dims), C.byref(self.params),
                                             C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
                                             C.byref(src) if src is not None else None,
                                             C.c_void_p(_ptr(h0)), C.c_void_p(_ptr(drop_mask)),
                                             C.c_void_p(d_out.data_ptr()), C.byref(g), C.c_void_p(_ptr(d_h0)), ws, wsb,
-                                            C.c_void_p(tr.data_ptr()), C.c_size_t(tr.numel() * 4), self._stream()),
-                   "matgcn_backward")
+                                            C.c_void_p(tr.data_ptr()), C.c_size_t(tr.numel() * 4), self._stream())
+        _lib.check(status, "matgcn_backward")
         if d_h0 is not None:
             grads[self.D_H0] = d_h0
         return grads

@@ -1,6 +1,8 @@
 """Training steps of the bench workload (default Baltimore 403, B=64): forward_train + backward through the plugin
 surface (calculate_loss().backward()), timed with HIP events.
-usage: train_step.py [workload] [steps] [serial|wave] [batch] [fp32|bf16_mix|bf16]
+usage: train_step.py [--deterministic] [workload] [steps] [serial|wave] [batch] [fp32|bf16_mix|bf16]
+(--deterministic: the model's hip_deterministic = True - the backward's sums in a fixed order, see matgcn_set_deterministic;
+the summary line then also gives the bytes the train buffer grew by)
 (serial: matgcn_set_wavefront(0) - every kernel alone on one stream, so a profiler's durations are the kernels' own;
 the last argument is the model's hip_precision; the last line gives the medians over the steps after the first three)"""
 import os, sys
@@ -9,6 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench
 from multistgraph_amd import synthetic as syn
+deterministic = "--deterministic" in sys.argv
+if deterministic:
+    sys.argv.remove("--deterministic")
 name = sys.argv[1] if len(sys.argv) > 1 else "bm403"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 w = dict(bench.WORKLOADS[name])
@@ -17,6 +22,7 @@ if len(sys.argv) > 4:
 dev = torch.device("cuda:0")
 model, df, cfg = bench.build_model(w, dev, 0)
 model.train()
+model.hip_deterministic = deterministic
 if len(sys.argv) > 5:
     model.hip_precision = sys.argv[5]
 if len(sys.argv) > 3 and sys.argv[3] == "serial":
@@ -46,5 +52,16 @@ print("train buffer %.2f GB  workspace %.2f GB  peak torch memory %.2f GB" % (
 if len(times) > 3:
     import statistics
     med = [statistics.median(t[k] for t in times[3:]) for k in range(3)]
-    print("median of %d steps (%s, B = %d, %s): step %.3f ms  forward %.3f ms  backward %.3f ms" % (
-        len(times) - 3, name, w["batch"], model.hip_precision, med[0], med[1], med[2]))
+    print("median of %d steps (%s, B = %d, %s%s): step %.3f ms  forward %.3f ms  backward %.3f ms" % (
+        len(times) - 3, name, w["batch"], model.hip_precision, ", deterministic" if deterministic else "", med[0], med[1],
+        med[2]))
+if deterministic:
+    import ctypes
+    from multistgraph_amd import _lib
+    hp, lib, nb = next(iter(model._paths.values())), _lib.load(), [ctypes.c_size_t(), ctypes.c_size_t()]
+    for on in (0, 1):
+        prev = lib.matgcn_set_deterministic(on)
+        lib.matgcn_train_bytes(ctypes.byref(hp.dims), ctypes.byref(nb[on]))
+        lib.matgcn_set_deterministic(prev)
+    print("deterministic scratch: %d bytes (%.1f MB) behind a train buffer of %d" % (
+        nb[1].value - nb[0].value, (nb[1].value - nb[0].value) / 2**20, nb[0].value))
