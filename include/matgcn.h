@@ -31,6 +31,9 @@
  * existing argument - no symbol, signature or struct changed, and every value ABI 12 defined keeps its meaning and bits.
  * Still ABI 12: matgcn_set_deterministic is one more symbol - no existing symbol, signature or struct changed, and with
  * the setting at its default (0) matgcn_train_bytes and matgcn_backward are what ABI 12 defined.
+ * Still ABI 12: matgcn_set_train_bf16x3 is one more symbol, on the same terms - with it at its default (0) every entry
+ * point launches the kernels ABI 12 defined, with their arguments and bits, and both *_bytes() give its numbers;
+ * matgcn_set_train_precision keeps every value's meaning (3 included: it means 0).
  */
 #ifndef MATGCN_H
 #define MATGCN_H
@@ -128,7 +131,8 @@ const char* matgcn_error_string(int status);
  * weight streams (half the bytes of the fp32 streams, behind everything else); a mode-2 forward on a workspace sized
  * without them returns MATGCN_ERR_SMALL_BUFFER (ask again and re-allocate).  While matgcn_set_mix_precision(3) is in force
  * it counts the three bf16 planes of the support stack instead (6 bytes per element of the [Np up to 32][Ks*Np up to 64]
- * stack), under the same contract.  The fp32 paths never pay for either. */
+ * stack), under the same contract; likewise while matgcn_set_train_bf16x3 is the effective training mode (see there).  The
+ * fp32 paths never pay for either. */
 int matgcn_prepared_bytes(const matgcn_dims* dims, size_t* bytes);
 int matgcn_workspace_bytes(const matgcn_dims* dims, size_t* bytes);
 
@@ -411,8 +415,9 @@ int matgcn_prepare_join(void* stream);
  * recurrent state, the node-wise contractions, the residual cell, matgcn_prepare, the unit entry points and everything in
  * memory stay fp32; modes 0, 1 and 2 keep their kernels and their bits.  Every mix of the two forwards has a mode-3
  * kernel (one 64 x 128 tile shape at every batch and graph size, odd batch sizes and the small batches of the fp32 path's
- * 64 x 32 tiles included), so no shape of the forwards falls back to an fp32 mix.  Training is out of scope:
- * matgcn_set_train_precision(3) means 0, so the backward's 32 x 128 and 64 x 64 transposed-mix tiles never see the mode.
+ * 64 x 32 tiles included), so no shape of the forwards falls back to an fp32 mix.  Training is a switch of its own,
+ * matgcn_set_train_bf16x3 (below): matgcn_set_train_precision(3) means 0 and always will, so a process that sets only this
+ * mode trains with the fp32 kernels and their bits.
  * Measured gap to the reference's float64 prediction (MI355X, tests/test_bf16x3.py, the bound is twice the reference's
  * own fp32-vs-float64 gap): bm403_out24 (N = 403, B = 4) worst element 3.87e-7, r.m.s. 4.91e-8 - the reference's own
  * fp32 run 4.45e-7 / 6.15e-8; synth4096_out24 (N = 4096, B = 2, partial sums) 2.66e-7 / 4.19e-8 - reference 4.69e-7 /
@@ -423,13 +428,14 @@ int matgcn_prepare_join(void* stream);
 int matgcn_set_mix_precision(int mode);
 
 /* Modes 1 and 2 for the training entry points (matgcn_forward_train, matgcn_backward); 0 (default) = fp32, any other
- * value - 3 included: the three-piece mode is inference only - means 0; returns the previous setting.  The two settings are independent (a model can train in bf16 and
+ * value - 3 included: three-piece training is a switch of its own, matgcn_set_train_bf16x3 - means 0; returns the previous setting.  The two settings are independent (a model can train in bf16 and
  * evaluate in fp32).
  *   matgcn_forward_train runs the kernels of the inference forward of that mode - mode >= 1: bf16 operands for the
  *   graph mixes (the mixed rows it saves for the weight gradients are their fp32 outputs); mode 2: also for the
  *   node-wise contractions of the recurrent step and of the hoisted x part of layers >= 1 (bf16 copies of the weight
  *   streams, made once per call in the workspace).  The saved activations, the state, the residual cell and every
  *   epilogue stay fp32.
+ *   (fp32-accurate graph mixes on the bf16 instruction for training: matgcn_set_train_bf16x3, below.)
  *   matgcn_backward, mode >= 1: the transposed graph mixes (the chain's two per step and layer, the x columns of the
  *   last step and of layer 0) take bf16 operands with fp32 accumulation; mode 2: also the node-wise data-gradient
  *   contractions (the h columns of both AGCNs in the chain, the x columns of the layers), from bf16 copies of the plain
@@ -445,6 +451,50 @@ int matgcn_set_mix_precision(int mode);
  * backward on a train buffer without them returns MATGCN_ERR_SMALL_BUFFER.  Measured gap to the reference's autograd: <= 1.4e-2 max-normalised per gradient tensor
  * (tests/test_train_precision.py holds both modes to 2.7e-2; figures in DESIGN.md section 5). */
 int matgcn_set_train_precision(int mode);
+
+/* ---- three-piece training ("bf16x3" for the training entry points) ---------------------------------------------------
+ * matgcn_set_train_bf16x3(1): the graph mixes of the training step - matgcn_forward_train's and the transposed ones of
+ * matgcn_backward - take both operands as three bf16 pieces and accumulate the six leading piece products in fp32 on
+ * v_mfma_f32_16x16x32_bf16, as matgcn_set_mix_precision(3) does for the inference forwards: fp32 accuracy, held to the fp32
+ * path's own tolerances (1e-4 per gradient tensor against float64 autograd, tests/test_bf16x3_train.py).  Returns the
+ * previous setting; 0 (default) = off; any non-zero value = on.  A symbol of its own, not a value of
+ * matgcn_set_train_precision: ABI 12 defined every value of that setter outside 1 and 2 as 0.
+ * Effective training mode, read by matgcn_forward_train on entry:
+ *   matgcn_set_train_precision at 1 or 2 - that mode; this switch is ignored (the narrower arithmetic was asked for);
+ *   matgcn_set_train_precision at 0 and this switch on - mode 3;
+ *   otherwise - 0, fp32.
+ * The library records mode 3 per train buffer like modes 1 and 2: matgcn_backward FOLLOWS the mode of its matching
+ * matgcn_forward_train whatever the switch says when it is called; a backward on a train buffer the library has no
+ * record of runs with the current effective mode.
+ *   matgcn_forward_train, mode 3: the mixes of the inference forward of matgcn_set_mix_precision(3) (k_mix_bf16x3<0|1>,
+ *   partial sums past 1 024 nodes); the support stack is split once per call into three planes in the workspace.  The
+ *   mixed rows it saves are those kernels' fp32 outputs; node kernels, residual cell, saved activations and every
+ *   epilogue stay fp32.
+ *   matgcn_backward, mode 3: every transposed mix on the graph-mix kernels - the chain's two per step and layer (split by
+ *   support slot), the 64-channel x columns of the last step and of the layers, layer 0's narrow x columns when they fill
+ *   whole 64-column tiles - runs on k_mix_bf16x3<2>: one 64 x 128 tile shape for odd and even batch rows, partial sums
+ *   when one part's reduction is longer than 1 024 indices (the fp32 transposed mix has none).  Its A operand is the plain
+ *   stack (the transposed supports) as three bf16 planes that matgcn_forward_train writes into the train buffer on its
+ *   side stream, SLOT BY SLOT: [piece][slot][Np rounded up to 32][N rounded up to 64], zero-filled - Np is a multiple of
+ *   16, the kernel's K-tile holds 32 reduction indices, and the last tile of a slot must not run into the next slot's
+ *   rows.  Layer-0 x columns that take the generic GEMM, every parameter-gradient product, the adjacency gradient and
+ *   everything in memory stay fp32.  gcn_off models have no graph mixes: the mode is a no-op there.
+ * Buffers: while mode 3 is the effective mode matgcn_workspace_bytes counts the forward's planes (as
+ * matgcn_set_mix_precision(3)) and matgcn_train_bytes the plain stack's - 6 bytes per element of [Ks][Np up to 32][N up
+ * to 64], behind everything else the mode uses and in front of the deterministic slabs; a mode-3 forward_train or
+ * backward on a buffer sized without them returns MATGCN_ERR_SMALL_BUFFER (ask again and re-allocate).  fp32 and modes 1
+ * and 2 pay nothing and keep their bits.
+ * matgcn_set_deterministic is independent and composes: the mixes meet nothing in memory (the slot parts are added by
+ * their consumers), so a deterministic mode-3 backward is bit-reproducible and both matgcn_set_wavefront schedules give
+ * the same bits.
+ * Measured at Baltimore 403 / B = 64 (MI355X, tools/train_step.py [--bf16x3], one box and one session, the parent build
+ * and this one alternating twice, median of 30 steps each): training step 20.11 / 20.02 ms against
+ * 21.68 / 21.65 ms in fp32 (-7.4 %), forward_train 6.82 / 6.79 against 7.63 / 7.61 ms, backward 13.11 / 13.10 against
+ * 13.91 / 13.89 ms; the parent's fp32 step 21.80 / 21.62 ms - the default path is as fast as before the switch existed.
+ * 3 354 624 bytes of planes in the train buffer, 3 194 880 in the workspace.  The per-launch time of k_mix_bf16x3<2>
+ * against k_mix_n32<false> under a kernel trace has NOT been measured yet; the backward's 0.8 ms are the only evidence
+ * that the transposed three-piece mix is the faster one. */
+int matgcn_set_train_bf16x3(int enabled);
 
 /* ---- deterministic backward --------------------------------------------------------------------------------------
  * matgcn_set_deterministic(1): every sum of matgcn_backward that several workgroups (or waves) form together is added

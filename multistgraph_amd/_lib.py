@@ -112,6 +112,7 @@ _SIGNATURES = {
     "matgcn_set_stream_pool": (C.c_int, [C.c_int]),
     "matgcn_set_mix_precision": (C.c_int, [C.c_int]),
     "matgcn_set_train_precision": (C.c_int, [C.c_int]),
+    "matgcn_set_train_bf16x3": (C.c_int, [C.c_int]),
     "matgcn_set_deterministic": (C.c_int, [C.c_int]),
     "matgcn_set_lazy_prepare": (C.c_int, [C.c_int]),
     "matgcn_prepare_join": (C.c_int, [_P]),

@@ -228,11 +228,26 @@ StackEntries stack_entries(const StackMap& map) {
 // between the callers: the column tiles of X and of the result, and how many.  parts > 1 cuts the reduction by support
 // slot - that many times the workgroups, each with a K loop of the forward's length; part k's result lands `partStride`
 // floats behind part k-1's, the consumers add them up.  tile: MIX_64x64 over the NpC padded rows, or MIX_32x128 over the
-// N rows (mix_backward_tile).  Training precision mode >= 1: bf16 operands.
+// N rows (mix_backward_tile).  Training precision mode >= 1: bf16 operands.  Three-piece training (MIX_BF16X3): every
+// launch takes the one 64 x 128 tile of k_mix_bf16x3 over the NpC padded rows, whatever `tile` the fp32 rule chose, and
+// reads StP from its per-slot planes in the train buffer (TrainPlan::oStPl); partial sums (FLUSH) by the forward's rule
+// on the length of one part's reduction.
 int launch_mix_plain(const Bwd& b, MixArgs a, MixTile tile, int parts = 1, long partStride = 0) {
   const Plan& P = b.c.P;
   a.St = b.tr + b.c.R.oStP; a.ldS = P.NpC; a.sK = 0;
   a.Np = P.NpC; a.N = P.N; a.Ks = 1; a.nK = P.Ks * P.Np / 16;
+  if (b.c.prec.mix == MIX_BF16X3) {
+    a.Apl = b.tr + b.c.R.oStPl; a.plStride = b.c.R.stPlaneWords;
+    a.nK = P.Np / 16; a.kSlots = parts > 1 ? 1 : P.Ks;
+    if (parts > 1) {
+      a.parts = parts;
+      a.aPartStride = (long)P.nKg * P.NpC; a.xPartStride = (long)P.Np * a.ldX; a.outPartStride = partStride;
+    }
+    if (!mix_x3_ok(a)) return MATGCN_ERR_UNSUPPORTED;
+    MixArgs len = a;
+    len.nK = a.kSlots * a.nK;   // groups of 16 in one part's reduction
+    return launch_mix_variant(MIX_64x128, MIX_BF16X3, mix_flush(MIX_BF16X3, len), 2, a, P.NpC, b.c.s);
+  }
   if (parts > 1) {
     a.parts = parts; a.nK = P.Np / 16;
     a.aPartStride = (long)P.Np * P.NpC; a.xPartStride = (long)P.Np * H; a.outPartStride = partStride;
@@ -589,7 +604,7 @@ int bwd_clear(Pass& pass) {
 // plain copies the backward GEMMs contract with: the support stack and the folded node-adaptive weights.  Parameter-only
 // work: matgcn_forward_train runs it on a side stream beside the forward (it used to open every backward: 0.8 ms on the
 // critical path), matgcn_backward finds the copies in the train buffer.
-int plain_operands(const Ctx& c, float* tr, hipStream_t s, bool bf16Copies) {
+int plain_operands(const Ctx& c, float* tr, hipStream_t s, bool bf16Copies, bool x3Planes) {
   const Plan& P = c.P;
   const TrainPlan& R = c.R;
   const StackMap map = build_stack_map(P, c.D, c.prm);
@@ -597,6 +612,15 @@ int plain_operands(const Ctx& c, float* tr, hipStream_t s, bool bf16Copies) {
     hipLaunchKernelGGL(k_stack_plain, dim3((unsigned)((P.Ks * P.Np + 31) / 32), (unsigned)((P.NpC + 31) / 32)), dim3(256),
                        0, s, c.prep + P.oSt, P.Mp, P.N, P.Ks * P.Np, P.NpC, tr + R.oStP);
     CHECK_LAUNCH();
+    // three-piece training: its bf16 planes, slot by slot - each slot's Np reduction indices rounded up to 32 and
+    // zero-filled, so that no K-tile of the transposed mix crosses into the next slot (k_mix_bf16x3, ROLE 2)
+    for (int k = 0; k < P.Ks && x3Planes; ++k) {
+      const long slotWords = (long)P.nKg * P.NpC;
+      hipLaunchKernelGGL(k_split_bf16x3, dim3(blocks_for((size_t)slotWords)), dim3(256), 0, s,
+                         tr + R.oStP + (size_t)k * P.Np * P.NpC, P.NpC, P.Np, P.nKg,
+                         reinterpret_cast<uint4*>(tr + R.oStPl) + (size_t)k * slotWords, R.stPlaneWords);
+      CHECK_LAUNCH();
+    }
   }
   // plain folded weights of both AGCNs of every layer
   for (int l = 0; l < P.L && !P.gcnOff; ++l)
@@ -1504,8 +1528,8 @@ int matgcn_train_bytes(const matgcn_dims* dims, size_t* bytes) {
   RETURN_IF(make_plan(dims, &P));
   TrainPlan R;
   RETURN_IF(make_train_plan(P, &R));
-  *bytes = (size_t)((g_train_precision == 2 && !P.gcnOff ? R.floatsBf16 : R.floats) + (g_deterministic ? R.detFloats : 0)) *
-           sizeof(float);
+  const int mode = effective_train_mode();
+  *bytes = (size_t)(train_floats(P, R, mode) + (g_deterministic ? R.detFloats : 0)) * sizeof(float);
   return MATGCN_OK;
 }
 
@@ -1527,11 +1551,16 @@ static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* para
   c.train = (float*)train;
   // precision (matgcn_set_train_precision): bf16 operands for the graph mixes (mode >= 1) and the node-wise contractions
   // (mode 2, bf16 copies of the weight streams in the workspace) - as the inference forward of that mode; the saved
-  // activations, the state and every epilogue stay fp32.  The matching backward follows this mode (train_mode_of).
-  const int mode = g_train_precision;
+  // activations, the state and every epilogue stay fp32.  Mode 3 (matgcn_set_train_bf16x3 while the setting above is
+  // 0): the inference forward's three-piece graph mixes, and the planes of the plain stack for the backward's.  The
+  // matching backward follows this mode (train_mode_of).
+  const int mode = effective_train_mode();
   if (mode == 2 && !P.gcnOff && (workspace_bytes < (size_t)P.workspaceFloatsBf16 * sizeof(float) ||
                                  train_bytes < (size_t)c.R.floatsBf16 * sizeof(float)))
     return MATGCN_ERR_SMALL_BUFFER;   // sized without mode 2's bf16 copies
+  if (mode == 3 && (workspace_bytes < (size_t)P.workspaceFloatsX3 * sizeof(float) ||
+                    train_bytes < (size_t)c.R.floatsX3 * sizeof(float)))
+    return MATGCN_ERR_SMALL_BUFFER;   // sized without mode 3's planes
   c.prec = precision_of(mode);
   note_train_mode(train, -1);   // until this call has enqueued everything: a backward on this buffer is refused
   // the forward kernels write the rows of the real nodes only: the rows of the padding nodes must read as zero.  The
@@ -1551,7 +1580,7 @@ static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* para
     HIP_OK(hipEventRecord(g_wf.auxFork, c.s));
     HIP_OK(hipStreamWaitEvent(aux, g_wf.auxFork, 0));
   }
-  RETURN_IF(plain_operands(c, c.train, aux, mode == 2 && !P.gcnOff));
+  RETURN_IF(plain_operands(c, c.train, aux, mode == 2 && !P.gcnOff, mode == 3));
   if (side) HIP_OK(hipEventRecord(g_wf.auxDone, aux));
   float* x0p = c.ws + P.oX0p;
   if (src) RETURN_IF(fuse_padded(c, src->series, x0p, src->label_start, src->rel_steps, src->series_steps));
@@ -1612,10 +1641,10 @@ static int backward_entry(const matgcn_dims* dims, const matgcn_params* params, 
   // the mode the matching forward_train ran with, whatever the setting is now (-1: that forward_train failed)
   const int mode = train_mode_of(train);
   if (mode < 0) return MATGCN_ERR_BAD_ARG;
-  if (mode == 2 && !b.c.P.gcnOff && train_bytes < (size_t)b.c.R.floatsBf16 * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;
+  const long base = train_floats(b.c.P, b.c.R, mode);
+  if (train_bytes < (size_t)base * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;   // sized without mode 2's copies / mode 3's planes
   b.c.prec = precision_of(mode);
   if (g_deterministic) {   // the partial slabs of the ordered reductions sit behind everything this call's mode uses
-    const long base = mode == 2 && !b.c.P.gcnOff ? b.c.R.floatsBf16 : b.c.R.floats;
     if (train_bytes < (size_t)(base + b.c.R.detFloats) * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;
     b.detTail = b.tr + base;
   }

@@ -213,6 +213,13 @@ struct TrainPlan {
   // backward's node-wise data-gradient contractions; matgcn_train_bytes counts it only while mode 2 is set
   long oWp16[MATGCN_MAX_LAYERS][2];
   long floatsBf16;
+  // optional tail, three-piece training only (matgcn_set_train_bf16x3), behind `floats` as well - a train buffer holds one
+  // forward_train, which ran in one mode, so the two tails may share their floats: the three bf16 planes of the plain
+  // stack StP, [piece][slot][nKg][NpC] 16-byte words - every slot's Np reduction indices rounded up to 32, zero-filled
+  // (k_mix_bf16x3, ROLE 2) - written by forward_train beside StP; matgcn_train_bytes counts it only while that mode is
+  // the effective one
+  long oStPl, stPlaneWords;                // first float; words per plane (piece)
+  long floatsX3;
   // optional tail, deterministic backward only (matgcn_set_deterministic), behind whichever of the two ends above the
   // call uses: the partial slabs of the ordered reductions.  Two arenas of detArena floats - one for the sites on the
   // chains' streams, one for the sites on the weight-gradient stream; within a stream every site's slabs are read by
@@ -286,6 +293,9 @@ int make_train_plan(const Plan& P, TrainPlan* R) {
       R->oWp16[l][part] = take(((long)P.N * R->S * I * O + 1) / 2);   // bf16: two values per float slot
     }
   R->floatsBf16 = o;
+  R->oStPl = R->floats;
+  R->stPlaneWords = (long)P.Ks * P.nKg * P.NpC;
+  R->floatsX3 = R->floats + rup(3 * 4 * R->stPlaneWords, 64);
   {
     auto mx = [](long a, long b) { return a > b ? a : b; };
     const long NN = (long)P.N * P.N, nd = nEnt * P.N * P.d, cmax = P.C0 > H ? P.C0 : H;
@@ -306,6 +316,11 @@ int make_train_plan(const Plan& P, TrainPlan* R) {
     R->detFloats = d;
   }
   return MATGCN_OK;
+}
+// floats of the train buffer that a training step in `mode` uses in front of the deterministic slabs: mode 2's bf16 copies
+// of the plain weights, or mode 3's planes of the plain stack, sit behind everything else
+inline long train_floats(const Plan& P, const TrainPlan& R, int mode) {
+  return mode == 2 && !P.gcnOff ? R.floatsBf16 : mode == 3 ? R.floatsX3 : R.floats;
 }
 
 // ---- optional in-situ launch timing (matgcn_profile_*) ------------------------------------------------
@@ -447,7 +462,10 @@ int g_mix_precision = 0;      // matgcn_set_mix_precision: 0 fp32 operands, 1 bf
                               // 2 bf16 operands for the graph mixes AND the node-wise contractions (bf16 weight streams),
                               // 3 three bf16 pieces per operand of the graph mixes (fp32 accuracy on the bf16 pipe)
 int g_train_precision = 0;    // matgcn_set_train_precision: the same values for matgcn_forward_train / matgcn_backward
+int g_train_bf16x3 = 0;       // matgcn_set_train_bf16x3: mode 3 for the training entry points while g_train_precision is 0
 int g_deterministic = 0;      // matgcn_set_deterministic: matgcn_backward adds in a fixed order (slabs + k_ordered_reduce)
+// the mode matgcn_forward_train reads on entry: an explicit bf16 mode (1, 2) wins over the three-piece switch
+inline int effective_train_mode() { return g_train_precision ? g_train_precision : g_train_bf16x3 ? 3 : 0; }
 // The backward follows the mode its forward_train ran with: forward_train notes (device, train buffer) -> mode here and
 // matgcn_backward looks its train buffer up (a buffer without an entry runs with the current setting).  The last
 // TRAIN_MODE_SLOTS buffers are remembered - far more than the one per model a training loop keeps.
@@ -466,7 +484,7 @@ int train_mode_of(const void* train) {
   const int dev = current_device();
   for (int i = 0; i < TRAIN_MODE_SLOTS; ++i)
     if (g_train_modes[i].train == train && g_train_modes[i].dev == dev) return g_train_modes[i].mode;
-  return g_train_precision;
+  return effective_train_mode();
 }
 
 int wavefront_ready() {
@@ -605,9 +623,9 @@ StackMap build_stack_map(const Plan& P, const matgcn_dims* D, const matgcn_param
 }
 
 // The operands of a call: `mix` - of the graph mixes (transposed ones in the backward): fp32, rounded to bf16, or split
-// into three bf16 pieces (inference forwards only: the training setting never holds 3); `node` - bf16 for the node-wise
+// into three bf16 pieces (training: matgcn_set_train_bf16x3, never a value of the training setting); `node` - bf16 for the node-wise
 // contractions (bf16 copies of the weight streams).  The four hot entry points read their mode once, on entry
-// (matgcn_forward / matgcn_forward_series: g_mix_precision; matgcn_forward_train: g_train_precision; matgcn_backward:
+// (matgcn_forward / matgcn_forward_series: g_mix_precision; matgcn_forward_train: effective_train_mode(); matgcn_backward:
 // the mode of its forward_train), and every launch helper below them reads it from the context it is handed.
 enum MixPrec { MIX_F32 = 0, MIX_BF16 = 1, MIX_BF16X3 = 3 };
 struct Precision { MixPrec mix = MIX_F32; bool node = false; };
@@ -709,10 +727,12 @@ const MixVariant MIX[] = {
     {MIX_64x32, MIX_F32, false, 1, k_mix_c32<1>},        {MIX_32x128, MIX_F32, false, 2, k_mix_n32<false>},
     {MIX_32x128, MIX_BF16, false, 2, k_mix_n32<true>},   {MIX_64x64, MIX_BF16, false, 0, k_mix_bf16<0>},
     {MIX_64x64, MIX_BF16, false, 1, k_mix_bf16<1>},      {MIX_64x64, MIX_BF16, false, 2, k_mix_bf16<2>},
-    // three bf16 pieces per operand: the inference forward's mixes (roles 0 and 1), every batch size and graph size
+    // three bf16 pieces per operand: the forwards' mixes (roles 0 and 1), every batch size and graph size, and - three-piece
+    // training only - the backward's transposed mixes on the per-slot planes of the plain stack (role 2)
     {MIX_64x128, MIX_BF16X3, false, 0, k_mix_bf16x3<0>}, {MIX_64x128, MIX_BF16X3, false, 1, k_mix_bf16x3<1>},
     {MIX_64x128, MIX_BF16X3, true, 0, k_mix_bf16x3<0, true>},
     {MIX_64x128, MIX_BF16X3, true, 1, k_mix_bf16x3<1, true>},
+    {MIX_64x128, MIX_BF16X3, false, 2, k_mix_bf16x3<2>}, {MIX_64x128, MIX_BF16X3, true, 2, k_mix_bf16x3<2, true>},
 };
 // launches the table's entry for the selectors over `rows` output rows: grid.x = row tiles x column units of the entry's
 // tile shape (k_mix_bf16x3 alone takes an odd number of column tiles in pairs: rounded up), grid.y = a.parts; a
@@ -1316,6 +1336,12 @@ int matgcn_set_train_precision(int mode) {
   return prev;
 }
 
+int matgcn_set_train_bf16x3(int enabled) {
+  const int prev = g_train_bf16x3;
+  g_train_bf16x3 = enabled != 0 ? 1 : 0;
+  return prev;
+}
+
 int matgcn_set_deterministic(int enabled) {
   const int prev = g_deterministic;
   g_deterministic = enabled != 0 ? 1 : 0;
@@ -1361,7 +1387,8 @@ int matgcn_workspace_bytes(const matgcn_dims* dims, size_t* bytes) {
   RETURN_IF(make_plan(dims, &P));
   const bool bf16Streams = g_mix_precision == 2 || g_train_precision == 2;
   long floats = bf16Streams ? P.workspaceFloatsBf16 : P.workspaceFloats;
-  if (g_mix_precision == 3 && P.workspaceFloatsX3 > floats) floats = P.workspaceFloatsX3;   // the planes of mode 3
+  // the planes of mode 3: of an inference forward, or of a three-piece forward_train
+  if ((g_mix_precision == 3 || effective_train_mode() == 3) && P.workspaceFloatsX3 > floats) floats = P.workspaceFloatsX3;
   *bytes = (size_t)floats * sizeof(float);
   return MATGCN_OK;
 }

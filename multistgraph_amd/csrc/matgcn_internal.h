@@ -87,6 +87,10 @@ struct MixArgs {
   // St, each [Np32 / 8][ldS] 16-byte words of 8 consecutive reduction indices (k_split_bf16x3), plStride words apart
   const void* Apl = nullptr;
   long plStride = 0;
+  // role 2 (the backward's transposed mixes): the planes are those of the plain stack, padded PER SLOT -
+  // [slot][Np32 / 8][ldS] words - nK counts one slot's groups of 16, and a part walks kSlots slots back to back
+  // (aPartStride is in words there)
+  int kSlots = 1;
 };
 
 struct HeadArgs {

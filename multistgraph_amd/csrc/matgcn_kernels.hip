@@ -1249,6 +1249,15 @@ __global__ __launch_bounds__(256) void k_mix_bf16(MixArgs a) {
 // second buffer (3 x 72 KB > 160 KB) would cost the third.  An odd number of column tiles: the last pair's second half is fetched
 // from the first (clamped) and not stored.  FLUSH as k_mix: partial sums every 8 K-tiles (256 reduction indices), N > 1024.
 // Tile order and the store epilogue are the shared ones (mix_tile_order, mix_store_tile: twice per wave, 32 columns each).
+// ROLE 2 (matgcn_set_train_bf16x3: the backward's transposed mixes on the plain stack StP [Ks*Np][NpC], launch_mix_plain):
+// the reduction runs over support slots of Np indices each, and Np is a multiple of 16, not of the K-tile's 32 - the last
+// K-tile of a slot must not run into the next slot's first 16 rows, which are not zero.  ONE plane layout for every
+// role-2 launch: planes[piece][slot][nKg][NpC] words, every slot's Np reduction indices rounded up to 32 and zero-filled
+// (k_split_bf16x3 per slot, nKg = 4 K-tiles-per-slot), so slot k's K-tile t is K-tile k * nT + t of the planes; the B rows
+// of a slot's last K-tile are clamped to the slot's last row, where the planes hold zeros.  a.nK counts ONE slot's groups
+// of 16; a workgroup walks a.kSlots slots back to back: 1 when the launch splits the reduction by slot (part =
+// blockIdx.y: planes a.aPartStride WORDS, B rows a.xPartStride and output a.outPartStride floats further per part),
+// all Ks of them when it does not (parts == 1).  FLUSH counts K-tiles across the slots of a part.
 typedef __bf16 bf16x2v_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned int pack_bf16_pair(float lo, float hi) {    // round to nearest even, lo in bits 0..15
   const bf16x2v_t v = {(__bf16)lo, (__bf16)hi};
@@ -1292,23 +1301,42 @@ __global__ __launch_bounds__(256) void k_mix_bf16x3(MixArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1, j = lane & 15, kq = lane >> 4;
   const int kLast = 16 * a.nK - 1;                         // reduction indices 0 .. Np-1 (a.nK = Np / 16)
-  const int nT = (a.nK + 1) >> 1;                          // K-tiles of 32
+  const int nT = (a.nK + 1) >> 1;                          // K-tiles of 32 (ROLE 2: of one slot)
+  const int nTot = ROLE == 2 ? a.kSlots * nT : nT;         // K-tiles of this workgroup's reduction
+  const int part = ROLE == 2 ? (int)blockIdx.y : 0;
   // staging: k-group skg of the tile; A row sr (one word per piece), B columns 2 sr, 2 sr + 1 of the 128
   const int skg = tid >> 6, sr = tid & 63;
   const u32x4* ap = reinterpret_cast<const u32x4*>(a.Apl) + (size_t)skg * a.ldS + row0 + sr;
   const int bcol = 2 * sr;
   const int bTile = min(2 * colPair + (bcol >> 6), a.nColTiles - 1);
   const float* bp = a.X + (size_t)bTile * a.xTileStride + (bcol & 63);
+  if constexpr (ROLE == 2) {
+    ap += (size_t)part * a.aPartStride;
+    bp += (size_t)part * a.xPartStride;
+  }
   u32x4 ra[3];
   float2 rb[8];
+  int nxSlot = 0, nxT = 0;       // ROLE 2: slot, and K-tile within it, of the next load (the loads come in tile order)
   auto load = [&](int t) {
-    const int tc = min(t, nT - 1);
+    if constexpr (ROLE == 2) {
+      const int tc = nxSlot * nT + nxT, rowBase = nxSlot * 16 * a.nK;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) ra[p] = ap[(size_t)p * a.plStride + (size_t)tc * 4 * a.ldS];
+      for (int p = 0; p < 3; ++p) ra[p] = ap[(size_t)p * a.plStride + (size_t)tc * 4 * a.ldS];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      // (a reduction index past the last one repeats the last row: its St words are zero in every plane)
-      rb[i] = *reinterpret_cast<const float2*>(bp + (size_t)min(32 * tc + 8 * skg + i, kLast) * a.ldX);
+      for (int i = 0; i < 8; ++i) {
+        // (past the slot's last index: its last row again - the planes are zero there, the next slot's rows are not)
+        rb[i] = *reinterpret_cast<const float2*>(bp + (size_t)(rowBase + min(32 * nxT + 8 * skg + i, kLast)) * a.ldX);
+      }
+      if (t + 1 < nTot && ++nxT == nT) { nxT = 0; ++nxSlot; }   // (clamped past the end: the last tile again, unused)
+    } else {
+      const int tc = min(t, nT - 1);
+#pragma unroll
+      for (int p = 0; p < 3; ++p) ra[p] = ap[(size_t)p * a.plStride + (size_t)tc * 4 * a.ldS];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        // (a reduction index past the last one repeats the last row: its St words are zero in every plane)
+        rb[i] = *reinterpret_cast<const float2*>(bp + (size_t)min(32 * tc + 8 * skg + i, kLast) * a.ldX);
+      }
     }
   };
   auto store = [&]() {
@@ -1365,10 +1393,10 @@ __global__ __launch_bounds__(256) void k_mix_bf16x3(MixArgs a) {
       for (int p = 0; p < 2; ++p) acc[q >> 1][p][q & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0][p], bh, acc[q >> 1][p][q & 1], 0, 0, 0);
     }
   };
-  for (int t = 0; t < nT; ++t) {
+  for (int t = 0; t < nTot; ++t) {
     mma();                       // tile t
     __syncthreads();             // every wave has read tile t
-    if (t + 1 < nT) {
+    if (t + 1 < nTot) {
       store();                   // tile t+1
       load(t + 2);               // (clamped past the end: unused)
     }
@@ -1400,7 +1428,7 @@ __global__ __launch_bounds__(256) void k_mix_bf16x3(MixArgs a) {
   if (colTile < a.nColTiles) {
     float* stg = reinterpret_cast<float*>(&Bs[0][0][0]) + w * 1024;
 #pragma unroll
-    for (int half = 0; half < 2; ++half) mix_store_tile(a, 0, stg, acc[half], row0 + wr * 32, colTile, half * 32);
+    for (int half = 0; half < 2; ++half) mix_store_tile(a, part, stg, acc[half], row0 + wr * 32, colTile, half * 32);
   }
 }
 

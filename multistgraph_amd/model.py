@@ -113,8 +113,10 @@ def _is_series_batch(batch) -> bool:
     return isinstance(batch, dict) and "label_start" in batch and "series" in batch
 
 
-# config['hip_precision'] -> matgcn_set_*_precision mode ("bf16x3": an inference mode - the training setting reads 3 as 0)
-HIP_PRECISIONS = {"fp32": 0, "bf16_mix": 1, "bf16": 2, "bf16x3": 3}
+# config['hip_precision'] -> matgcn_set_*_precision mode ("bf16x3": an inference mode - the training setting reads 3 as 0;
+# "bf16x3_train": the same inference mode, and matgcn_set_train_bf16x3 around the training steps)
+HIP_PRECISIONS = {"fp32": 0, "bf16_mix": 1, "bf16": 2, "bf16x3": 3, "bf16x3_train": 3}
+HIP_TRAIN_BF16X3 = ("bf16x3_train",)
 
 
 def _precision_mode(name) -> int:
@@ -172,7 +174,8 @@ class MultiATGCN(AbstractTrafficStateModel):
         # operand precision of the HIP kernels (not a reference key): "fp32" (default) | "bf16_mix" (bf16 operands for the
         # graph mixes) | "bf16" (also for the node-wise contractions) | "bf16x3" (the graph mixes of the inference forwards
         # from three bf16 pieces per operand: fp32 accuracy on the bf16 matrix instruction; training steps of such a model
-        # run in fp32); fp32 accumulation and fp32 state, parameters and gradients in every mode.  Applies to this model's
+        # run in fp32) | "bf16x3_train" (as "bf16x3", and the graph mixes of the training step - forward and transposed -
+        # from three bf16 pieces as well); fp32 accumulation and fp32 state, parameters and gradients in every mode.  Applies to this model's
         # inference forwards and training steps; an attribute, so a model can train in bf16 and evaluate in fp32 by
         # reassigning it.
         self.hip_precision = get("hip_precision", "fp32")
@@ -318,6 +321,7 @@ class MultiATGCN(AbstractTrafficStateModel):
         # key existed); the bf16 modes are set around each of this model's library calls and restored afterwards
         mode = _precision_mode(self.hip_precision)
         hp.precision = mode if mode else None
+        hp.train_bf16x3 = True if self.hip_precision in HIP_TRAIN_BF16X3 else None
         hp.deterministic = self._deterministic()
         key = (id(hp),) + self._params_key()
         if key != self._prepared_key or not self.cache_prepared:

@@ -325,6 +325,11 @@ class HotPath:
         # and restored afterwards - around forward_train too, which sizes the train buffer with the partial slabs of the
         # ordered reductions -, None (default) leaves the process-wide setting as it is
         self.deterministic: Optional[bool] = None
+        # three-piece training (matgcn_set_train_bf16x3: the graph mixes of the training step, both directions, from three
+        # bf16 pieces per operand - fp32 accuracy; an explicit bf16 training mode, precision 1 or 2, wins over it): True /
+        # False are set around forward_train - which sizes both buffers with the mode's planes - and backward and
+        # restored afterwards, None (default) leaves the process-wide setting as it is
+        self.train_bf16x3: Optional[bool] = None
 
     # ---- plumbing ------------------------------------------------------------------------------
     def _stream(self):
@@ -339,7 +344,8 @@ class HotPath:
         """Run ``call(ws_ptr, ws_bytes)``; a workspace that is too small for the CURRENT library mode - precision mode 2
         or 3 was switched on after this binding sized it: the bf16 weight-stream copies (mode 2) and the three bf16 planes
         of the support stack (mode 3) are counted only while their mode is set - is re-sized once and the call repeated (train: the train buffer too - matgcn_train_bytes counts the bf16
-        copies of the plain weights while training precision mode 2 is set)."""
+        copies of the plain weights while training precision mode 2 is set, and the planes of the plain support stack
+        while the three-piece training switch is the effective mode)."""
         ws, wsb = self._ws()
         status = call(ws, wsb)
         if status == -4:      # MATGCN_ERR_SMALL_BUFFER
@@ -372,17 +378,24 @@ class HotPath:
         finally:
             setter(prev)
 
-    @contextlib.contextmanager
     def _det(self):
         """the library's deterministic-backward setting at this binding's value for the calls inside (None: untouched)"""
-        if self.deterministic is None:
+        return self._switch(self.lib.matgcn_set_deterministic, self.deterministic)
+
+    def _x3(self):
+        """the library's three-piece training switch at this binding's value for the calls inside (None: untouched)"""
+        return self._switch(self.lib.matgcn_set_train_bf16x3, self.train_bf16x3)
+
+    @contextlib.contextmanager
+    def _switch(self, setter, value: Optional[bool]):
+        if value is None:
             yield
             return
-        prev = self.lib.matgcn_set_deterministic(1 if self.deterministic else 0)
+        prev = setter(1 if value else 0)
         try:
             yield
         finally:
-            self.lib.matgcn_set_deterministic(prev)
+            setter(prev)
 
     def bind(self, state: Dict[str, torch.Tensor], static_supports: Optional[torch.Tensor]):
         """Point matgcn_params at the tensors of a reference-named state dict."""
@@ -541,7 +554,7 @@ class HotPath:
         h0 = self._h0(h0)
         self._need_prepared()
         out = torch.empty(self.batch, s.out_window, s.nodes, s.out_dim, dtype=torch.float32, device=self.device)
-        with self._mode(self.lib.matgcn_set_train_precision), self._det():
+        with self._mode(self.lib.matgcn_set_train_precision), self._x3(), self._det():
             self._train_buffer()
             self._with_workspace(lambda ws, wsb: self.lib.matgcn_forward_train(
                 C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
@@ -625,7 +638,7 @@ class HotPath:
             raise _lib.MatgcnError("backward() without a forward_train() before it")
         ws, wsb = self._ws()   # (the workspace and the train buffer as forward_train left them: no re-sizing here - a
         # deterministic backward behind a forward_train that ran without the setting reports MATGCN_ERR_SMALL_BUFFER)
-        with self._det():
+        with self._x3(), self._det():
             status = self.lib.matgcn_backward(C.byref(self.dims), C.byref(self.params),
                                             C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
                                             C.byref(src) if src is not None else None,

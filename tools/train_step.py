@@ -1,8 +1,10 @@
 """Training steps of the bench workload (default Baltimore 403, B=64): forward_train + backward through the plugin
 surface (calculate_loss().backward()), timed with HIP events.
-usage: train_step.py [--deterministic] [workload] [steps] [serial|wave] [batch] [fp32|bf16_mix|bf16]
+usage: train_step.py [--deterministic] [--bf16x3] [workload] [steps] [serial|wave] [batch] [fp32|bf16_mix|bf16]
 (--deterministic: the model's hip_deterministic = True - the backward's sums in a fixed order, see matgcn_set_deterministic;
 the summary line then also gives the bytes the train buffer grew by)
+(--bf16x3: the model's hip_precision = "bf16x3_train" - the step's graph mixes, both directions, from three bf16 pieces,
+see matgcn_set_train_bf16x3; a hip_precision argument wins over it)
 (serial: matgcn_set_wavefront(0) - every kernel alone on one stream, so a profiler's durations are the kernels' own;
 the last argument is the model's hip_precision; the last line gives the medians over the steps after the first three)"""
 import os, sys
@@ -14,6 +16,9 @@ from multistgraph_amd import synthetic as syn
 deterministic = "--deterministic" in sys.argv
 if deterministic:
     sys.argv.remove("--deterministic")
+bf16x3 = "--bf16x3" in sys.argv
+if bf16x3:
+    sys.argv.remove("--bf16x3")
 name = sys.argv[1] if len(sys.argv) > 1 else "bm403"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 w = dict(bench.WORKLOADS[name])
@@ -23,6 +28,8 @@ dev = torch.device("cuda:0")
 model, df, cfg = bench.build_model(w, dev, 0)
 model.train()
 model.hip_deterministic = deterministic
+if bf16x3:
+    model.hip_precision = "bf16x3_train"
 if len(sys.argv) > 5:
     model.hip_precision = sys.argv[5]
 if len(sys.argv) > 3 and sys.argv[3] == "serial":
