@@ -34,6 +34,10 @@
  * Still ABI 12: matgcn_set_train_bf16x3 is one more symbol, on the same terms - with it at its default (0) every entry
  * point launches the kernels ABI 12 defined, with their arguments and bits, and both *_bytes() give its numbers;
  * matgcn_set_train_precision keeps every value's meaning (3 included: it means 0).
+ * Still ABI 12: device-side dropout adds five names - the struct matgcn_dropout and the functions matgcn_dropout_mask,
+ * matgcn_forward_train_seeded, matgcn_backward_seeded, matgcn_forward_mc - and nothing else changes: no existing symbol,
+ * signature or struct changed, both *_bytes() give their numbers, and a caller that hands matgcn_forward_train /
+ * matgcn_backward a mask tensor (or NULL) launches the kernels ABI 12 defined, with their arguments and bits.
  */
 #ifndef MATGCN_H
 #define MATGCN_H
@@ -355,6 +359,67 @@ int matgcn_backward(const matgcn_dims* dims, const matgcn_params* params, const 
  * mode (0: C = alpha*acc + beta*C; 1: atomic add into C), split (K ranges per output tile, mode 1). */
 int matgcn_debug_gemm(const float* A, const float* B, float* C, const int64_t* desc, float alpha, float beta,
                       void* stream);
+
+/* ---- device-side dropout: seeded training masks and Monte-Carlo-dropout forecasts --------------------------------------
+ * The dropout in front of end_conv (MultiATGCN.py:416) drawn INSIDE the kernels that apply it, from a counter-based
+ * generator, so that no mask tensor exists anywhere: the descriptor below stands for a (B, headT, N, 64) tensor of
+ * multipliers 0 or 1/(1-p) - headT = T, or 1 with fnn_off; 64 is the kernel-visible width, zero-padded models included -
+ * that the library never materialises (matgcn_dropout_mask writes it out for whoever wants to look).
+ * Generator: Philox4x32-10 (Random123; multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85).
+ *   key = (lo32(seed), hi32(seed));  counter = (lo32(q), hi32(q), lo32(offset), hi32(offset)),  q = idx >> 2,
+ *   idx = ((b*headT + t')*N + n)*64 + h the element's position in the logical mask - independent of the padded node
+ *   count, tiles, row variants and schedule;  output word idx & 3 decides element idx:  kept iff word >= thr,
+ *   thr = floor((double)p * 2^32) (p = 0.1f: 429496736);  a kept element is multiplied by (float)(1.0 / (1.0 - (double)p)),
+ *   a dropped one by 0.  Monte-Carlo sample s of matgcn_forward_mc draws with offset + s.
+ * A host struct, read at call time; 0 <= p < 1, anything else (NaN included) is MATGCN_ERR_BAD_ARG.  A training loop
+ * advances `offset` by one per step; ranks of a data-parallel job use disjoint offset ranges. */
+typedef struct matgcn_dropout {
+  uint64_t seed;
+  uint64_t offset;
+  float p;
+} matgcn_dropout;
+
+#define MATGCN_MAX_MC_SAMPLES 1024
+
+/* Writes the (B, headT, N, 64) mask the descriptor stands for (for tests, and for callers that want to look at it). */
+int matgcn_dropout_mask(const matgcn_dims* dims, const matgcn_dropout* dropout, float* mask, void* stream);
+
+/* matgcn_forward_train / matgcn_backward with the descriptor in place of drop_mask (NULL = no dropout).  Bit for bit
+ * what the unseeded pair gives on the mask matgcn_dropout_mask writes for the same descriptor - `out`, the saved
+ * activations, and with matgcn_set_deterministic(1) every gradient - without the tensor: graph models draw in the top
+ * layer's update kernel as it stores the sequence (the SEED instantiations of k_update16), gcn_off models in one
+ * element-wise pass (k_apply_dropout), and the backward draws again in the epilogue of the head's data gradient
+ * (k_bgemm<BG_HEAD_SEED>).  The backward must get the descriptor its forward got, as it must get the same mask tensor
+ * today.  Every setting (training precision, three-piece training, deterministic, wavefront) applies as to the unseeded
+ * pair; matgcn_train_bytes and matgcn_workspace_bytes are unchanged.
+ * Measured at Baltimore 403 / B = 64 (MI355X, tools/train_step.py [--device-dropout] bm403 33, one box and one session, the
+ * parent build, this build and this build seeded alternating twice, median of 30 steps each): seeded
+ * training step 21.47 / 21.41 ms, forward_train 7.59 / 7.48, backward 13.74 / 13.78 - against the parent's step with torch
+ * drawing the mask 21.45 / 21.63 ms (7.71 / 7.58, 13.57 / 13.91) and this build's unseeded step 21.58 / 21.55 ms: all three
+ * level within run-to-run noise; no speed-up is claimed, the mask tensor (158 466 048 bytes at this shape) is what goes. */
+int matgcn_forward_train_seeded(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
+                                const matgcn_series* src, const float* h0, const matgcn_dropout* dropout, float* out,
+                                void* workspace, size_t workspace_bytes, void* train, size_t train_bytes, void* stream);
+int matgcn_backward_seeded(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
+                           const matgcn_series* src, const float* h0, const matgcn_dropout* dropout, const float* d_out,
+                           const matgcn_grads* grads, float* d_h0, void* workspace, size_t workspace_bytes, void* train,
+                           size_t train_bytes, void* stream);
+
+/* Monte-Carlo dropout: the eval-mode encoder ONCE - the kernels and the precision mode of matgcn_forward /
+ * matgcn_forward_series (src != NULL: the batch comes from the series, X is ignored) - then the head over `samples`
+ * masks (1 .. MATGCN_MAX_MC_SAMPLES, else MATGCN_ERR_BAD_ARG) in one launch (k_head_mc): sample s is the head of
+ * seq * mask(seed, offset + s), with k_head's reduction order - bit-equal to matgcn_output_head on that product.
+ * mean, std: (B, out, N, od); std is the POPULATION standard deviation over the samples, formed around a running mean
+ * (Welford) in fp32 - exactly 0 for samples == 1.  samples_out: (samples, B, out, N, od), or NULL.
+ * The head's 24 steps of a (b, 32-node) tile stay in registers over all samples (6 steps x 8 float4 per lane, one wave
+ * per SIMD): in_steps > 24 without fnn_off returns MATGCN_ERR_UNSUPPORTED.  Workspace as matgcn_forward.
+ * Measured at Baltimore 403 / B = 64 (MI355X, tools/mc_time.py bm403 20 32 128, median of 20 calls, HIP events): 9.09 ms at
+ * S = 32 and 16.85 ms at S = 128 against 6.46 ms for one matgcn_forward of the same process - 81-82 us per sample (S
+ * host-loop forwards: 207 / 827 ms).  k_head_mc's own duration under a kernel trace has NOT been measured yet (DESIGN.md
+ * section 5d says why, and that its register budget must be re-read from the ISA after a compiler change). */
+int matgcn_forward_mc(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
+                      const matgcn_series* src, const float* h0, const matgcn_dropout* dropout, int samples, float* mean,
+                      float* std, float* samples_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- scheduling option ------------------------------------------------------------------------
  * The encoder runs the recurrent chains of the layers as a wavefront on internal HIP streams (created once, on

@@ -50,6 +50,14 @@ class Series(C.Structure):
                 ("rel_steps", C.POINTER(C.c_int32))]
 
 
+class Dropout(C.Structure):
+    """matgcn_dropout: the descriptor of a device-side dropout mask (seed, offset, p) - no tensor behind it"""
+    _fields_ = [("seed", C.c_uint64), ("offset", C.c_uint64), ("p", C.c_float)]
+
+
+MAX_MC_SAMPLES = 1024
+
+
 class Params(C.Structure):
     _fields_ = [
         ("node_emb", C.c_void_p), ("node_vec1", C.c_void_p), ("node_vec2", C.c_void_p),
@@ -107,6 +115,13 @@ _SIGNATURES = {
     # matgcn_grads has the layout of matgcn_params (non-const pointers): the same ctypes struct serves both
     "matgcn_backward": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), _P, _P, C.POINTER(Series), _P, _P, _P,
                                   C.POINTER(Params), _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "matgcn_dropout_mask": (C.c_int, [C.POINTER(Dims), C.POINTER(Dropout), _P, _P]),
+    "matgcn_forward_train_seeded": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), _P, _P, C.POINTER(Series), _P,
+                                              C.POINTER(Dropout), _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "matgcn_backward_seeded": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), _P, _P, C.POINTER(Series), _P,
+                                         C.POINTER(Dropout), _P, C.POINTER(Params), _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "matgcn_forward_mc": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), _P, _P, C.POINTER(Series), _P, C.POINTER(Dropout),
+                                    C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
     "matgcn_debug_gemm": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int64), C.c_float, C.c_float, _P]),
     "matgcn_set_wavefront": (C.c_int, [C.c_int]),
     "matgcn_set_stream_pool": (C.c_int, [C.c_int]),

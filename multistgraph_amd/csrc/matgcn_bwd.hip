@@ -131,12 +131,17 @@ const GemmRole BGEMM[] = {
     {BG_X_MIX, k_bgemm<BG_X_MIX>, nullptr},             {BG_WGRAD, k_bgemm<BG_WGRAD>, k_bgemm_tn<BG_WGRAD>},
     {BG_ADJ, k_bgemm<BG_ADJ>, nullptr},                 {BG_LINEAR, k_bgemm<BG_LINEAR>, k_bgemm_tn<BG_LINEAR>},
     {BG_POOL, k_bgemm<BG_POOL>, nullptr},               {BG_HEAD, k_bgemm<BG_HEAD>, nullptr},
+    {BG_HEAD_SEED, k_bgemm<BG_HEAD_SEED>, nullptr},
 };
 
 int gemm(const GemmArgs& g, int nb1, hipStream_t s, int role = BG_GENERIC) {
   if (g.M <= 0 || g.N <= 0 || g.K <= 0 || g.K2 <= 0 || nb1 <= 0) return MATGCN_OK;
   const long gx = (g.N + 63) / 64, gy = (g.M + 63) / 64, gz = (long)nb1 * g.nb2 * g.split;
   if (gy > 65535 || gz > 65535 || (long)g.K2 * ((g.K + BG_KT - 1) / BG_KT) >= (1L << 30)) return MATGCN_ERR_UNSUPPORTED;
+  // BG_HEAD_SEED draws four columns of one mask row per Philox call and shares them inside aligned quads of lanes: the
+  // mask's columns must be the GEMM's (unit stride, whole quads per row, rows and batch items that start on a quad)
+  if (role == BG_HEAD_SEED && (!g.drop.on || g.scaleC || g.sSn != 1 || (g.N & 3) || (g.sSm & 3) || (g.bS1 & 3) || (g.bS2 & 3)))
+    return MATGCN_ERR_UNSUPPORTED;
   const GemmRole* r = find_variant(BGEMM, [&](auto& e) { return e.role == role; });
   if (!r) r = &BGEMM[0];   // a role without an entry only names a call site: it runs as BG_GENERIC
   const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)gz);
@@ -148,6 +153,7 @@ struct Bwd {
   Ctx c;
   const float* X;
   const float* dropMask;
+  DropDesc drop = {};       // matgcn_backward_seeded: the dropout of its forward from the generator (drop.on), no tensor
   const matgcn_grads* g;
   float* tr;
   const matgcn_series* src = nullptr;   // series mode: X rows are gathered from the raw series
@@ -671,7 +677,7 @@ int bwd_head(Pass& pass, const float* dOut) {
   auto pad_pow2 = [](int v) { int p2 = 1; while (p2 < v) p2 <<= 1; return p2; };
   RETURN_IF(zero_async(g->end_conv_bias, P.CH, s));
   RETURN_IF(colsum_all(b, 256, dOutRows, (size_t)B, P.CH, pad_pow2(P.CH), g->end_conv_bias));
-  const float* seqTop = b.dropMask ? tr + R.oSeqDrop : c.ws + P.oSeq[P.L - 1];   // what the head convolved
+  const float* seqTop = (b.dropMask || b.drop.on) ? tr + R.oSeqDrop : c.ws + P.oSeq[P.L - 1];   // what the head convolved
   float* dSeq = tr + R.oDSeq[0];
   {
     GemmArgs q = gemm_args(dOutRows, prm->end_conv_weight, dSeq + (size_t)tOff * slab, N, H, P.CH);
@@ -682,7 +688,11 @@ int bwd_head(Pass& pass, const float* dOut) {
     if (b.dropMask) {   // the dropout mask (B, hT, N, H) of the steps the head saw, applied where the gradient is produced
       q.scaleC = b.dropMask; q.bS1 = (long)N * H; q.bS2 = (long)hT * N * H; q.sSm = H; q.sSn = 1;
     }
-    RETURN_IF(gemm(q, hT, s, BG_HEAD));   // (a row-per-16-lanes VALU kernel for this K = CH product was measured: 205 vs 154 us)
+    if (b.drop.on) {    // the same multipliers drawn in the epilogue: position in the logical (B, hT, N, H) mask, same strides
+      q.drop = b.drop; q.bS1 = (long)N * H; q.bS2 = (long)hT * N * H; q.sSm = H; q.sSn = 1;
+      static_assert(H % 64 == 0, "BG_HEAD_SEED: whole quads of columns per row, tiles that start on a quad");
+    }
+    RETURN_IF(gemm(q, hT, s, b.drop.on ? BG_HEAD_SEED : BG_HEAD));   // (a row-per-16-lanes VALU kernel for this K = CH product was measured: 205 vs 154 us)
     // the head's weight gradient feeds nothing in this pass: with two streams it runs on the second one (behind the
     // operand preparation, joined with the last layer's weight gradients) instead of in front of the first chain
     hipStream_t hs = s;
@@ -1533,10 +1543,14 @@ int matgcn_train_bytes(const matgcn_dims* dims, size_t* bytes) {
   return MATGCN_OK;
 }
 
+// seeded (matgcn_forward_train_seeded; null or !on: none): the dropout from the generator in place of drop_mask
 static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
-                              const matgcn_series* src, const float* h0, const float* drop_mask, float* out,
-                              void* workspace, size_t workspace_bytes, void* train, size_t train_bytes, void* stream) {
+                              const matgcn_series* src, const float* h0, const float* drop_mask, const DropDesc* seeded,
+                              float* out, void* workspace, size_t workspace_bytes, void* train, size_t train_bytes,
+                              void* stream) {
   if (!prepared || (!X && !src) || !out || !train) return MATGCN_ERR_NULL;
+  const bool seed = seeded && seeded->on;
+  if (seed && drop_mask) return MATGCN_ERR_BAD_ARG;
   if (src) RETURN_IF(check_series(dims, src->series, src->series_steps, src->label_start, src->rel_steps));
   Ctx c;
   // (a lazy matgcn_prepare: the encoder's chains wait for the weight streams they read, as in the inference forward;
@@ -1587,8 +1601,11 @@ static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* para
   else RETURN_IF(fuse_padded(c, X, x0p));
   // graph layers: the top layer's update kernel writes the dropped-out sequence beside the plain one (a pass of its own
   // over 3 x 163 MB used to sit between the encoder and the head, 0.14 ms that nothing hides)
-  const bool fusedDrop = drop_mask != nullptr && !P.gcnOff;
-  if (fusedDrop) c.dropMask = drop_mask;
+  const bool fusedDrop = (drop_mask != nullptr || seed) && !P.gcnOff;
+  if (fusedDrop) {
+    if (seed) c.drop = *seeded;   // the SEED instantiations of the top layer's update kernel: no mask tensor
+    else c.dropMask = drop_mask;
+  }
   RETURN_IF(encoder_padded(c, x0p, h0, nullptr));
   if (side) HIP_OK(hipStreamWaitEvent(c.s, g_wf.auxDone, 0));
   const float* seqTop = c.ws + P.oSeq[P.L - 1];
@@ -1601,6 +1618,13 @@ static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* para
                        drop_mask, dropped + ofs, P.B, P.headT, P.N, P.Np);
     CHECK_LAUNCH();
     seqTop = dropped;
+  } else if (seed) {        // the same pass with the multipliers drawn in the kernel
+    const size_t ofs = (size_t)(P.T - P.headT) * P.B * P.Np * H;
+    float* dropped = c.train + c.R.oSeqDrop;
+    hipLaunchKernelGGL(k_apply_dropout, dim3(blocks_for((size_t)P.headT * P.B * P.Np * (H / 4))), dim3(256), 0, c.s,
+                       seqTop + ofs, *seeded, dropped + ofs, P.B, P.headT, P.N, P.Np);
+    CHECK_LAUNCH();
+    seqTop = dropped;
   }
   RETURN_IF(head_padded(c, seqTop, out));
   note_train_mode(train, mode);
@@ -1610,9 +1634,10 @@ static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* para
 // a failure between a fork onto the library streams and their join (side stream of the plain operands, the layers'
 // chains) joins them into the caller's stream before the error code is returned (join_library_streams)
 static int forward_train_entry(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
-                               const matgcn_series* src, const float* h0, const float* drop_mask, float* out, void* workspace,
-                               size_t workspace_bytes, void* train, size_t train_bytes, void* stream) {
-  JOINED(forward_train_impl(dims, params, prepared, X, src, h0, drop_mask, out, workspace, workspace_bytes, train,
+                               const matgcn_series* src, const float* h0, const float* drop_mask, const DropDesc* seeded,
+                               float* out, void* workspace, size_t workspace_bytes, void* train, size_t train_bytes,
+                               void* stream) {
+  JOINED(forward_train_impl(dims, params, prepared, X, src, h0, drop_mask, seeded, out, workspace, workspace_bytes, train,
                             train_bytes, stream), stream);
 }
 
@@ -1620,13 +1645,25 @@ int matgcn_forward_train(const matgcn_dims* dims, const matgcn_params* params, c
                          const matgcn_series* src, const float* h0, const float* drop_mask, float* out, void* workspace,
                          size_t workspace_bytes, void* train, size_t train_bytes, void* stream) {
   return on_main_stream(stream, [&](void* s) {
-    return forward_train_entry(dims, params, prepared, X, src, h0, drop_mask, out, workspace, workspace_bytes, train,
+    return forward_train_entry(dims, params, prepared, X, src, h0, drop_mask, nullptr, out, workspace, workspace_bytes,
+                               train, train_bytes, s);
+  });
+}
+
+int matgcn_forward_train_seeded(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
+                                const matgcn_series* src, const float* h0, const matgcn_dropout* dropout, float* out,
+                                void* workspace, size_t workspace_bytes, void* train, size_t train_bytes, void* stream) {
+  DropDesc d = {};
+  if (dropout) RETURN_IF(make_drop_desc(dropout, &d));
+  return on_main_stream(stream, [&](void* s) {
+    return forward_train_entry(dims, params, prepared, X, src, h0, nullptr, &d, out, workspace, workspace_bytes, train,
                                train_bytes, s);
   });
 }
 
 static int backward_entry(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
-                          const matgcn_series* src, const float* h0, const float* drop_mask, const float* d_out,
+                          const matgcn_series* src, const float* h0, const float* drop_mask, const DropDesc* seeded,
+                          const float* d_out,
                           const matgcn_grads* grads, float* d_h0, void* workspace, size_t workspace_bytes, void* train,
                           size_t train_bytes, void* stream) {
   if (!prepared || (!X && !src) || !d_out || !grads || !train) return MATGCN_ERR_NULL;
@@ -1637,6 +1674,10 @@ static int backward_entry(const matgcn_dims* dims, const matgcn_params* params, 
   RETURN_IF(make_train_plan(b.c.P, &b.c.R));
   if (train_bytes < (size_t)b.c.R.floats * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;
   b.X = X; b.dropMask = drop_mask; b.g = grads; b.tr = (float*)train;
+  if (seeded && seeded->on) {
+    if (drop_mask) return MATGCN_ERR_BAD_ARG;
+    b.drop = *seeded;
+  }
   b.hasH0 = h0 != nullptr; b.dH0 = d_h0; b.src = src;
   // the mode the matching forward_train ran with, whatever the setting is now (-1: that forward_train failed)
   const int mode = train_mode_of(train);
@@ -1656,7 +1697,19 @@ int matgcn_backward(const matgcn_dims* dims, const matgcn_params* params, const 
                     const matgcn_grads* grads, float* d_h0, void* workspace, size_t workspace_bytes, void* train,
                     size_t train_bytes, void* stream) {
   return on_main_stream(stream, [&](void* s) {
-    return backward_entry(dims, params, prepared, X, src, h0, drop_mask, d_out, grads, d_h0, workspace, workspace_bytes,
+    return backward_entry(dims, params, prepared, X, src, h0, drop_mask, nullptr, d_out, grads, d_h0, workspace,
+                          workspace_bytes, train, train_bytes, s);
+  });
+}
+
+int matgcn_backward_seeded(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
+                           const matgcn_series* src, const float* h0, const matgcn_dropout* dropout, const float* d_out,
+                           const matgcn_grads* grads, float* d_h0, void* workspace, size_t workspace_bytes, void* train,
+                           size_t train_bytes, void* stream) {
+  DropDesc d = {};
+  if (dropout) RETURN_IF(make_drop_desc(dropout, &d));
+  return on_main_stream(stream, [&](void* s) {
+    return backward_entry(dims, params, prepared, X, src, h0, nullptr, &d, d_out, grads, d_h0, workspace, workspace_bytes,
                           train, train_bytes, s);
   });
 }

@@ -11,6 +11,7 @@
 #define MATGCN_BWD_KERNELS_HIP
 
 // f32x4 / MFMA16 / sigmoid_f / cheb_scalar / StackMap come from matgcn_kernels.hip (same translation unit)
+#include "matgcn_philox.h"
 
 // ---- generic strided batched GEMM ------------------------------------------------------------------------
 //   C[b1][b2][m][n] (+)= alpha * sum_{k2 < K2} sum_{k < K} A[b1][b2][m][k2][k] * B[b1][b2][k2][k][n]
@@ -38,6 +39,10 @@ struct GemmArgs {
   // k_ordered_reduce then adds the slabs in ascending p (nb2 == 1, checked by the launcher)
   float* part;
   float* colPart;
+  // k_bgemm<BG_HEAD_SEED> only (behind every field the other instantiations read): the multiplier of scaleC from the
+  // counter-based generator instead of a tensor - element b1*bS1 + b2*bS2 + m*sSm + n*sSn of the logical mask (the same
+  // four strides; sSn == 1, the others multiples of 4, N a multiple of 4: gemm() in matgcn_bwd.hip refuses anything else)
+  DropDesc drop;
 };
 
 #define BG_LD 80   // LDS row pitch (floats): 80 = 16 mod 32, so k and k + 1 sit half a bank row apart
@@ -55,7 +60,11 @@ constexpr int BG_KT = 16 * BG_KH;
 
 // ROLE only names the instantiation, so that profilers list the call sites of the backward on separate lines
 enum { BG_GENERIC = 0, BG_CHAIN_DENSE, BG_CHAIN_NODE, BG_CHAIN_MIX, BG_X_NODE, BG_X_MIX, BG_WGRAD, BG_ADJ, BG_LINEAR,
-       BG_POOL, BG_HEAD, BG_ROLES };
+       BG_POOL, BG_HEAD, BG_HEAD_SEED, BG_ROLES };
+// BG_HEAD_SEED is the one role that changes code: the head's data gradient with the dropout multipliers drawn in the
+// epilogue (matgcn_backward_seeded).  One Philox call decides four consecutive columns, and the accumulator layout gives a
+// lane ONE column of four rows per 16 x 16 block - so lane r of every aligned quad of lanes draws the call of row r, and
+// the four keep bits travel through the quad with quad_perm DPP moves: one call per lane and block, not four.
 template <int ROLE>
 __global__ __launch_bounds__(256) void k_bgemm(GemmArgs g) {
   __shared__ float As[2][BG_KT][BG_LD];
@@ -192,6 +201,27 @@ __global__ __launch_bounds__(256) void k_bgemm(GemmArgs g) {
   }
   float* slab = (g.mode == 1 && g.part)
                     ? g.part + ((size_t)part * (gridDim.z / (unsigned)(g.nb2 * g.split)) + b1) * g.M * g.N : nullptr;
+  // BG_HEAD_SEED: keep bits of this lane's column in the four rows of every block, gathered before any lane leaves the
+  // epilogue (the DPP moves read the other lanes of the quad; the position is arithmetic only - nothing is addressed)
+  unsigned int keep[2][2];
+  if constexpr (ROLE == BG_HEAD_SEED) {
+    const int r = j & 3;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int m = m0 + wm * 32 + a * 16 + 4 * kq + r, n = n0 + wn * 32 + b * 16 + j;
+        const unsigned long long idx = (unsigned long long)b1 * g.bS1 + (unsigned long long)b2 * g.bS2 +
+                                       (unsigned long long)m * g.sSm + (unsigned long long)n;
+        const int mine = (int)drop_keep4(g.drop, idx >> 2);                // row r, columns n & ~3 .. + 3
+        const int k0 = __builtin_amdgcn_update_dpp(0, mine, 0x00, 0xf, 0xf, false);   // quad_perm [0,0,0,0]: row 0's bits
+        const int k1 = __builtin_amdgcn_update_dpp(0, mine, 0x55, 0xf, 0xf, false);   // [1,1,1,1]
+        const int k2 = __builtin_amdgcn_update_dpp(0, mine, 0xaa, 0xf, 0xf, false);   // [2,2,2,2]
+        const int k3 = __builtin_amdgcn_update_dpp(0, mine, 0xff, 0xf, 0xf, false);   // [3,3,3,3]
+        keep[a][b] = (((unsigned)k0 >> r) & 1u) | ((((unsigned)k1 >> r) & 1u) << 1) | ((((unsigned)k2 >> r) & 1u) << 2) |
+                     ((((unsigned)k3 >> r) & 1u) << 3);                    // bit e: row e of the block, this lane's column
+      }
+  }
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -202,6 +232,7 @@ __global__ __launch_bounds__(256) void k_bgemm(GemmArgs g) {
         if (m >= g.M || n >= g.N) continue;
         float* dst = C + (size_t)m * g.sCm + (size_t)n * g.sCn;
         float v = g.alpha * acc[a][b][e];
+        if constexpr (ROLE == BG_HEAD_SEED) v *= ((keep[a][b] >> e) & 1u) ? g.drop.scale : 0.f;
         if (g.scaleC) v *= g.scaleC[(size_t)b1 * g.bS1 + (size_t)b2 * g.bS2 + (size_t)m * g.sSm + (size_t)n * g.sSn];
         if (slab) slab[(size_t)m * g.N + n] = v;
         else if (g.mode == 1) unsafeAtomicAdd(dst, v);
@@ -2513,6 +2544,32 @@ __global__ __launch_bounds__(256) void k_apply_mask(const float* __restrict__ sr
   const int b = (idx / ((size_t)64 * Np)) % B;
   const int t = idx / ((size_t)64 * Np * B);
   dst[idx] = n < N ? src[idx] * mask[(((size_t)b * T + t) * N + n) * 64 + h] : 0.f;
+}
+
+// the same from the counter-based generator (matgcn_forward_train_seeded, gcn_off models; graph models draw in the top
+// layer's update kernel): no mask tensor.  One thread per float4 of dst = one Philox call.
+__global__ __launch_bounds__(256) void k_apply_dropout(const float* __restrict__ src, DropDesc d, float* __restrict__ dst,
+                                                       int B, int T, int N, int Np) {
+  const size_t i4 = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i4 >= (size_t)T * B * Np * 16) return;
+  const int h4 = i4 & 15;
+  const int n = (i4 >> 4) % Np;
+  const int b = (i4 / ((size_t)16 * Np)) % B;
+  const int t = i4 / ((size_t)16 * Np * B);
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (n < N) {
+    const float4 x = *reinterpret_cast<const float4*>(src + i4 * 4);
+    const float4 m = drop_mult4(d, (((unsigned long long)b * T + t) * N + n) * 16 + h4);
+    v = make_float4(x.x * m.x, x.y * m.y, x.z * m.z, x.w * m.w);
+  }
+  *reinterpret_cast<float4*>(dst + i4 * 4) = v;
+}
+
+// the (B, T, N, 64) mask a descriptor stands for, written out (matgcn_dropout_mask: tests, callers that want to look)
+__global__ __launch_bounds__(256) void k_dropout_mask(DropDesc d, float* __restrict__ mask, size_t quads) {
+  const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (q >= quads) return;
+  *reinterpret_cast<float4*>(mask + q * 4) = drop_mult4(d, q);
 }
 
 // ---- output head backward (MultiATGCN.py:416-418): dOut (B, out, N, od) -> plain [B][Np][CH] with oc = o*od + d

@@ -645,6 +645,7 @@ struct Ctx {
   TrainPlan R;
   const float* dropMask = nullptr;   // matgcn_forward_train: (B, headT, N, H) dropout mask of the head's input, applied by the
                                      // top layer's update kernel as it writes the sequence (graph layers)
+  DropDesc drop = {};                // matgcn_forward_train_seeded: the same dropout from the generator (drop.on), no tensor
   Precision prec;             // fp32 unless a hot entry point sets it: matgcn_prepare and the unit entry points
                               // (matgcn_agcn_gate_fwd, matgcn_encoder_fwd, ...) deliberately leave the default
 };
@@ -667,7 +668,8 @@ constexpr int UPDATE_SAVE_LDS = 5 * 64 * 64 * (int)sizeof(float);   // training:
 // cell alone, 1 + residual cell and blend, 2 residual cell alone; k_gate16 has none: 0), save - training keeps z, r, hc,
 // rows - of a (node, row block) work item, bf - bf16 copies of the weight streams, zero - the step from the all-zero
 // initial state (step 0 of an inference forward without h0: encoder_chains).
-struct NodeVariant { int mode; bool save; int rows; bool bf; bool zero; void (*fn)(Node16Args); int lds; };
+// seed - the head's dropout from the counter-based generator (matgcn_forward_train_seeded; top layer's head steps only).
+struct NodeVariant { int mode; bool save; int rows; bool bf; bool zero; void (*fn)(Node16Args); int lds; bool seed = false; };
 const NodeVariant GATE16[] = {
     {0, false, 64, false, false, k_gate16<false, 64>, GATE_LDS},
     {0, true, 64, false, false, k_gate16<true, 64>, GATE_LDS},
@@ -695,6 +697,10 @@ const NodeVariant UPDATE16[] = {
     {1, false, 64, false, true, k_update16<1, false, 64, false, true>, UPDATE_LDS},
     {1, false, 64, true, true, k_update16<1, false, 64, true, true>, UPDATE_LDS},
     {1, false, 32, false, true, k_update16<1, false, 32, false, true>, UPDATE_LDS / 2},
+    // seeded dropout in the sequence store (training, top layer): one entry per SAVE entry of mode 1
+    {1, true, 64, false, false, k_update16<1, true, 64, false, false, true>, UPDATE_SAVE_LDS, true},
+    {1, true, 64, true, false, k_update16<1, true, 64, true, false, true>, UPDATE_SAVE_LDS, true},
+    {1, true, 32, false, false, k_update16<1, true, 32, false, false, true>, UPDATE_SAVE_LDS / 2, true},
 };
 struct PxVariant { int nrt; bool bf; void (*fn)(Px16Args); };   // nrt: row tiles that hold batch rows; LDS: the plan's nodeLds
 const PxVariant PX16[] = {
@@ -704,9 +710,9 @@ const PxVariant PX16[] = {
 // launches the table's entry for the selectors; a combination without an entry is an error, never another variant
 template <size_t n>
 int launch_node(const NodeVariant (&table)[n], int mode, bool save, int rows, bool bf, bool zero, const dim3& grid,
-                hipStream_t s, const Node16Args& a) {
+                hipStream_t s, const Node16Args& a, bool seed = false) {
   const NodeVariant* v = find_variant(table, [&](auto& e) {
-    return e.mode == mode && e.save == save && e.rows == rows && e.bf == bf && e.zero == zero; });
+    return e.mode == mode && e.save == save && e.rows == rows && e.bf == bf && e.zero == zero && e.seed == seed; });
   if (!v) return MATGCN_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(v->fn, grid, dim3(512), v->lds, s, a);
   return launch_ok();
@@ -940,6 +946,7 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
   }
   a.s = ZHx; a.w = bf ? c.ws + P.oW16u[l] : c.prep + P.oWu[l]; a.r = R; a.h = Hx; a.hout = Hx;
   ProfScope prof(MATGCN_PROF_UPDATE, s);
+  bool seeded = false;
   if (res) {
     a.xt = res->xt; a.xRowStride = res->xRowStride; a.C = res->C; a.Cpad = res->Cpad;
     a.rg = res->rg; a.rgb = res->rgb; a.ru = res->ru; a.rub = res->rub;
@@ -949,8 +956,13 @@ int cell_phase(const Ctx& c, int l, int t, int phase, float* raw, const Node16Ar
       a.dropRowStride = (long)P.headT * P.N * H;
       a.seqDrop = c.train + c.R.oSeqDrop + (a.seq - (c.ws + P.oSeq[l]));
     }
+    if (save && c.drop.on && l == P.L - 1 && t >= P.T - P.headT && a.seq) {   // ... or is drawn there, from the generator
+      a.drop = c.drop; a.dropT = t - (P.T - P.headT); a.dropHeadT = P.headT;
+      a.seqDrop = c.train + c.R.oSeqDrop + (a.seq - (c.ws + P.oSeq[l]));
+      seeded = true;
+    }
   }
-  return launch_node(UPDATE16, res ? 1 : 0, save, rows32 ? 32 : 64, bf, zeroState, grid, s, a);
+  return launch_node(UPDATE16, res ? 1 : 0, save, rows32 ? 32 : 64, bf, zeroState, grid, s, a, seeded);
 }
 
 // One recurrent step of layer l at step t on the layer's state Hx_l:
@@ -1179,6 +1191,36 @@ int head_padded(const Ctx& c, const float* seqp, float* out) {
   a.B = P.B; a.T = P.headT; a.N = P.N; a.Np = P.Np; a.CH = P.CH; a.od = P.od; a.NTc = P.NTc;
   ProfScope prof(MATGCN_PROF_HEAD, c.s);
   hipLaunchKernelGGL(k_head, dim3((unsigned)(P.B * ((P.N + 31) / 32))), dim3(256), 0, c.s, a);
+  return launch_ok();
+}
+
+// matgcn_dropout -> what the kernels read: the threshold an output word is compared with and the multiplier of a kept
+// element (matgcn_philox.h).  p outside [0, 1) - NaN included - is an error.
+int make_drop_desc(const matgcn_dropout* in, DropDesc* d) {
+  if (!in || !d) return MATGCN_ERR_NULL;
+  if (!(in->p >= 0.f && in->p < 1.f)) return MATGCN_ERR_BAD_ARG;
+  memset(d, 0, sizeof(*d));
+  d->seed = in->seed; d->offset = in->offset;
+  d->thr = (unsigned int)((double)in->p * 4294967296.0);          // floor: the product is below 2^32 and not negative
+  d->scale = (float)(1.0 / (1.0 - (double)in->p));
+  d->on = 1;
+  return MATGCN_OK;
+}
+
+// the head over `samples` masks of the padded time-major sequence seqp (matgcn_forward_mc)
+int head_mc_padded(const Ctx& c, const float* seqp, const DropDesc& d, int samples, float* mean, float* stdev,
+                   float* samplesOut) {
+  const Plan& P = c.P;
+  if (P.headT > 4 * HEAD_MC_STEPS || P.NTc > 2) return MATGCN_ERR_UNSUPPORTED;   // what k_head_mc holds in registers
+  HeadMcArgs m;
+  memset(&m, 0, sizeof(m));
+  HeadArgs& a = m.h;
+  a.seq = seqp + (size_t)(P.T - P.headT) * P.B * P.Np * H; a.w = c.prep + P.oHead;
+  a.bias = c.prm->end_conv_bias; a.out = nullptr;
+  a.B = P.B; a.T = P.headT; a.N = P.N; a.Np = P.Np; a.CH = P.CH; a.od = P.od; a.NTc = P.NTc;
+  m.drop = d; m.samples = samples; m.mean = mean; m.stdev = stdev; m.samplesOut = samplesOut;
+  ProfScope prof(MATGCN_PROF_HEAD, c.s);
+  hipLaunchKernelGGL(k_head_mc, dim3((unsigned)(P.B * ((P.N + 31) / 32))), dim3(256), 0, c.s, m);
   return launch_ok();
 }
 
@@ -1656,6 +1698,52 @@ int matgcn_forward_series(const matgcn_dims* dims, const matgcn_params* params, 
     return forward_series_entry(dims, params, prepared, series, series_steps, label_start, rel_steps, h0, out, workspace,
                                 workspace_bytes, s);
   });
+}
+
+// Monte-Carlo dropout: the inference forward's encoder once (its kernels, its precision mode), then the head over the
+// samples' masks in one launch (k_head_mc)
+static int forward_mc_entry(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
+                            const matgcn_series* src, const float* h0, const matgcn_dropout* dropout, int samples,
+                            float* mean, float* stdev, float* samples_out, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+  if (!prepared || (!X && !src) || !dropout || !mean || !stdev) return MATGCN_ERR_NULL;
+  if (samples < 1 || samples > MATGCN_MAX_MC_SAMPLES) return MATGCN_ERR_BAD_ARG;
+  DropDesc d;
+  RETURN_IF(make_drop_desc(dropout, &d));
+  Ctx c;
+  RETURN_IF(make_ctx(&c, dims, params, prepared, workspace, workspace_bytes, stream, false));   // chains wait per layer
+  if (!params->weight_tsg || !params->end_conv_bias) return MATGCN_ERR_NULL;
+  for (int h = 0; h < dims->n_heads; ++h) if (!params->weight_ts[h]) return MATGCN_ERR_NULL;
+  RETURN_IF(check_layer_params(dims, params));
+  if (src) RETURN_IF(check_series(dims, src->series, src->series_steps, src->label_start, src->rel_steps));
+  const Plan& P = c.P;
+  if (P.headT > 4 * HEAD_MC_STEPS || P.NTc > 2) return MATGCN_ERR_UNSUPPORTED;   // before anything is enqueued
+  c.prec = precision_of(g_mix_precision);
+  float* x0p = c.ws + P.oX0p;
+  if (src) RETURN_IF(fuse_padded(c, src->series, x0p, src->label_start, src->rel_steps, src->series_steps));
+  else RETURN_IF(fuse_padded(c, X, x0p));
+  RETURN_IF(encoder_padded(c, x0p, h0, nullptr));
+  return head_mc_padded(c, c.ws + P.oSeq[P.L - 1], d, samples, mean, stdev, samples_out);
+}
+
+int matgcn_forward_mc(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
+                      const matgcn_series* src, const float* h0, const matgcn_dropout* dropout, int samples, float* mean,
+                      float* std, float* samples_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return on_main_stream(stream, [&](void* s) {
+    return forward_mc_entry(dims, params, prepared, X, src, h0, dropout, samples, mean, std, samples_out, workspace,
+                            workspace_bytes, s);
+  });
+}
+
+int matgcn_dropout_mask(const matgcn_dims* dims, const matgcn_dropout* dropout, float* mask, void* stream) {
+  if (!mask) return MATGCN_ERR_NULL;
+  Plan P;
+  RETURN_IF(make_plan(dims, &P));
+  DropDesc d;
+  RETURN_IF(make_drop_desc(dropout, &d));
+  const size_t quads = (size_t)P.B * P.headT * P.N * (H / 4);
+  hipLaunchKernelGGL(k_dropout_mask, dim3(blocks_for(quads)), dim3(256), 0, (hipStream_t)stream, d, mask, quads);
+  return launch_ok();
 }
 
 int matgcn_fuse_heads(const matgcn_dims* dims, const matgcn_params* params, const float* X, float* x0,

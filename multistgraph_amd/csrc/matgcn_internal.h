@@ -3,6 +3,7 @@
 #define MATGCN_INTERNAL_H
 #include <stddef.h>
 #include <stdint.h>
+#include "matgcn_philox.h"
 
 #define MATGCN_MAX_STACK 16   /* entries of the reference's support stack (identity included) this build maps */
 
@@ -99,6 +100,16 @@ struct HeadArgs {
   const float* bias;
   float* out;
   int B, T, N, Np, CH, od, NTc;   // seq is time-major [T][B][Np][64]
+};
+
+// k_head_mc: the head over `samples` dropout masks of one sequence (matgcn_forward_mc)
+struct HeadMcArgs {
+  HeadArgs h;            // h.out is not used
+  DropDesc drop;         // sample s draws with offset drop.offset + s
+  int samples;
+  float* mean;           // (B, out, N, od)
+  float* stdev;          // (B, out, N, od) population standard deviation over the samples
+  float* samplesOut;     // (samples, B, out, N, od) or null
 };
 
 #endif

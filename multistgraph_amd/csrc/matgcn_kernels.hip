@@ -1489,6 +1489,152 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
   }
 }
 
+// ---- the head over S dropout masks (matgcn_forward_mc: Monte-Carlo dropout) ---------------------------------------------
+// k_head's product repeated over the samples: the same grid, the same split of the T steps over the four waves, the same
+// MFMA order per accumulator and the same fixed order of the partial sums in LDS - sample s is, bit for bit, what k_head
+// gives on seq * mask_s.  The mask never exists: a lane's float4 of A is multiplied by the four multipliers of one Philox
+// call (matgcn_philox.h) as it enters the MFMAs.
+// Register / LDS choice: a workgroup's A tile is T * 32 * 64 * 4 = 196 608 bytes - more than the 160 KB of LDS - but per
+// LANE it is 6 steps x 8 float4 = 192 values, and the kernel runs one wave per SIMD (__launch_bounds__(256): a budget of
+// 512 registers), so the tile is loaded ONCE into VGPRs and every sample re-reads only the conv weight (L2-resident,
+// 96 KB per wave).  Wave 0 keeps the running mean and M2 of its 32 outputs per lane (Welford, fp32; the count is the
+// sample index) in 16 KB of lane-private LDS - with them in registers as well the kernel spilled 784 bytes per lane to
+// scratch - and writes mean and the population standard deviation when the samples are done.
+constexpr int HEAD_MC_STEPS = 6;   // steps per wave held in registers: headT <= 24 (checked by the launcher)
+template <int K> struct HeadStep { static constexpr int value = K; };
+__global__ __launch_bounds__(256) void k_head_mc(HeadMcArgs m) {
+  const HeadArgs& a = m.h;
+  __shared__ f32x16 part[3][2][64];      // partial accumulators of waves 1..3
+  __shared__ float stat[2][32][64];      // wave 0: running mean [0] and M2 [1] of its 32 outputs per lane (lane-private)
+  const int tilesPerB = (a.N + 31) >> 5;
+  const int b = blockIdx.x / tilesPerB, n0 = (blockIdx.x % tilesPerB) * 32;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), i = lane & 31, half = lane >> 5;
+  const int node = min(n0 + i, a.Np - 1);  // pad rows are zero / in bounds
+  const int nt = a.NTc;
+  float4 av[HEAD_MC_STEPS][8];
+#pragma unroll
+  for (int k = 0; k < HEAD_MC_STEPS; ++k) {
+    const int t = w + 4 * k;
+    const float* rowp = a.seq + (((size_t)min(t, a.T - 1) * a.B + b) * a.Np + node) * 64 + half * 4;
+#pragma unroll
+    for (int g = 0; g < 8; ++g) av[k][g] = *reinterpret_cast<const float4*>(rowp + g * 8);
+  }
+  float bias[2];
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt) bias[tt] = (tt < nt && tt * 32 + i < a.CH) ? a.bias[tt * 32 + i] : 0.f;
+  if (w == 0) {
+#pragma unroll
+    for (int e = 0; e < 32; ++e) { stat[0][e][lane] = 0.f; stat[1][e][lane] = 0.f; }
+  }
+  const size_t sampleFloats = (size_t)a.B * a.CH * a.N;
+  // The conv weight is the same for every sample, and a loop-invariant load is hoisted: all 96 float4 of a wave ended up
+  // live across the sample loop (512 registers, 928 bytes of scratch per lane in the ISA).  So the weight's base is made
+  // opaque once per sample, the fragments of group g + 1 are requested while group g multiplies (8 MFMAs of 16 passes and
+  // one Philox call cover an L2 hit), and a scheduling barrier per group keeps the requests from piling up.
+  const int tFirst = min(w, a.T - 1);
+  auto wload = [&](const float* wbase, int jg, float4 (&dst)[2]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+      dst[tt] = *reinterpret_cast<const float4*>(wbase + ((size_t)(jg * nt + min(tt, nt - 1)) * 64 + lane) * 4);
+  };
+  float4 wc[2];
+  wload(a.w, tFirst * 8, wc);
+  const unsigned long long qLane = ((unsigned long long)b * a.T * a.N + (n0 + i)) * 16 + half;   // mask quad of step 0, g = 0
+  for (int s = 0; s < m.samples; ++s) {
+    DropDesc d = m.drop;
+    d.offset += (unsigned long long)s;
+    const float* wbase = a.w;
+    asm volatile("" : "+s"(wbase));
+    // (likewise the lane's mask position: the counters of all 48 calls and their first-round products are the same for
+    // every sample and were kept live across the loop - about 200 registers)
+    unsigned int qlo = (unsigned int)qLane, qhi = (unsigned int)(qLane >> 32);
+    asm volatile("" : "+v"(qlo), "+v"(qhi));
+    const unsigned long long qb = ((unsigned long long)qhi << 32) | qlo;
+    f32x16 acc[2];
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[tt][r] = 0.f;
+    // (one call per step with the step as a compile-time constant: left to `#pragma unroll` the compiler kept part of the
+    // loop rolled, which made av[k] a runtime index and moved the whole tile to scratch)
+    auto step = [&](auto kc) __attribute__((always_inline)) {
+      constexpr int k = decltype(kc)::value;
+      const int t = w + 4 * k;
+      if (t < a.T) {   // wave-uniform
+        // mask quad of (b, t, n0 + i, 8 g + 4 half .. + 3): position arithmetic only, rows past N decide nothing written
+        const unsigned long long q0 = qb + (unsigned long long)t * a.N * 16;
+        const int tNext = t + 4 < a.T ? t + 4 : tFirst;   // behind the wave's last step: the next sample's first group
+#pragma unroll
+        for (int g = 0; g < 8; ++g) {
+          float4 wn[2];
+          wload(wbase, (g < 7 ? t : tNext) * 8 + ((g + 1) & 7), wn);
+          const float4 mk = drop_mult4(d, q0 + 2 * g);
+          const float4 a4 = make_float4(av[k][g].x * mk.x, av[k][g].y * mk.y, av[k][g].z * mk.z, av[k][g].w * mk.w);
+#pragma unroll
+          for (int tt = 0; tt < 2; ++tt) {
+            if (tt < nt) {
+              acc[tt] = MFMA32(a4.x, wc[tt].x, acc[tt]);
+              acc[tt] = MFMA32(a4.y, wc[tt].y, acc[tt]);
+              acc[tt] = MFMA32(a4.z, wc[tt].z, acc[tt]);
+              acc[tt] = MFMA32(a4.w, wc[tt].w, acc[tt]);
+            }
+          }
+          wc[0] = wn[0]; wc[1] = wn[1];
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    };
+    static_assert(HEAD_MC_STEPS == 6, "one call per step below");
+    step(HeadStep<0>{}); step(HeadStep<1>{}); step(HeadStep<2>{}); step(HeadStep<3>{}); step(HeadStep<4>{});
+    step(HeadStep<5>{});
+    if (w > 0) { part[w - 1][0][lane] = acc[0]; part[w - 1][1][lane] = acc[1]; }
+    __syncthreads();
+    if (w == 0) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const f32x16 p0 = part[q][0][lane], p1 = part[q][1][lane];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { acc[0][r] += p0[r]; acc[1][r] += p1[r]; }
+      }
+      const float inv = 1.0f / (float)(s + 1);
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt) {
+        const int ch = tt * 32 + i;
+        const int o = ch / a.od, dd = ch - o * a.od;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float x = acc[tt][r] + bias[tt];
+          const float mu0 = stat[0][tt * 16 + r][lane];
+          const float delta = x - mu0;
+          const float mu1 = mu0 + delta * inv;
+          stat[0][tt * 16 + r][lane] = mu1;
+          stat[1][tt * 16 + r][lane] += delta * (x - mu1);
+          const int n = n0 + acc_row(r, half);
+          if (m.samplesOut && tt < nt && ch < a.CH && n < a.N)
+            m.samplesOut[s * sampleFloats + (((size_t)b * (a.CH / a.od) + o) * a.N + n) * a.od + dd] = x;
+        }
+      }
+    }
+    __syncthreads();   // the partial tiles are free for the next sample
+  }
+  if (w > 0) return;
+  const float invS = 1.0f / (float)m.samples;
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt) {
+    const int ch = tt * 32 + i;
+    if (tt >= nt || ch >= a.CH) continue;
+    const int o = ch / a.od, dd = ch - o * a.od;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int n = n0 + acc_row(r, half);
+      if (n >= a.N) continue;
+      const size_t at = (((size_t)b * (a.CH / a.od) + o) * a.N + n) * a.od + dd;
+      m.mean[at] = stat[0][tt * 16 + r][lane];
+      m.stdev[at] = sqrtf(stat[1][tt * 16 + r][lane] * invS);
+    }
+  }
+}
+
 // =================================================================================================
 // 9. loss / metric epilogue (MultiATGCN.py:422-427, loss.py:17-29, traffic_state_evaluator.py:87-104)
 // =================================================================================================

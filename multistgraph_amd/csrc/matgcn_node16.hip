@@ -31,6 +31,7 @@
 #define MATGCN_NODE16_HIP
 
 // f32x4 / MFMA16 come from matgcn_kernels.hip (same translation unit)
+#include "matgcn_philox.h"
 
 constexpr int NODE_MIN_WAVES = 4;   // __launch_bounds__ second argument of k_gate16 / k_update16 (both row counts): 4 waves
                                     // per SIMD = a budget of 128 VGPRs (no spills).  5 (96 VGPRs: two node waves per SIMD
@@ -82,6 +83,11 @@ struct Node16Args {
   const float* dropMask;
   long dropRowStride;
   float* seqDrop;
+  // the same dropout from the counter-based generator (the SEED instantiations of k_update16; behind every argument the
+  // other kernels read, whose offsets stay): no mask tensor - element (b, dropT, n, o) of the logical (B, dropHeadT, N, 64)
+  // mask is decided by matgcn_philox.h from its position
+  DropDesc drop;
+  int dropT, dropHeadT;
 };
 
 // Gate non-linearities of the step kernels.  The node kernels' epilogues are VALU-bound stretches in which the matrix
@@ -628,9 +634,13 @@ __global__ __launch_bounds__(512, 4) void k_px16(Px16Args p) {
 // r*h + (1 - r)*hc is (1 - r)*hc.  Both agree in value with the general instantiation for finite weights (every skipped
 // fma(0, w, acc) leaves acc as it is, r*0 is a zero); the previous state is not read.  The residual cell runs on
 // [x_t | h'] of the NEW state h', as in every step: nothing of it is skipped.
-template <int MODE, bool SAVE, int ROWS, bool BF = false, bool ZERO = false>
+//
+// SEED (MODE 1, SAVE; matgcn_forward_train_seeded): the multipliers of the head's dropout come from one Philox call per
+// float4 of the sequence row instead of a float4 of the mask tensor - the same values, so seqDrop gets the same bits.
+template <int MODE, bool SAVE, int ROWS, bool BF = false, bool ZERO = false, bool SEED = false>
 __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_update16(Node16Args a) {
   static_assert(!ZERO || (MODE == 1 && !SAVE), "the zero-state step exists for the inference forward's fused update only");
+  static_assert(!SEED || (MODE == 1 && SAVE), "the seeded dropout rides in the training forward's sequence store only");
   typedef typename NodeOp<BF>::T Op;
   constexpr int NRT = ROWS / 16, NR2 = ROWS / 32, NS = ROWS / 32, CH = ROWS * 64;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -914,7 +924,13 @@ __global__ __launch_bounds__(512, NODE_MIN_WAVES) void k_update16(Node16Args a) 
       save16(a.svR2, sat, *reinterpret_cast<const float4*>(&R2[at]));
       save16(a.svHC2, sat, *reinterpret_cast<const float4*>(&HC2t[at]));
       if (a.seqDrop) {
-        const float4 m = *reinterpret_cast<const float4*>(a.dropMask + (size_t)b * a.dropRowStride + (size_t)n * 64 + sq * 4);
+        float4 m;
+        if constexpr (SEED) {
+          const unsigned long long idx = (((unsigned long long)b * a.dropHeadT + a.dropT) * a.N + n) * 64 + sq * 4;
+          m = drop_mult4(a.drop, idx >> 2);
+        } else {
+          m = *reinterpret_cast<const float4*>(a.dropMask + (size_t)b * a.dropRowStride + (size_t)n * 64 + sq * 4);
+        }
         save16(a.seqDrop, (size_t)b * a.seqRowStride + (size_t)n * 64 + sq * 4,
                make_float4(v.x * m.x, v.y * m.y, v.z * m.z, v.w * m.w));
       }

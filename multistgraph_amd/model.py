@@ -125,6 +125,11 @@ def _precision_mode(name) -> int:
     return HIP_PRECISIONS[name]
 
 
+# config['hip_dropout']: where the training-mode dropout in front of end_conv (:416) is drawn
+HIP_DROPOUTS = ("torch", "device")
+DROPOUT_P = 0.1   # F.dropout(output, p=0.1) (:416): the reference hard-codes it
+
+
 def _torch_deterministic() -> bool:
     return bool(torch.are_deterministic_algorithms_enabled())
 
@@ -137,8 +142,13 @@ class _TrainStep(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, path, x, drop_mask, h0, names, *params):
+        # drop_mask: the mask tensor torch drew, or - config['hip_dropout'] = "device" - the (seed, offset, p) triple the
+        # kernels draw it from (the backward gets the same one), or None
         h0 = None if h0 is None else h0.detach()
-        out = path.forward_train(x, drop_mask, h0)
+        ctx.dropout = drop_mask if isinstance(drop_mask, tuple) else None
+        if ctx.dropout is not None:
+            drop_mask = None
+        out = path.forward_train(x, drop_mask, h0, dropout=ctx.dropout)
         ctx.path, ctx.x, ctx.mask, ctx.names, ctx.h0 = path, x, drop_mask, names, h0
         ctx.params = params
         ctx.generation = path.train_generation
@@ -152,7 +162,7 @@ class _TrainStep(torch.autograd.Function):
                                "backward; the saved activations live in the shared workspace (one graph at a time)")
         state = {k: p for k, p in zip(ctx.names, ctx.params)}
         # (no precision setting here: the library runs the backward in the mode its forward_train ran with)
-        grads = path.backward(ctx.x, d_out.contiguous(), state, ctx.mask, ctx.h0)
+        grads = path.backward(ctx.x, d_out.contiguous(), state, ctx.mask, ctx.h0, dropout=ctx.dropout)
         # the initial state (static features, :406-409) gets its gradient back: torch autograd carries it on through
         # expand() and static_initial_gru
         return (None, None, None, grads.get(path.D_H0), None) + tuple(grads.get(k) if p.requires_grad else None
@@ -187,6 +197,16 @@ class MultiATGCN(AbstractTrafficStateModel):
         self.hip_deterministic = get("hip_deterministic", None)
         if self.hip_deterministic not in (None, True, False):
             raise ValueError("hip_deterministic = %r: expected None, True or False" % (self.hip_deterministic,))
+        # config['hip_dropout']: "torch" (default) - the training-mode dropout mask is a tensor F.dropout draws from torch's
+        # generator; "device" - it is drawn inside the HIP kernels that apply it from a counter-based generator
+        # (matgcn_forward_train_seeded / matgcn_backward_seeded): no mask tensor, nothing taken from torch's generator.
+        # Seed: torch.initial_seed(); offset: a per-model counter that advances by one per training forward (and by
+        # `samples` per predict_mc without an explicit seed), inside an initialised process group (rank << 40) | counter,
+        # so ranks draw different masks.  An attribute like the two above: checkpoints are unchanged.
+        self.hip_dropout = get("hip_dropout", "torch")
+        if self.hip_dropout not in HIP_DROPOUTS:
+            raise ValueError("hip_dropout = %r: expected one of %s" % (self.hip_dropout, ", ".join(HIP_DROPOUTS)))
+        self._dropout_counter = 0
         self.batch_size = get("batch_size", 64)
         self.device = get("device", torch.device("cpu"))
         config["num_nodes"] = self.num_nodes  # the reference writes this back (:233)
@@ -300,6 +320,15 @@ class MultiATGCN(AbstractTrafficStateModel):
         """config['hip_deterministic'], None following torch.use_deterministic_algorithms"""
         return _torch_deterministic() if self.hip_deterministic is None else bool(self.hip_deterministic)
 
+    def _dropout_offset(self, draws: int) -> int:
+        """the offset of the next device-side dropout draw; advances the model's counter by ``draws``"""
+        counter = self._dropout_counter
+        self._dropout_counter += int(draws)
+        rank = 0
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank = torch.distributed.get_rank()
+        return ((rank << 40) | (counter & ((1 << 40) - 1))) & (2 ** 64 - 1)
+
     def _params_key(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters())
 
@@ -348,7 +377,9 @@ class MultiATGCN(AbstractTrafficStateModel):
             return hp.forward_series(source[0], source[1], source[2], h0)
         # training step: HIP forward that keeps its activations + HIP backward behind torch autograd
         mask = None
-        if self.training:   # F.dropout(output, p=0.1) in front of end_conv (:416), drawn from torch's generator
+        if self.training and self.hip_dropout == "device":   # the same dropout, drawn by the kernels that apply it
+            mask = (torch.initial_seed(), self._dropout_offset(1), DROPOUT_P)
+        elif self.training:   # F.dropout(output, p=0.1) in front of end_conv (:416), drawn from torch's generator
             mask = nn.functional.dropout(torch.ones(batch, 1 if self.fnn_off else self.input_window,
                                                     self.num_nodes, self.hidden_dim, device=device),
                                          p=0.1, training=True)   # fnn_off keeps the last step only (:412)
@@ -376,6 +407,36 @@ class MultiATGCN(AbstractTrafficStateModel):
 
     def predict(self, batch):
         return self.forward(batch)
+
+    def predict_mc(self, batch, samples: int = 32, seed: Optional[int] = None, keep_samples: bool = False):
+        """Monte-Carlo-dropout forecast: ``samples`` stochastic forward passes with the training-mode dropout in front of
+        end_conv (:416, p = 0.1) switched on, as (mean, std[, samples]) - std the population standard deviation over the
+        samples, all (B, out, N, od); the samples (samples, B, out, N, od) with ``keep_samples``.  Dropout sits only in
+        front of the head, so the encoder runs ONCE (in eval form) and the head ``samples`` times, in one kernel launch
+        (matgcn_forward_mc).  Works in eval and in train mode (the mode is left as it was; no autograd graph is built)
+        and with window and resident-series batches.  seed = None: the model's seed (torch.initial_seed()) and the next
+        ``samples`` offsets of its dropout counter; an explicit seed draws at offsets 0 .. samples - 1 and leaves the
+        counter alone, so the same call gives the same result."""
+        if _is_series_batch(batch):
+            source = self._batch_source(batch)
+            nb, device = int(source[1].shape[0]), source[0].device
+        else:
+            x = batch["X"]
+            assert x.shape[2] == self.num_nodes
+            if not x.is_cuda:
+                raise RuntimeError("MultiATGCN.predict_mc runs on the HIP hot path only: batch['X'] is on %s." % x.device)
+            source = (x if x.dtype == torch.float32 else x.float()).contiguous()
+            nb, device = int(x.shape[0]), x.device
+        with torch.no_grad():
+            h0 = self._initial_state(nb)
+            h0 = None if h0 is None else (hidden_pad.pad_last(h0) if self._padded else h0.contiguous())
+            hp = self._path_for_batch(nb, device)
+            if seed is None:
+                seed, offset = torch.initial_seed(), self._dropout_offset(samples)
+            else:
+                offset = 0
+            return hp.forward_mc(source, h0, seed=seed, offset=offset, p=DROPOUT_P, samples=samples,
+                                 keep_samples=keep_samples)
 
     # ---- the same surface fed from the device-resident raw series (no windows, no labels materialised) ----------
     def _batch_source(self, batch):

@@ -542,26 +542,78 @@ class HotPath:
         s = self.spec
         return _check_tensor(drop_mask, "drop_mask", (self.batch, 1 if s.fnn_off else s.in_steps, s.nodes, s.hidden))
 
+    @staticmethod
+    def _dropout(dropout, drop_mask=None) -> Optional[_lib.Dropout]:
+        """(seed, offset, p) -> matgcn_dropout, or None.  The range of p is the library's to check."""
+        if dropout is None:
+            return None
+        if drop_mask is not None:
+            raise _lib.MatgcnError("drop_mask and dropout = (seed, offset, p) exclude each other")
+        seed, offset, p = dropout
+        return _lib.Dropout(int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), float(p))
+
+    def dropout_mask(self, seed: int, offset: int, p: float) -> torch.Tensor:
+        """The (B, headT, N, 64) mask the descriptor (seed, offset, p) stands for, written out by matgcn_dropout_mask
+        (tests, and callers that want to look at it: the training and MC entry points never materialise it)."""
+        s = self.spec
+        mask = torch.empty(self.batch, 1 if s.fnn_off else s.in_steps, s.nodes, s.hidden, dtype=torch.float32,
+                           device=self.device)
+        d = self._dropout((seed, offset, p))
+        _lib.check(self.lib.matgcn_dropout_mask(C.byref(self.dims), C.byref(d), C.c_void_p(mask.data_ptr()),
+                                                self._stream()), "matgcn_dropout_mask")
+        return mask
+
     def forward_train(self, x, drop_mask: Optional[torch.Tensor] = None,
-                      h0: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      h0: Optional[torch.Tensor] = None, dropout=None) -> torch.Tensor:
         """matgcn_forward that keeps the activations the backward needs (in the train buffer and the workspace).
         x: the windows tensor X, or a (series, label_start, rel_steps) triple (see _source).
         drop_mask: the (B, T, N, H) multipliers of the dropout in front of end_conv (training mode) or None;
+        dropout: (seed, offset, p) instead - the same dropout drawn on the device by matgcn_forward_train_seeded, no mask
+        tensor (the matching backward must get the same triple);
         h0: initial encoder state (L, B, N, H) or None."""
         s = self.spec
         xp, src, _keep = self._source(x)
         drop_mask = self._mask(drop_mask)
+        seeded = self._dropout(dropout, drop_mask)
         h0 = self._h0(h0)
         self._need_prepared()
         out = torch.empty(self.batch, s.out_window, s.nodes, s.out_dim, dtype=torch.float32, device=self.device)
         with self._mode(self.lib.matgcn_set_train_precision), self._x3(), self._det():
             self._train_buffer()
-            self._with_workspace(lambda ws, wsb: self.lib.matgcn_forward_train(
+            fn, what, drop = ((self.lib.matgcn_forward_train, "matgcn_forward_train", C.c_void_p(_ptr(drop_mask)))
+                              if seeded is None else
+                              (self.lib.matgcn_forward_train_seeded, "matgcn_forward_train_seeded", C.byref(seeded)))
+            self._with_workspace(lambda ws, wsb: fn(
                 C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
-                C.byref(src) if src is not None else None, C.c_void_p(_ptr(h0)), C.c_void_p(_ptr(drop_mask)),
+                C.byref(src) if src is not None else None, C.c_void_p(_ptr(h0)), drop,
                 C.c_void_p(out.data_ptr()), ws, wsb, C.c_void_p(self._train.data_ptr()),
-                C.c_size_t(self._train.numel() * 4), self._stream()), "matgcn_forward_train", train=True)
+                C.c_size_t(self._train.numel() * 4), self._stream()), what, train=True)
         return out
+
+    def forward_mc(self, x, h0: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0, p: float = 0.1,
+                   samples: int = 32, keep_samples: bool = False):
+        """Monte-Carlo dropout (matgcn_forward_mc): the eval-mode encoder once, the head over ``samples`` masks - sample
+        s draws with (seed, offset + s, p).  x: the windows tensor X or a (series, label_start, rel_steps) triple.
+        Returns (mean, std) of shape (B, out, N, od) - the population standard deviation over the samples - and, with
+        keep_samples, the (samples, B, out, N, od) forecasts as a third entry."""
+        s = self.spec
+        xp, src, _keep = self._source(x)
+        h0 = self._h0(h0)
+        d = self._dropout((seed, offset, p))
+        self._need_prepared()
+        shape = (self.batch, s.out_window, s.nodes, s.out_dim)
+        mean = torch.empty(shape, dtype=torch.float32, device=self.device)
+        std = torch.empty(shape, dtype=torch.float32, device=self.device)
+        kept = None
+        if keep_samples and 1 <= int(samples) <= _lib.MAX_MC_SAMPLES:
+            kept = torch.empty((int(samples),) + shape, dtype=torch.float32, device=self.device)
+        with self._mode(self.lib.matgcn_set_mix_precision):
+            self._with_workspace(lambda ws, wsb: self.lib.matgcn_forward_mc(
+                C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
+                C.byref(src) if src is not None else None, C.c_void_p(_ptr(h0)), C.byref(d), int(samples),
+                C.c_void_p(mean.data_ptr()), C.c_void_p(std.data_ptr()), C.c_void_p(_ptr(kept)), ws, wsb,
+                self._stream()), "matgcn_forward_mc")
+        return (mean, std, kept) if keep_samples else (mean, std)
 
     D_H0 = "__d_h0__"   # key of the initial-state gradient in backward()'s result
 
@@ -581,15 +633,19 @@ class HotPath:
         return {k: bucket[offs[k]:offs[k] + state[k].numel()].view(state[k].shape) for k in names}
 
     def backward(self, x, d_out: torch.Tensor, state: Dict[str, torch.Tensor],
-                 drop_mask: Optional[torch.Tensor] = None, h0: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                 drop_mask: Optional[torch.Tensor] = None, h0: Optional[torch.Tensor] = None,
+                 dropout=None) -> Dict[str, torch.Tensor]:
         """Gradients of every tensor of `state` (the dict bind() saw) that the loss depends on, keyed by the same
         names; must directly follow the matching forward_train (same workspace, same train buffer).  With h0 (the
         tensor forward_train saw) the result also holds its gradient (L, B, N, H) under HotPath.D_H0.  The library runs
-        the backward in the precision mode of the matching forward_train, whatever the settings are now."""
+        the backward in the precision mode of the matching forward_train, whatever the settings are now.
+        dropout: the (seed, offset, p) triple the matching forward_train got (matgcn_backward_seeded), in place of
+        drop_mask."""
         s = self.spec
         xp, src, _keep = self._source(x)
         d_out = _check_tensor(d_out, "d_out", (self.batch, s.out_window, s.nodes, s.out_dim))
         drop_mask = self._mask(drop_mask)
+        seeded = self._dropout(dropout, drop_mask)
         h0 = self._h0(h0)
         d_h0 = torch.empty_like(h0) if h0 is not None else None
         grads: Dict[str, torch.Tensor] = {}
@@ -638,14 +694,15 @@ class HotPath:
             raise _lib.MatgcnError("backward() without a forward_train() before it")
         ws, wsb = self._ws()   # (the workspace and the train buffer as forward_train left them: no re-sizing here - a
         # deterministic backward behind a forward_train that ran without the setting reports MATGCN_ERR_SMALL_BUFFER)
+        # the two entry points differ in one argument: the mask tensor, or the descriptor that stands for it
+        fn, what, drop = ((self.lib.matgcn_backward, "matgcn_backward", C.c_void_p(_ptr(drop_mask))) if seeded is None else
+                          (self.lib.matgcn_backward_seeded, "matgcn_backward_seeded", C.byref(seeded)))
         with self._x3(), self._det():
-            status = self.lib.matgcn_backward(C.byref(self.dims), C.byref(self.params),
-                                            C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
-                                            C.byref(src) if src is not None else None,
-                                            C.c_void_p(_ptr(h0)), C.c_void_p(_ptr(drop_mask)),
-                                            C.c_void_p(d_out.data_ptr()), C.byref(g), C.c_void_p(_ptr(d_h0)), ws, wsb,
-                                            C.c_void_p(tr.data_ptr()), C.c_size_t(tr.numel() * 4), self._stream())
-        _lib.check(status, "matgcn_backward")
+            status = fn(C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
+                        C.byref(src) if src is not None else None, C.c_void_p(_ptr(h0)), drop,
+                        C.c_void_p(d_out.data_ptr()), C.byref(g), C.c_void_p(_ptr(d_h0)), ws, wsb,
+                        C.c_void_p(tr.data_ptr()), C.c_size_t(tr.numel() * 4), self._stream())
+        _lib.check(status, what)
         if d_h0 is not None:
             grads[self.D_H0] = d_h0
         return grads

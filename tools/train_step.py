@@ -1,10 +1,12 @@
 """Training steps of the bench workload (default Baltimore 403, B=64): forward_train + backward through the plugin
 surface (calculate_loss().backward()), timed with HIP events.
-usage: train_step.py [--deterministic] [--bf16x3] [workload] [steps] [serial|wave] [batch] [fp32|bf16_mix|bf16]
+usage: train_step.py [--deterministic] [--bf16x3] [--device-dropout] [workload] [steps] [serial|wave] [batch] [fp32|bf16_mix|bf16]
 (--deterministic: the model's hip_deterministic = True - the backward's sums in a fixed order, see matgcn_set_deterministic;
 the summary line then also gives the bytes the train buffer grew by)
 (--bf16x3: the model's hip_precision = "bf16x3_train" - the step's graph mixes, both directions, from three bf16 pieces,
 see matgcn_set_train_bf16x3; a hip_precision argument wins over it)
+(--device-dropout: the model's hip_dropout = "device" - the dropout in front of the head drawn inside the kernels that apply
+it, no mask tensor and no F.dropout; see matgcn_forward_train_seeded)
 (serial: matgcn_set_wavefront(0) - every kernel alone on one stream, so a profiler's durations are the kernels' own;
 the last argument is the model's hip_precision; the last line gives the medians over the steps after the first three)"""
 import os, sys
@@ -19,6 +21,9 @@ if deterministic:
 bf16x3 = "--bf16x3" in sys.argv
 if bf16x3:
     sys.argv.remove("--bf16x3")
+device_dropout = "--device-dropout" in sys.argv
+if device_dropout:
+    sys.argv.remove("--device-dropout")
 name = sys.argv[1] if len(sys.argv) > 1 else "bm403"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 w = dict(bench.WORKLOADS[name])
@@ -30,6 +35,8 @@ model.train()
 model.hip_deterministic = deterministic
 if bf16x3:
     model.hip_precision = "bf16x3_train"
+if device_dropout:
+    model.hip_dropout = "device"
 if len(sys.argv) > 5:
     model.hip_precision = sys.argv[5]
 if len(sys.argv) > 3 and sys.argv[3] == "serial":
@@ -59,9 +66,9 @@ print("train buffer %.2f GB  workspace %.2f GB  peak torch memory %.2f GB" % (
 if len(times) > 3:
     import statistics
     med = [statistics.median(t[k] for t in times[3:]) for k in range(3)]
-    print("median of %d steps (%s, B = %d, %s%s): step %.3f ms  forward %.3f ms  backward %.3f ms" % (
-        len(times) - 3, name, w["batch"], model.hip_precision, ", deterministic" if deterministic else "", med[0], med[1],
-        med[2]))
+    print("median of %d steps (%s, B = %d, %s%s%s): step %.3f ms  forward %.3f ms  backward %.3f ms" % (
+        len(times) - 3, name, w["batch"], model.hip_precision, ", deterministic" if deterministic else "",
+        ", device dropout" if device_dropout else "", med[0], med[1], med[2]))
 if deterministic:
     import ctypes
     from multistgraph_amd import _lib
