@@ -38,6 +38,10 @@ struct Plan {
   int NpC;                    // N rounded up to 64: plain N x N scratch leading dimension
   // prepared offsets (floats)
   long oSt, oPlainA, oPlainB, oPlainC;
+  // the tight copy of the support stack, [Np][Mt] with column k*N + n = St's column k*Np + n and Mt = Ks*N rounded up to 64
+  // (zero behind Ks*N): the A operand of the forward's fp32 64 x 64 mixes, which then launch no row tile of pure padding
+  int Mt;
+  long oStT;
   long oWg[MATGCN_MAX_LAYERS], oWu[MATGCN_MAX_LAYERS], oWx[MATGCN_MAX_LAYERS], oBx[MATGCN_MAX_LAYERS];
   long wgFloats[MATGCN_MAX_LAYERS], wuFloats[MATGCN_MAX_LAYERS];   // floats of the two recurrent weight streams
   long oW16g[MATGCN_MAX_LAYERS], oW16u[MATGCN_MAX_LAYERS];         // workspace: their bf16 copies (precision mode 2)
@@ -140,6 +144,8 @@ int make_plan(const matgcn_dims* D, Plan* P) {
     P->oRu[l] = take((long)(P->Cpad[l] + H) * 64);
   }
   P->oHead = take((long)P->headT * H * 32 * P->NTc);
+  P->Mt = (int)rup((long)P->Ks * P->N, 64);
+  P->oStT = take((long)P->Np * P->Mt);     // behind everything else: every other offset stays
   P->preparedFloats = o;
   P->nodeLds = 3 * 64 * 64 * (int)sizeof(float);   // the x-row chunk + two ping-pong chunks of mixed rows
   P->RB = (P->B + 63) / 64;
@@ -747,6 +753,8 @@ int launch_mix_variant(MixTile tile, MixPrec prec, bool flush, int role, MixArgs
   const MixVariant* v = find_variant(MIX, [&](auto& e) {
     return e.tile.rows == tile.rows && e.tile.cols == tile.cols && e.prec == prec && e.flush == flush && e.role == role; });
   if (!v) return MATGCN_ERR_UNSUPPORTED;
+  if (a.stackStride <= 0) a.stackStride = a.Np;   // a caller that does not know the tight stack: the rows of St
+  if (a.stackStride <= 0) return MATGCN_ERR_BAD_ARG;   // k_mix divides by it
   a.nRowTiles = (rows + tile.rows - 1) / tile.rows;
   const dim3 grid((unsigned)(a.nRowTiles * ((a.nColTiles * 64 + tile.cols - 1) / tile.cols)), (unsigned)a.parts);
   hipLaunchKernelGGL(v->fn, grid, dim3(256), 0, s, a);
@@ -768,28 +776,34 @@ inline bool mix_half_tiles(MixPrec prec, const MixArgs& a) {
 // mix of the forward has even strides, and one that had not is an error, never another kernel
 inline bool mix_x3_ok(const MixArgs& a) { return a.Apl != nullptr && a.xTileStride % 2 == 0 && a.ldX % 2 == 0; }
 
-// the graph-mix operands of a forward: the call's Precision::mix, the support stack St [Np][Mp] and, in MIX_BF16X3, its
-// three bf16 planes in the workspace (split_supports)
-struct MixOps { MixPrec prec; const float* St; const void* planes; };
+// the graph-mix operands of a forward: the call's Precision::mix, the support stack St [Np][Mp], in MIX_BF16X3 its
+// three bf16 planes in the workspace (split_supports), and the tight copy of St [Np][Mt] (null: there is none - the
+// Chebyshev products of matgcn_prepare, which read single slots of a stack that is still being built)
+struct MixOps { MixPrec prec; const float* St; const void* planes; const float* tight; };
 inline MixOps mix_ops(const Ctx& c) {
-  return MixOps{c.prec.mix, c.prep + c.P.oSt, c.prec.mix == MIX_BF16X3 ? c.ws + c.P.oPlanes : nullptr};
+  return MixOps{c.prec.mix, c.prep + c.P.oSt, c.prec.mix == MIX_BF16X3 ? c.ws + c.P.oPlanes : nullptr,
+                c.prep + c.P.oStT};
 }
 
 // out[(k,n)][col] = sum_m S_k[n][m] X[m][col]; see k_mix
 int launch_mix(const Plan& P, const MixOps& m, const float* X, long xTileStride, int ldX, int nColTiles,
-               float* out, long sN, long sK, long sT, int Ks, int rowsM, hipStream_t s, bool stepRole = false,
+               float* out, long sN, long sK, long sT, int Ks, hipStream_t s, bool stepRole = false,
                long outFloats = 0) {
-  if (Ks <= 0 || rowsM <= 0) return MATGCN_OK;   // every support folded away: nothing to mix
+  if (Ks <= 0) return MATGCN_OK;   // every support folded away: nothing to mix
   MixArgs a;
   a.St = m.St; a.ldS = P.Mp; a.X = X; a.xTileStride = xTileStride; a.ldX = ldX;
   a.Apl = m.planes; a.plStride = P.planeWords;
   a.out = out; a.sN = sN; a.sK = sK; a.sT = sT; a.outFloats = outFloats;
   a.Np = P.Np; a.N = P.N; a.Ks = Ks; a.nK = P.Np / 16; a.nColTiles = nColTiles;
+  a.stackStride = P.Np;
   ProfScope prof(stepRole ? MATGCN_PROF_MIX : MATGCN_PROF_MIX_PRE, s);
   const MixPrec prec = m.prec;
   if (prec == MIX_BF16X3 && !mix_x3_ok(a)) return MATGCN_ERR_UNSUPPORTED;
   const MixTile tile = prec == MIX_BF16X3 ? MIX_64x128 : mix_half_tiles(prec, a) ? MIX_64x32 : MIX_64x64;
-  return launch_mix_variant(tile, prec, mix_flush(prec, a), stepRole ? 1 : 0, a, rowsM, s);
+  // the fp32 64 x 64 kernel reads the tight stack: Ks*N stacked rows instead of Ks*Np (19 row tiles instead of 20 at
+  // N = 403, Ks = 3); every other variant keeps St and its grid
+  if (prec == MIX_F32 && tile.cols == 64 && m.tight) { a.St = m.tight; a.ldS = P.Mt; a.stackStride = P.N; }
+  return launch_mix_variant(tile, prec, mix_flush(prec, a), stepRole ? 1 : 0, a, Ks * a.stackStride, s);
 }
 
 // mix of `rows` contiguous [Np][64] slabs into the node-major buffer G [N][rows][Ks][64]
@@ -797,7 +811,7 @@ int launch_mix(const Plan& P, const MixOps& m, const float* X, long xTileStride,
 int mix_rows(const Plan& P, const MixOps& m, const float* X, int rows, float* G, hipStream_t s, bool stepRole = false,
              long nodeStride = 0) {
   const long sN = nodeStride ? nodeStride : (long)rows * P.Ks * H;
-  return launch_mix(P, m, X, (long)P.Np * H, H, rows, G, sN, H, (long)P.Ks * H, P.Ks, P.Ks * P.Np, s, stepRole,
+  return launch_mix(P, m, X, (long)P.Np * H, H, rows, G, sN, H, (long)P.Ks * H, P.Ks, s, stepRole,
                     (long)(P.N - 1) * sN + (long)rows * P.Ks * H);
 }
 
@@ -827,7 +841,7 @@ int fold_x0(const Ctx& c, const float* xin, int Tq, hipStream_t s) {
   hipLaunchKernelGGL(k_x0_to_matrix, dim3(blocks_for((size_t)P.Np * ld)), dim3(256), 0, s, xin, X0m, rows, P.Np, P.C0,
                      ld);
   CHECK_LAUNCH();
-  RETURN_IF(launch_mix(P, mix_ops(c), X0m, 64, ld, ld / 64, MX0, (long)ld, (long)P.Np * ld, 64, P.Ks, P.Ks * P.Np, s));
+  RETURN_IF(launch_mix(P, mix_ops(c), X0m, 64, ld, ld / 64, MX0, (long)ld, (long)P.Np * ld, 64, P.Ks, s));
   hipLaunchKernelGGL(k_build_xa0, dim3(blocks_for((size_t)Tq * P.N * P.B * P.Kx)), dim3(256), 0, s, xin, MX0,
                      c.ws + P.oXA0, P.B, Tq, P.N, P.Np, P.C0, P.Ks, P.Kx, ld);
   return launch_ok();
@@ -1519,14 +1533,21 @@ static int prepare_impl(const matgcn_dims* dims, const matgcn_params* params, vo
     int iPrev1 = 0, iPrev2 = -1;
     for (int k = 2; k < dims->cheb_k; ++k) {
       const int iOut = (iPrev2 < 0) ? 1 : 3 - iPrev1 - iPrev2;
-      RETURN_IF(launch_mix(P, MixOps{MIX_F32, St + col0, nullptr}, buf[iPrev1], 64, P.NpC, P.NpC / 64, buf[iOut], (long)P.NpC, 0, 64, 1, P.Np,
-                           c.s));
+      RETURN_IF(launch_mix(P, MixOps{MIX_F32, St + col0, nullptr, nullptr}, buf[iPrev1], 64, P.NpC, P.NpC / 64, buf[iOut],
+                           (long)P.NpC, 0, 64, 1, c.s));
       hipLaunchKernelGGL(k_cheb_combine, tgrid, dim3(256), 0, c.s, buf[iOut], iPrev2 < 0 ? nullptr : buf[iPrev2],
                          iPrev2 < 0 ? 1 : 0, P.N, P.NpC, St, P.Mp, (slot0 + k - 1) * P.Np, buf[iOut]);
       CHECK_LAUNCH();
       iPrev2 = iPrev1;
       iPrev1 = iOut;
     }
+  }
+  // the stack is complete: its tight copy for the forward's fp32 mixes, on the stream that wrote St and ahead of the fork
+  // below, so every event a chain waits for covers it
+  if ((long)P.Np * P.Mt > 0) {
+    hipLaunchKernelGGL(k_stack_tight, dim3(blocks_for((size_t)P.Np * P.Mt)), dim3(256), 0, c.s, St, P.Mp, P.Np, P.N, P.Ks,
+                       prep + P.oStT, P.Mt);
+    CHECK_LAUNCH();
   }
   // node-adaptive weights: independent of the support stack and of each other, so the per-(layer, part) pieces
   // go to the library's internal streams (forked from / joined into the caller's stream) and overlap

@@ -92,6 +92,10 @@ struct MixArgs {
   // [slot][Np32 / 8][ldS] words - nK counts one slot's groups of 16, and a part walks kSlots slots back to back
   // (aPartStride is in words there)
   int kSlots = 1;
+  // k_mix, roles 0 and 1 only (launch_mix; behind everything else for the same reason): stacked output row r is support
+  // r / stackStride, node r % stackStride - N on the tight stack (column k*N + n), Np on St (0: launch_mix_variant
+  // takes Np)
+  int stackStride = 0;
 };
 
 struct HeadArgs {

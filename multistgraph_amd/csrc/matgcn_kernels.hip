@@ -11,6 +11,7 @@
 //
 // Data layout (all fp32, Np = N rounded up to 16, H = 64; DESIGN.md section 3 has the full tables):
 //   St   [Np][Mp]              transposed dense support stack, column k*Np+n holds S_k[n][.]   (mix A operand)
+//   StT  [Np][rup(Ks*N,64)]    its tight copy, column k*N+n (k_stack_tight)   (A operand of the forward's fp32 64 x 64 mix)
 //   Hx   [rows][Np][64]        recurrent state / any per-row node features                    (mix B operand)
 //   G    [N][rows][Ks][64]     graph-mixed features, node-major                                (node GEMM A operand)
 //   W*   [N][K/16][OT][64][4]  node-adaptive weights in 16x16x4 B-fragment order               (node GEMM B operand)
@@ -132,6 +133,18 @@ __global__ __launch_bounds__(256) void k_cheb_combine(const float* __restrict__ 
     const int m = bx + j, n = by + tx;
     if (m < N && n < N) St[(size_t)m * ldS + col0 + n] = tile[tx][j];
   }
+}
+
+// The finished stack St [Np][ldS] (column k*Np + n) -> its tight copy [Np][ldT] (column k*N + n, zero from Ks*N on):
+// the A operand of the forward's fp32 64 x 64 mixes (k_mix), which then launch over Ks*N stacked rows.  Writes every
+// element of the copy; once per matgcn_prepare.
+__global__ __launch_bounds__(256) void k_stack_tight(const float* __restrict__ St, int ldS, int Np, int N, int Ks,
+                                                     float* __restrict__ tight, int ldT) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)Np * ldT) return;
+  const int m = (int)(idx / ldT), c = (int)(idx % ldT);
+  const int k = c / N, n = c - k * N;
+  tight[idx] = k < Ks ? St[(size_t)m * ldS + k * Np + n] : 0.f;
 }
 
 // =================================================================================================
@@ -757,7 +770,9 @@ __global__ __launch_bounds__(256) void k_mix(MixArgs a) {
     const int lrow = u * 8 + (lane >> 3), q = lane & 7;
     const float4 v = v4[u];
     const int row = row0 + wr * 32 + lrow;
-    const int k = row / a.Np, n = row - k * a.Np;
+    // stacked row -> (support, node): the forward's mixes take the stride of their A operand (N on the tight stack)
+    const int stride = ROLE != 2 ? a.stackStride : a.Np;
+    const int k = row / stride, n = row - k * stride;
     const bool ok = k < a.Ks && n < a.N;
     const size_t off = (size_t)colTile * a.sT + (size_t)n * a.sN + (size_t)k * a.sK + wc * 32 + q * 4;
     if (wt) {
