@@ -842,8 +842,16 @@ int fold_x0(const Ctx& c, const float* xin, int Tq, hipStream_t s) {
                      ld);
   CHECK_LAUNCH();
   RETURN_IF(launch_mix(P, mix_ops(c), X0m, 64, ld, ld / 64, MX0, (long)ld, (long)P.Np * ld, 64, P.Ks, s));
-  hipLaunchKernelGGL(k_build_xa0, dim3(blocks_for((size_t)Tq * P.N * P.B * P.Kx)), dim3(256), 0, s, xin, MX0,
-                     c.ws + P.oXA0, P.B, Tq, P.N, P.Np, P.C0, P.Ks, P.Kx, ld);
+  // k_build_xa0's tile: (Ks + 1) runs of tChunk*C0 floats per sample, bChunk samples - up to 16 of them (a destination
+  // run of 16*Kx floats is at least 1 KB) and whole sequences while the tile stays within 32 KB of LDS
+  const long perStep = (long)(P.Ks + 1) * P.C0, ldsFloats = 8192;
+  int bChunk = P.B < 16 ? P.B : 16, tChunk = Tq;
+  while (bChunk > 1 && perStep * tChunk * bChunk > ldsFloats) bChunk >>= 1;
+  while (tChunk > 1 && perStep * tChunk * bChunk > ldsFloats) tChunk = (tChunk + 1) / 2;
+  if (perStep * tChunk * bChunk > ldsFloats) return MATGCN_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)P.N, (unsigned)((P.B + bChunk - 1) / bChunk), (unsigned)((Tq + tChunk - 1) / tChunk));
+  hipLaunchKernelGGL(k_build_xa0, grid, dim3(256), (size_t)(perStep * tChunk * bChunk) * sizeof(float), s, X0m, MX0,
+                     c.ws + P.oXA0, P.B, Tq, P.N, P.Np, P.C0, P.Ks, P.Kx, ld, bChunk, tChunk);
   return launch_ok();
 }
 
@@ -1050,6 +1058,21 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
                        P.nKg, reinterpret_cast<uint4*>(c.ws + P.oPlanes), P.planeWords);
     CHECK_LAUNCH();
   }
+  // ---- state and padding rows of every layer: one launch on the caller's stream, in front of the fork event, so every
+  // chain and x-part stream is ordered behind it (k_state_init; training with h0: the backward's copy of h_{-1} too) ----
+  {
+    StateInitArgs ia;
+    memset(&ia, 0, sizeof(ia));
+    for (int l = 0; l < P.L; ++l) {
+      ia.zhx[l] = c.ws + P.oZHx[l]; ia.hx[l] = c.ws + P.oHx[l]; ia.seq[l] = c.ws + P.oSeq[l];
+      ia.h0[l] = h0User ? h0User + (size_t)l * P.B * P.N * H : nullptr;
+      ia.h0dst[l] = (c.train && h0User) ? c.train + c.R.oH0 + (size_t)l * P.B * P.Np * H : nullptr;
+    }
+    const size_t work = (size_t)P.B * P.Np * 16 + (size_t)P.B * P.T * (P.Np - P.N) * 16;
+    hipLaunchKernelGGL(k_state_init, dim3(blocks_for(work), (unsigned)P.L), dim3(256), 0, c.s, ia, P.B, P.B * P.T, P.N,
+                       P.Np);
+    CHECK_LAUNCH();
+  }
   if (multi) {
     HIP_OK(hipEventRecord(W.fork, c.s));
     for (int l = 1; l < P.L; ++l) {
@@ -1064,26 +1087,6 @@ int encoder_chains(const Ctx& c, const float* x0p, const float* h0User, float* f
   if (!P.gcnOff) RETURN_IF(fold_x0(c, x0p, P.T, c.s));
   const long stepRows = (long)P.B * P.Np * H;     // one step of a time-major sequence
   auto chain_stream = [&](int l) { return (l == 0 || !multi) ? c.s : W.chain[l]; };
-  // ---- per layer: state, padding rows ----
-  for (int l = 0; l < P.L; ++l) {
-    hipStream_t cs = chain_stream(l);
-    RETURN_IF(zero_async(c.ws + P.oZHx[l], (long)P.B * P.Np * H, cs));
-    if (P.Np != P.N) {
-      hipLaunchKernelGGL(k_zero_pad_rows, dim3(blocks_for((size_t)P.B * P.T * (P.Np - P.N) * H)), dim3(256), 0, cs,
-                         c.ws + P.oSeq[l], P.B * P.T, P.N, P.Np, H);
-      CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(k_pack_rows, dim3(blocks_for((size_t)P.B * P.Np * H)), dim3(256), 0, cs,
-                       h0User ? h0User + (size_t)l * P.B * P.N * H : nullptr,
-                       c.ws + P.oHx[l], P.B, P.N, P.Np, H);
-    CHECK_LAUNCH();
-    if (c.train && h0User) {   // the backward needs h_{-1} of every layer (gate algebra, weight gradients of step 0)
-      hipLaunchKernelGGL(k_pack_rows, dim3(blocks_for((size_t)P.B * P.Np * H)), dim3(256), 0, cs,
-                         h0User + (size_t)l * P.B * P.N * H, c.train + c.R.oH0 + (size_t)l * P.B * P.Np * H, P.B, P.N,
-                         P.Np, H);
-      CHECK_LAUNCH();
-    }
-  }
   int nextChunk[MATGCN_MAX_LAYERS] = {0};
   // ---- one step of one layer ----
   auto enqueue_step = [&](int l, int t) -> int {
@@ -1180,8 +1183,7 @@ int fuse_padded(const Ctx& c, const float* X, float* x0p, const int32_t* labelSt
                 const int32_t* relSteps = nullptr, int64_t seriesSteps = 0) {
   const Plan& P = c.P;
   const matgcn_dims* D = c.D;
-  RETURN_IF(zero_async(x0p, (long)P.B * P.T * P.Np * P.C0, c.s));
-  FuseArgs a;
+  FuseArgs a;      // (k_fuse_heads writes every element of x0p, the padding rows as zeros: no memset)
   memset(&a, 0, sizeof(a));
   a.X = X; a.x0 = x0p; a.tsg = c.prm->weight_tsg;
   a.labelStart = labelStart; a.seriesSteps = (long)seriesSteps;
@@ -1191,7 +1193,7 @@ int fuse_padded(const Ctx& c, const float* X, float* x0p, const int32_t* labelSt
   for (int j = 0; j < P.C0 - P.od; ++j) a.extSrc[j] = D->ext_src[j];
   a.B = P.B; a.T = P.T; a.N = P.N; a.Np = P.Np; a.C0 = P.C0; a.od = P.od; a.F = D->x_feat;
   a.xSteps = D->x_steps; a.startDim = D->start_dim; a.nHeads = D->n_heads; a.nTs = D->n_ts;
-  hipLaunchKernelGGL(k_fuse_heads, dim3(blocks_for((size_t)P.B * P.T * P.N)), dim3(256), 0, c.s, a);
+  hipLaunchKernelGGL(k_fuse_heads, dim3(blocks_for((size_t)P.B * P.T * P.Np)), dim3(256), 0, c.s, a);
   return launch_ok();
 }
 
@@ -1494,19 +1496,56 @@ static int prepare_impl(const matgcn_dims* dims, const matgcn_params* params, vo
   float* prep = (float*)prepared;
   float* St = prep + P.oSt;
   const int per = P.per;  // stack slots per first-order support
-  if (P.Mp > 0) RETURN_IF(zero_async(St, (long)P.Np * P.Mp, c.s));
   const bool cheb = dims->cheb_k > 2 && P.nDenseFirst > 0;
   const bool hasAdp = dims->adp_mode != MATGCN_ADP_NONE && !P.gcnOff;
+  // cheb_k == 2 (every cheb_order = 2 model): one slot per dense support, no recursion, no accumulation - the supports go
+  // straight into both stacks (k_adaptive_stack, k_static_stack), which also write all of their padding; no memset, no
+  // staging in plainA (prepare-internal scratch, not written on this path), no k_stack_tight
+  const bool direct = dims->cheb_k == 2 && !P.sumDense && P.Ks > 0;
+  if (direct) {
+    const bool adpDense = hasAdp && P.denseFirst[0] == 0;    // the adaptive support is never diagonal: always slot 0
+    const int nStatic = P.nDenseFirst - (adpDense ? 1 : 0);
+    float* StT = prep + P.oStT;
+    if (adpDense) {
+      const bool bi = dims->adp_mode == MATGCN_ADP_BI;
+      const float* e1 = bi ? params->node_emb : params->node_vec1;
+      const float* e2 = bi ? nullptr : params->node_vec2;
+      const int rank = bi ? dims->embed_dim : dims->adj_rank, tail = nStatic == 0 ? 1 : 0;
+      // four rows of logits per workgroup while they fit the 64 KB of LDS a kernel gets without opting in
+      if (P.N <= 3072)
+        hipLaunchKernelGGL(k_adaptive_stack<4>, dim3((unsigned)(P.Np / 4)), dim3(1024), (size_t)4 * P.N * sizeof(float), c.s,
+                           e1, e2, rank, bi ? 1 : 0, P.N, P.Np, P.Ks, St, P.Mp, StT, P.Mt, tail);
+      else
+        hipLaunchKernelGGL(k_adaptive_stack<1>, dim3((unsigned)P.Np), dim3(256), (size_t)P.N * sizeof(float), c.s,
+                           e1, e2, rank, bi ? 1 : 0, P.N, P.Np, P.Ks, St, P.Mp, StT, P.Mt, tail);
+      CHECK_LAUNCH();
+    }
+    if (nStatic > 0) {
+      StaticStackArgs sa;
+      memset(&sa, 0, sizeof(sa));
+      int ns = 0;
+      for (int fd = adpDense ? 1 : 0; fd < P.nDenseFirst; ++fd, ++ns) {
+        const int sidx = P.denseFirst[fd] - (dims->adp_mode != MATGCN_ADP_NONE ? 1 : 0);
+        sa.S[ns] = params->static_supports + (size_t)sidx * P.N * P.N;
+        sa.slot[ns] = fd;
+      }
+      const unsigned tiles = (unsigned)((P.Np + 31) / 32);
+      hipLaunchKernelGGL(k_static_stack, dim3(tiles, tiles, (unsigned)ns), dim3(256), 0, c.s, sa, P.N, P.Np, P.Ks, St, P.Mp,
+                         StT, P.Mt, 1);
+      CHECK_LAUNCH();
+    }
+  }
+  if (!direct && P.Mp > 0) RETURN_IF(zero_async(St, (long)P.Np * P.Mp, c.s));
   float* plainA = (cheb || hasAdp) ? prep + P.oPlainA : nullptr;  // T_{k-1}; staging of the adaptive adjacency
   float* plainB = cheb ? prep + P.oPlainB : nullptr;  // T_{k-2} / product scratch
   float* plainC = cheb ? prep + P.oPlainC : nullptr;
-  if (cheb || hasAdp) RETURN_IF(zero_async(plainA, (long)P.Np * P.NpC, c.s));
+  if (!direct && (cheb || hasAdp)) RETURN_IF(zero_async(plainA, (long)P.Np * P.NpC, c.s));
   if (cheb) {
     RETURN_IF(zero_async(plainB, (long)P.Np * P.NpC, c.s));
     RETURN_IF(zero_async(plainC, (long)P.Np * P.NpC, c.s));
   }
   const dim3 tgrid((unsigned)((P.N + 31) / 32), (unsigned)((P.N + 31) / 32));
-  for (int fd = 0; fd < P.nDenseFirst; ++fd) {   // diagonal supports are folded into the weights instead
+  for (int fd = 0; fd < P.nDenseFirst && !direct; ++fd) {   // diagonal supports are folded into the weights instead
     const int f = P.denseFirst[fd];
     const int slot0 = P.sumDense ? 0 : fd * per;   // cheb_order = 1: every dense support adds into the one slot
     const int col0 = slot0 * P.Np;
@@ -1544,7 +1583,7 @@ static int prepare_impl(const matgcn_dims* dims, const matgcn_params* params, vo
   }
   // the stack is complete: its tight copy for the forward's fp32 mixes, on the stream that wrote St and ahead of the fork
   // below, so every event a chain waits for covers it
-  if ((long)P.Np * P.Mt > 0) {
+  if (!direct && (long)P.Np * P.Mt > 0) {
     hipLaunchKernelGGL(k_stack_tight, dim3(blocks_for((size_t)P.Np * P.Mt)), dim3(256), 0, c.s, St, P.Mp, P.Np, P.N, P.Ks,
                        prep + P.oStT, P.Mt);
     CHECK_LAUNCH();
@@ -1563,6 +1602,36 @@ static int prepare_impl(const matgcn_dims* dims, const matgcn_params* params, vo
     HIP_OK(hipEventRecord(W.fork, c.s));
     HIP_OK(hipStreamWaitEvent(pool[1], W.fork, 0));
     HIP_OK(hipStreamWaitEvent(pool[2], W.fork, 0));
+  }
+  // The dense weights - Rg_l, Ru_l of every layer and Head - in one launch (k_prep_dense), off the caller's stream when
+  // the weight streams are: on pool[1], in front of everything else there.  Who reads them, and why each is ordered
+  // behind this launch:
+  //  * lazy: the launch precedes the records of E.l0[0] and E.l1[0] on pool[1], so both events cover it.
+  //    - the wavefront forward, forward_train and forward_mc (make_ctx without the join; encoder_chains): Rg_0 / Ru_0 are
+  //      first read by layer 0's update kernel of step 0, enqueued behind prep_wait(cs, 1) = E.l0; Rg_l / Ru_l, l >= 1, by
+  //      the chains W.chain[l], which take prep_wait(.., 2) = E.l1 when they fork; one stream, precision mode 2 and
+  //      gcn_off take prep_wait(c.s, 3) before anything else.  Head is read by k_head / k_head_mc on the caller's stream
+  //      behind the encoder - behind layer 0's chain, which waited for E.l0.
+  //    - every other entry point that takes `prepared` (the unit entry points, matgcn_backward, matgcn_prepare_join)
+  //      goes through make_ctx, which orders its stream behind all four events first.
+  //  * fork without lazy: pool[1] is joined into the caller's stream below (W.done[1]) before matgcn_prepare returns.
+  //  * matgcn_set_wavefront(0): pool[1] is not used; the launch runs on the caller's stream like everything else.
+  // (Writes after reads: pool[1] waits for W.fork, recorded on the caller's stream behind whatever read the old values.)
+  {
+    PrepDenseArgs da;
+    memset(&da, 0, sizeof(da));
+    size_t units = 0;
+    int nm = 0;
+    for (int l = 0; l < P.L; ++l) {
+      const int I = P.Cl[l] + H, nG1 = (P.Cpad[l] + H) / 16;
+      da.m[nm++] = DenseMat{params->res_gate[l].weight, prep + P.oRg[l], I, 128, P.Cl[l], P.Cpad[l], nG1, 0};
+      da.m[nm++] = DenseMat{params->res_update[l].weight, prep + P.oRu[l], I, 64, P.Cl[l], P.Cpad[l], nG1, 0};
+      if ((size_t)nG1 * 8 * 64 > units) units = (size_t)nG1 * 8 * 64;
+    }
+    da.m[nm++] = DenseMat{params->end_conv_weight, prep + P.oHead, P.headT * H, P.CH, 0, 0, P.headT * H, P.NTc};
+    if ((size_t)(P.headT * H / 8) * P.NTc * 64 > units) units = (size_t)(P.headT * H / 8) * P.NTc * 64;
+    hipLaunchKernelGGL(k_prep_dense, dim3(blocks_for(units), (unsigned)nm), dim3(256), 0, fork ? pool[1] : c.s, da);
+    CHECK_LAUNCH();
   }
   int piece = 0;
   const StackMap map = build_stack_map(P, dims, params);
@@ -1630,17 +1699,7 @@ static int prepare_impl(const matgcn_dims* dims, const matgcn_params* params, vo
       HIP_OK(hipEventRecord(E.l0[0], pool[1]));
       HIP_OK(hipEventRecord(E.l0[1], pool[2]));
     }
-    const int nG1 = (P.Cpad[l] + H) / 16;
-    hipLaunchKernelGGL(k_prep_linear16, dim3(blocks_for((size_t)nG1 * 8 * 64)), dim3(256), 0, c.s,
-                       params->res_gate[l].weight, I, 128, P.Cl[l], P.Cpad[l], nG1, prep + P.oRg[l]);
-    CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_prep_linear16, dim3(blocks_for((size_t)nG1 * 4 * 64)), dim3(256), 0, c.s,
-                       params->res_update[l].weight, I, 64, P.Cl[l], P.Cpad[l], nG1, prep + P.oRu[l]);
-    CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(k_prep_linear, dim3(blocks_for((size_t)(P.headT * H / 8) * P.NTc * 64)), dim3(256), 0, c.s,
-                     params->end_conv_weight, P.headT * H, P.CH, 0, 0, P.headT * H, P.NTc, prep + P.oHead);
-  CHECK_LAUNCH();
   if (lazy) {          // no join: every consumer waits for what it reads (make_ctx, encoder_chains)
     HIP_OK(hipEventRecord(E.l1[0], pool[1]));
     HIP_OK(hipEventRecord(E.l1[1], pool[2]));

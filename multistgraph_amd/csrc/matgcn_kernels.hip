@@ -11,7 +11,8 @@
 //
 // Data layout (all fp32, Np = N rounded up to 16, H = 64; DESIGN.md section 3 has the full tables):
 //   St   [Np][Mp]              transposed dense support stack, column k*Np+n holds S_k[n][.]   (mix A operand)
-//   StT  [Np][rup(Ks*N,64)]    its tight copy, column k*N+n (k_stack_tight)   (A operand of the forward's fp32 64 x 64 mix)
+//   StT  [Np][rup(Ks*N,64)]    its tight copy, column k*N+n (written with St: k_adaptive_stack / k_static_stack; k_stack_tight on
+//                              the Chebyshev and cheb_order = 1 paths)   (A operand of the forward's fp32 64 x 64 mix)
 //   Hx   [rows][Np][64]        recurrent state / any per-row node features                    (mix B operand)
 //   G    [N][rows][Ks][64]     graph-mixed features, node-major                                (node GEMM A operand)
 //   W*   [N][K/16][OT][64][4]  node-adaptive weights in 16x16x4 B-fragment order               (node GEMM B operand)
@@ -145,6 +146,133 @@ __global__ __launch_bounds__(256) void k_stack_tight(const float* __restrict__ S
   const int m = (int)(idx / ldT), c = (int)(idx % ldT);
   const int k = c / N, n = c - k * N;
   tight[idx] = k < Ks ? St[(size_t)m * ldS + k * Np + n] : 0.f;
+}
+
+// ---- cheb_k == 2 without sumDense: both stacks in at most two launches, no memset, no staging matrix ----
+// Every dense first-order support owns exactly one slot, so a support can be stored straight into its columns of St
+// (column k*Np + n) and of the tight copy StT (column k*N + n).  k_adaptive_stack writes slot 0 (the adaptive support is
+// always the first dense one), k_static_stack every other slot, and together they write EVERY element of both buffers:
+// rows m >= N and the columns n >= N of a slot as zeros, and - the launch that is told so (`tail`) - the columns behind
+// the last slot (St: Ks*Np .. ldS, StT: Ks*N .. ldT).  `prepared` may hold anything before.
+__device__ __forceinline__ void stack_tail_zero(float* __restrict__ St, int ldS, float* __restrict__ StT, int ldT,
+                                                int Np, int N, int Ks, int block, int nBlocks, int tid, int nThreads) {
+  const int s0 = Ks * Np, t0 = Ks * N, ws = ldS - s0, wt = ldT - t0;
+  for (int m = block; m < Np; m += nBlocks) {
+    for (int c = tid; c < ws; c += nThreads) St[(size_t)m * ldS + s0 + c] = 0.f;
+    for (int c = tid; c < wt; c += nThreads) StT[(size_t)m * ldT + t0 + c] = 0.f;
+  }
+}
+
+// The row softmax of k_adaptive_adj, value for value (same partition of a row over 256 threads, same reduction trees,
+// same expf, maximum and division), for ROWS rows per workgroup - one group of 256 threads each - so that the transposed
+// store moves ROWS consecutive columns per row m: 16 bytes at ROWS = 4 (ROWS = 1: graphs whose four rows of logits
+// would not fit the LDS).  grid = Np / ROWS (Np is a multiple of 16); dynamic LDS = ROWS * N floats.
+template <int ROWS>
+__global__ __launch_bounds__(256 * ROWS) void k_adaptive_stack(const float* __restrict__ e1, const float* __restrict__ e2,
+                                                               int rank, int bidir, int N, int Np, int Ks,
+                                                               float* __restrict__ St, int ldS, float* __restrict__ StT,
+                                                               int ldT, int tail) {
+  extern __shared__ float logitsAll[];   // ROWS x N floats
+  __shared__ float redAll[ROWS][256];
+  __shared__ float erowAll[ROWS][64];
+  __shared__ float invAll[ROWS];
+  const int sub = threadIdx.x >> 8, tid = threadIdx.x & 255;
+  const int n0 = blockIdx.x * ROWS, n = n0 + sub;
+  const bool live = n < N;                 // a padding column: zeros, but every barrier is still met
+  float* logits = logitsAll + (size_t)sub * N;
+  float* red = redAll[sub];
+  float* erow = erowAll[sub];
+  if (live)
+    for (int r = tid; r < rank; r += 256) erow[r] = e1[(size_t)n * rank + r];
+  __syncthreads();
+  float mx = 0.f;  // relu output is >= 0
+  if (live)
+    for (int m = tid; m < N; m += 256) {
+      float s = 0.f;
+      if (bidir) {
+        for (int r = 0; r < rank; ++r) s = fmaf(erow[r], e1[(size_t)m * rank + r], s);
+      } else {
+        for (int r = 0; r < rank; ++r) s = fmaf(erow[r], e2[(size_t)r * N + m], s);
+      }
+      s = fmaxf(s, 0.f);
+      logits[m] = s;
+      mx = fmaxf(mx, s);
+    }
+  red[tid] = mx;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]);
+    __syncthreads();
+  }
+  mx = red[0];
+  __syncthreads();
+  float sum = 0.f;
+  if (live)
+    for (int m = tid; m < N; m += 256) {
+      const float e = expf(logits[m] - mx);
+      logits[m] = e;
+      sum += e;
+    }
+  red[tid] = sum;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) invAll[sub] = 1.0f / red[0];
+  __syncthreads();
+  // transposed store: row m of both stacks takes columns n0 .. n0 + ROWS - 1 of slot 0
+  for (int m = threadIdx.x; m < Np; m += 256 * ROWS) {
+    float v[ROWS];
+#pragma unroll
+    for (int j = 0; j < ROWS; ++j) v[j] = (m < N && n0 + j < N) ? logitsAll[(size_t)j * N + m] * invAll[j] : 0.f;
+    float* ds = St + (size_t)m * ldS + n0;       // n0 + ROWS <= Np: inside the slot
+    float* dt = StT + (size_t)m * ldT + n0;      // columns < N only: column N is the next support's first
+    if (ROWS == 4) {
+      *reinterpret_cast<float4*>(ds) = make_float4(v[0], v[1], v[2], v[3]);
+      if (n0 + 4 <= N) *reinterpret_cast<float4*>(dt) = make_float4(v[0], v[1], v[2], v[3]);
+      else
+#pragma unroll
+        for (int j = 0; j < ROWS; ++j) if (n0 + j < N) dt[j] = v[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < ROWS; ++j) {
+        ds[j] = v[j];
+        if (n0 + j < N) dt[j] = v[j];
+      }
+    }
+  }
+  if (tail) stack_tail_zero(St, ldS, StT, ldT, Np, N, Ks, blockIdx.x, gridDim.x, threadIdx.x, 256 * ROWS);
+}
+
+// every static dense support -> its slot of both stacks: blockIdx.z picks the support, a workgroup turns one 32 x 32
+// tile through LDS as k_static_transpose does and covers the Np x Np extent of the slot
+struct StaticStackArgs {
+  const float* S[4];     // (N, N) supports
+  int slot[4];           // stack slot of each
+};
+__global__ __launch_bounds__(256) void k_static_stack(StaticStackArgs a, int N, int Np, int Ks, float* __restrict__ St,
+                                                      int ldS, float* __restrict__ StT, int ldT, int tail) {
+  __shared__ float tile[32][33];
+  const float* __restrict__ S = a.S[blockIdx.z];
+  const int slot = a.slot[blockIdx.z];
+  const int bx = blockIdx.x * 32, by = blockIdx.y * 32;  // bx: m block, by: n block
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+  for (int j = ty; j < 32; j += 8) {
+    const int n = by + j, m = bx + tx;
+    tile[j][tx] = (n < N && m < N) ? S[(size_t)n * N + m] : 0.f;
+  }
+  __syncthreads();
+  for (int j = ty; j < 32; j += 8) {
+    const int m = bx + j, n = by + tx;
+    if (m < Np && n < Np) {
+      St[(size_t)m * ldS + slot * Np + n] = tile[tx][j];
+      if (n < N) StT[(size_t)m * ldT + slot * N + n] = tile[tx][j];
+    }
+  }
+  if (tail)
+    stack_tail_zero(St, ldS, StT, ldT, Np, N, Ks, (int)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x),
+                    (int)(gridDim.x * gridDim.y * gridDim.z), threadIdx.x, 256);
 }
 
 // =================================================================================================
@@ -427,9 +555,9 @@ __global__ __launch_bounds__(256) void k_prep_bias(const float* __restrict__ E, 
 
 // nn.Linear / Conv2d weight (O, I) -> fragment order [jg][OT][64][4] of B[j][o] = W[o][in(j)].
 // Rows j < Cpad map to input j (zero beyond C); rows j >= Cpad map to input C + (j - Cpad).
-__global__ __launch_bounds__(256) void k_prep_linear(const float* __restrict__ W, int I, int O, int C, int Cpad,
-                                                     int rows, int OT, float* __restrict__ out) {
-  const int unit = blockIdx.x * 256 + threadIdx.x;
+// (one matrix of k_prep_dense, matgcn_node16.hip: `unit` is the float4 this thread writes)
+__device__ __forceinline__ void prep_linear(const float* __restrict__ W, int I, int O, int C, int Cpad, int rows, int OT,
+                                            float* __restrict__ out, int unit) {
   const int units = (rows >> 3) * OT * 64;
   if (unit >= units) return;
   const int lane = unit & 63, ot = (unit >> 6) % OT, jg = (unit >> 6) / OT;
@@ -537,11 +665,16 @@ __device__ __forceinline__ size_t series_row(long row, long steps) {
 
 __global__ __launch_bounds__(256) void k_fuse_heads(FuseArgs a) {
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const size_t total = (size_t)a.B * a.T * a.N;
+  const size_t total = (size_t)a.B * a.T * a.Np;   // the padding rows n >= N too: they are written as zeros here
   if (idx >= total) return;
-  const int n = idx % a.N;
-  const int t = (idx / a.N) % a.T;
-  const int b = idx / ((size_t)a.N * a.T);
+  const int n = idx % a.Np;
+  const int t = (idx / a.Np) % a.T;
+  const int b = idx / ((size_t)a.Np * a.T);
+  if (n >= a.N) {
+    float* pad = a.x0 + idx * a.C0;
+    for (int c = 0; c < a.C0; ++c) pad[c] = 0.f;
+    return;
+  }
   float gmax = -3.0e38f, gsum = 0.f;
   for (int h = 0; h < a.nTs; ++h) gmax = fmaxf(gmax, a.tsg[h]);
   for (int h = 0; h < a.nTs; ++h) gsum += expf(a.tsg[h] - gmax);
@@ -584,25 +717,82 @@ __global__ __launch_bounds__(256) void k_x0_to_matrix(const float* __restrict__ 
 
 // folded x-part of the layer-0 node GEMM: XA0[t][n][b][Kx] = [x0 (k=0) | mix_k(x0), k<Ks | 1.0 | 0...]
 // (the 1.0 column meets the bias row of the folded weights)
-__global__ __launch_bounds__(256) void k_build_xa0(const float* __restrict__ x0p, const float* __restrict__ MX0,
+// Both sides move whole lines.  For one node n the sources are rows of two matrices - X0m[n][.] (the x0 columns, as
+// k_x0_to_matrix laid them out) and MX0[k*Np + n][.] - whose column (b*T + t)*C0 + c is contiguous over (t, c) for one
+// b; the destination XA0[t][n][b0 ..][0 .. Kx) is contiguous over (b, j) for one t.  A workgroup takes (n, bChunk
+// samples, tChunk steps): it reads (Ks + 1) * bChunk runs of tChunk*C0 floats into LDS [k][b][t*C0 + c] and writes
+// tChunk runs of bChunk*Kx floats with 16-byte stores (Kx is a multiple of 16).  bChunk / tChunk: fold_x0, from the
+// LDS the tile takes.  grid = (N, ceil(B / bChunk), ceil(T / tChunk)); dynamic LDS = (Ks+1)*bChunk*tChunk*C0 floats.
+__global__ __launch_bounds__(256) void k_build_xa0(const float* __restrict__ X0m, const float* __restrict__ MX0,
                                                    float* __restrict__ XA0, int B, int T, int N, int Np, int C0,
-                                                   int Ks, int Kx, int ld) {
+                                                   int Ks, int Kx, int ld, int bChunk, int tChunk) {
+  extern __shared__ float xs[];
+  const int n = blockIdx.x, b0 = blockIdx.y * bChunk, t0 = blockIdx.z * tChunk;
+  const int nb = min(bChunk, B - b0), nt = min(tChunk, T - t0);
+  const int run = nt * C0, perK = nb * run;
+  for (int i = threadIdx.x; i < (Ks + 1) * perK; i += 256) {
+    const int k = i / perK, r = i - k * perK;
+    const int bb = r / run, q = r - bb * run;
+    const float* src = k == 0 ? X0m + (size_t)n * ld : MX0 + ((size_t)(k - 1) * Np + n) * ld;
+    xs[i] = src[((size_t)(b0 + bb) * T + t0) * C0 + q];
+  }
+  __syncthreads();
+  const int nx = (Ks + 1) * C0, kx4 = Kx >> 2, perT = nb * kx4;
+  for (int i = threadIdx.x; i < nt * perT; i += 256) {
+    const int tt = i / perT, r = i - tt * perT;
+    const int bb = r / kx4, j0 = 4 * (r - bb * kx4);
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int j = j0 + e;
+      v[e] = 0.f;
+      if (j < nx) {
+        const int k = j / C0, c = j - k * C0;
+        v[e] = xs[(k * nb + bb) * run + tt * C0 + c];
+      } else if (j == nx) v[e] = 1.0f;
+    }
+    float* dst = XA0 + (((size_t)(t0 + tt) * N + n) * B + b0) * Kx + 4 * (size_t)r;
+    *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+// state initialisation of every layer in ONE launch per forward (blockIdx.y = layer), 16 bytes per thread:
+//   ZHx_l [B][Np][64] <- 0;  Hx_l [B][Np][64] <- h0_l (user layout (B, N, 64), padding rows zero) or zeros;
+//   H0_l (training forward with h0: the copy the backward reads) <- the same;
+//   Seq_l [B*T][Np][64]: rows n >= N <- 0 (the update kernels write the rows of the real nodes only).
+// Thread idx < state4 takes a float4 of the three state buffers, the threads behind it one of the padding rows.
+struct StateInitArgs {
+  float* zhx[4];
+  float* hx[4];
+  float* h0dst[4];        // or null
+  const float* h0[4];     // or null: zero state
+  float* seq[4];
+};
+__global__ __launch_bounds__(256) void k_state_init(StateInitArgs a, int B, int rowsSeq, int N, int Np) {
+  const int l = blockIdx.y;
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const size_t total = (size_t)T * N * B * Kx;
-  if (idx >= total) return;
-  const int j = idx % Kx;
-  const int b = (idx / Kx) % B;
-  const int n = (idx / ((size_t)Kx * B)) % N;
-  const int t = idx / ((size_t)Kx * B * N);
-  const int row = b * T + t;
-  float v = 0.f;
-  const int nx = (Ks + 1) * C0;
-  if (j < C0) v = x0p[((size_t)row * Np + n) * C0 + j];
-  else if (j < nx) {
-    const int k = j / C0 - 1, c = j % C0;
-    v = MX0[((size_t)k * Np + n) * ld + (size_t)row * C0 + c];
-  } else if (j == nx) v = 1.0f;
-  XA0[idx] = v;
+  const size_t state4 = (size_t)B * Np * 16;
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (idx < state4) {
+    const int c4 = (int)(idx & 15);
+    const int n = (int)((idx >> 4) % Np);
+    const size_t r = (idx >> 4) / Np;
+    float4 v = zero;
+    if (a.h0[l] && n < N) {
+      const float* src = a.h0[l] + (r * N + n) * 64 + 4 * c4;   // a caller's tensor: no alignment beyond its floats
+      v = make_float4(src[0], src[1], src[2], src[3]);
+    }
+    reinterpret_cast<float4*>(a.zhx[l])[idx] = zero;
+    reinterpret_cast<float4*>(a.hx[l])[idx] = v;
+    if (a.h0dst[l]) reinterpret_cast<float4*>(a.h0dst[l])[idx] = v;
+    return;
+  }
+  const int per4 = (Np - N) * 16;
+  const size_t q = idx - state4;
+  if (q >= (size_t)rowsSeq * per4) return;
+  const size_t r = q / per4;
+  const int e = (int)(q - r * per4);
+  *reinterpret_cast<float4*>(a.seq[l] + (r * Np + N) * 64 + 4 * e) = zero;
 }
 
 // =================================================================================================

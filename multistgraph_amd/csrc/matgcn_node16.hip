@@ -952,9 +952,8 @@ __global__ __launch_bounds__(256) void k_stream_to_bf16(const float* __restrict_
 
 // nn.Linear weight (O, I) -> [g][ct][lane][4] of B[kk][o] = W[o][in(kk)]: rows kk < Cpad map to input kk (zero
 // beyond C), rows kk >= Cpad map to input C + (kk - Cpad)
-__global__ __launch_bounds__(256) void k_prep_linear16(const float* __restrict__ W, int I, int O, int C, int Cpad,
-                                                       int nG, float* __restrict__ out) {
-  const int unit = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void prep_linear16(const float* __restrict__ W, int I, int O, int C, int Cpad, int nG,
+                                              float* __restrict__ out, int unit) {
   const int OT = O >> 4;
   if (unit >= nG * OT * 64) return;
   const int lane = unit & 63, ct = (unit >> 6) % OT, g = (unit >> 6) / OT;
@@ -968,6 +967,23 @@ __global__ __launch_bounds__(256) void k_prep_linear16(const float* __restrict__
     v[s] = (in >= 0 && in < I) ? W[(size_t)o * I + in] : 0.f;
   }
   *reinterpret_cast<float4*>(out + (size_t)unit * 4) = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// every dense weight matrix of matgcn_prepare in ONE launch: blockIdx.y picks the matrix - the residual cells' gate and
+// update nn.Linear weights of every layer (16x16x4 fragment order) and, last, the head's convolution weight (32x32x2
+// fragment order, prep_linear in matgcn_kernels.hip).  grid.x covers the largest of them.
+struct DenseMat {
+  const float* W;
+  float* out;
+  int I, O, C, Cpad, rows;   // rows: k-groups of 16 (nG) of a cell matrix, reduction rows of the head's
+  int OT;                    // head only: 32-column tiles; 0 marks a cell matrix
+};
+struct PrepDenseArgs { DenseMat m[2 * 4 + 1]; };
+__global__ __launch_bounds__(256) void k_prep_dense(PrepDenseArgs a) {
+  const DenseMat& q = a.m[blockIdx.y];
+  const int unit = blockIdx.x * 256 + threadIdx.x;
+  if (q.OT == 0) prep_linear16(q.W, q.I, q.O, q.C, q.Cpad, q.rows, q.out, unit);
+  else prep_linear(q.W, q.I, q.O, q.C, q.Cpad, q.rows, q.OT, q.out, unit);
 }
 
 #endif
