@@ -38,6 +38,9 @@
  * matgcn_forward_train_seeded, matgcn_backward_seeded, matgcn_forward_mc - and nothing else changes: no existing symbol,
  * signature or struct changed, both *_bytes() give their numbers, and a caller that hands matgcn_forward_train /
  * matgcn_backward a mask tensor (or NULL) launches the kernels ABI 12 defined, with their arguments and bits.
+ * Still ABI 12: quantiles and scores of a Monte-Carlo-dropout ensemble add three functions - matgcn_mc_quantiles,
+ * matgcn_mc_scores_bytes, matgcn_mc_scores - and two constants; no existing symbol, signature, struct or value changed, and
+ * matgcn_forward_mc launches the kernel it launched, with its arguments and bits.
  */
 #ifndef MATGCN_H
 #define MATGCN_H
@@ -420,6 +423,55 @@ int matgcn_backward_seeded(const matgcn_dims* dims, const matgcn_params* params,
 int matgcn_forward_mc(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
                       const matgcn_series* src, const float* h0, const matgcn_dropout* dropout, int samples, float* mean,
                       float* std, float* samples_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- prediction intervals and probabilistic scores from the Monte-Carlo-dropout samples ----------------------------------
+ * Both entry points read the sample-major tensor matgcn_forward_mc writes to samples_out: samples (S, E), E = B*out*N*od,
+ * S = n_samples in 1 .. MATGCN_MAX_MC_SAMPLES.  A workgroup takes a tile of consecutive elements and all S samples of each
+ * (every sample row is read from HBM once), de-scales on load, p = x*std + mean as an fp32 product and an fp32 sum (two
+ * roundings, never fused), and sorts every element's column x(0) <= .. <= x(S-1) in LDS (bitonic network over S rounded
+ * up to a power of two; the padding never reaches a result).  Tile: 64 elements up to S = 256, 32 up to 512, 16 up to 1024
+ * (at most 64 KB of LDS).  Nothing is allocated, no atomics, work on the caller's stream only, fixed summation order:
+ * results are run-to-run identical and independent of the order the workgroups run in.
+ * Samples are assumed finite.  A non-finite sample (NaN, +-inf) causes no out-of-bounds access and no hang, but the
+ * results of its element - and the sums that element enters - are UNSPECIFIED.  The sign of a zero result is unspecified.
+ *
+ * Quantile of level q (probs: HOST array of n_probs floats, 1 .. MATGCN_MAX_MC_QUANTILES of them, each in [0, 1], ascending;
+ * anything else, NaN included, is MATGCN_ERR_BAD_ARG): the host forms h = (double)q*(S-1), j = floor(h), g = (float)(h-j);
+ * the device Q = lo + g*(hi - lo) with lo = x(j), hi = x(min(j+1, S-1)), three fp32 roundings - numpy's default "linear"
+ * rule, reproduced bit for bit by numpy float32 arithmetic.  Level 0 is the minimum and level 1 the maximum, exactly.
+ * quantiles: (n_probs, E), device. */
+#define MATGCN_MAX_MC_QUANTILES 8
+#define MATGCN_MC_SCORE_SUMS 5            /* + one pinball sum per level */
+int matgcn_mc_quantiles(const float* samples, int n_samples, int64_t elems, const float* probs /*HOST*/, int n_probs,
+                        float mean, float std, float* quantiles /* (n_probs, elems) */, void* stream);
+
+/* Scores of the ensemble against the labels, per horizon, for a whole test set batch by batch.  Labels, mask and
+ * geometry as matgcn_masked_mae: l = y*std + mean (two fp32 roundings); l := 0 where |l| < min_s (min_s < 0: off);
+ * mask = (l != null_val), with a NaN null_val mask = !isnan(l); y (B, y_steps >= out, N, y_feat), channels y_start ..
+ * y_start+od-1, or - label_start != NULL (device, B int32) - the raw series (y_steps, N, y_feat) whose rows
+ * label_start[b] + o are sample b's targets (rows outside the series are clamped and counted: matgcn_series_violations).
+ * Per unmasked element, in fp64 from the fp32 values (Q_k the quantile of level k, first / last = the outer two levels):
+ *   CRPS    = (1/S) sum_i |x(i) - l| - (1/S^2) sum_i (2i - S + 1) x(i)        (= mean|x - l| - mean|x - x'| / 2)
+ *   covered = 1 iff Q_first <= l <= Q_last, compared in fp32;    width = Q_last - Q_first
+ *   Winkler = width + (2/alpha) max(Q_first - l, 0) + (2/alpha) max(l - Q_last, 0),  alpha = 1 - ((double)q_last -
+ *             (double)q_first); for alpha = 0 the width alone
+ *   pinball_k = max(q_k (l - Q_k), (q_k - 1)(l - Q_k))
+ * sums (out_steps, 5 + n_probs) doubles, device: [count, sum CRPS, sum covered, sum width, sum Winkler, sum pinball_0 ..],
+ * overwritten, or added to when accumulate != 0 (several batches = one call over their concatenation).  A tile never
+ * straddles two (b, horizon) rows; stage 1 writes one partial per workgroup into `scratch` (caller-owned device memory of
+ * matgcn_mc_scores_bytes bytes, less is MATGCN_ERR_SMALL_BUFFER; contents before and after are of no interest), stage 2 adds
+ * them in ascending index.  Every argument is checked on the host before anything is launched.
+ * Measured at Baltimore 403 / B = 64 (MI355X, tools/mc_scores_time.py, median of 20 calls, HIP events; DESIGN.md section
+ * 5d): S = 32 (79 MB of samples): matgcn_mc_quantiles (three
+ * levels) 0.122 ms, matgcn_mc_scores 0.235 ms, torch.sort + the same interpolation 0.391 ms, one read of the tensor
+ * (samples.sum(0)) 0.019 ms;  S = 128 (317 MB): 0.828 / 1.044 / 4.760 / 0.058 ms.  Faster than the torch route (3.2x and
+ * 5.7x for the quantiles) and 6 to 14 times the single read: the kernels are bound by the LDS passes of the sorting
+ * network (one barrier per stage), not by HBM. */
+int matgcn_mc_scores_bytes(int batch, int out_steps, int nodes, int out_dim, int n_samples, int n_probs, size_t* bytes);
+int matgcn_mc_scores(const float* samples, int n_samples, const float* y, const int32_t* label_start, int batch,
+                     int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start, float mean, float std,
+                     float null_val, float min_s, const float* probs /*HOST*/, int n_probs, void* scratch,
+                     size_t scratch_bytes, double* sums /* (out_steps, 5 + n_probs) */, int accumulate, void* stream);
 
 /* ---- scheduling option ------------------------------------------------------------------------
  * The encoder runs the recurrent chains of the layers as a wavefront on internal HIP streams (created once, on

@@ -56,6 +56,8 @@ class Dropout(C.Structure):
 
 
 MAX_MC_SAMPLES = 1024
+MAX_MC_QUANTILES = 8
+MC_SCORE_SUMS = 5   # count, CRPS, covered, width, Winkler; one pinball sum per level follows
 
 
 class Params(C.Structure):
@@ -122,6 +124,11 @@ _SIGNATURES = {
                                          C.POINTER(Dropout), _P, C.POINTER(Params), _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
     "matgcn_forward_mc": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), _P, _P, C.POINTER(Series), _P, C.POINTER(Dropout),
                                     C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
+    "matgcn_mc_quantiles": (C.c_int, [_P, C.c_int, C.c_int64, C.POINTER(C.c_float), C.c_int, C.c_float, C.c_float, _P, _P]),
+    "matgcn_mc_scores_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "matgcn_mc_scores": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_int, _P,
+                                   C.c_size_t, _P, C.c_int, _P]),
     "matgcn_debug_gemm": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int64), C.c_float, C.c_float, _P]),
     "matgcn_set_wavefront": (C.c_int, [C.c_int]),
     "matgcn_set_stream_pool": (C.c_int, [C.c_int]),

@@ -17,6 +17,7 @@
 #include "matgcn_kernels.hip"
 #include "matgcn_node16.hip"
 #include "matgcn_bwd_kernels.hip"
+#include "matgcn_mc_scores.hip"
 
 namespace {
 
@@ -1356,6 +1357,110 @@ int matgcn_metric_table(const double* sums, int out_steps, int swap_r2, double* 
   if (!sums || !table) return MATGCN_ERR_NULL;
   if (out_steps < 1 || out_steps > 64) return MATGCN_ERR_BAD_ARG;
   hipLaunchKernelGGL(k_metric_table, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, out_steps, swap_r2, table);
+  return launch_ok();
+}
+
+// ---- quantiles and probabilistic scores of a Monte-Carlo-dropout ensemble (matgcn_mc_scores.hip) -----------------------
+namespace {
+// the tile of S samples: P = S rounded up to a power of two, TE = 2^logTE elements with P * TE <= MC_TILE_FLOATS
+struct McTile { int P, logTE, ldsBytes; };
+McTile mc_tile(int S) {
+  McTile t;
+  t.P = 1;
+  while (t.P < S) t.P <<= 1;
+  t.logTE = 6;
+  while ((t.P << t.logTE) > MC_TILE_FLOATS) --t.logTE;
+  const int bytes = (t.P << t.logTE) * (int)sizeof(float);
+  t.ldsBytes = bytes > MC_REDUCE_BYTES ? bytes : MC_REDUCE_BYTES;
+  return t;
+}
+// levels in [0, 1], ascending (NaN fails every comparison) -> the interpolation indices and weights of each
+int mc_levels(const float* probs, int n_probs, int S, McLevels* lv) {
+  if (n_probs < 1 || n_probs > MATGCN_MAX_MC_QUANTILES) return MATGCN_ERR_BAD_ARG;
+  memset(lv, 0, sizeof(*lv));
+  lv->n = n_probs;
+  for (int k = 0; k < n_probs; ++k) {
+    const float q = probs[k];
+    if (!(q >= 0.f && q <= 1.f) || (k > 0 && !(q >= probs[k - 1]))) return MATGCN_ERR_BAD_ARG;
+    const double h = (double)q * (double)(S - 1);
+    int j = (int)floor(h);
+    if (j > S - 1) j = S - 1;
+    lv->lo[k] = j;
+    lv->hi[k] = j + 1 < S ? j + 1 : S - 1;
+    lv->g[k] = (float)(h - (double)j);
+    lv->q[k] = (double)q;
+  }
+  const double alpha = 1.0 - ((double)probs[n_probs - 1] - (double)probs[0]);
+  lv->winkler = alpha != 0.0 ? 2.0 / alpha : 0.0;
+  return MATGCN_OK;
+}
+// geometry of a score call -> tiles per (b, horizon) row and the number of workgroups
+int mc_score_grid(int batch, int out_steps, int nodes, int out_dim, int n_samples, int* tilesPerRow, long* blocks) {
+  if (batch < 1 || out_steps < 1 || nodes < 1 || out_dim < 1) return MATGCN_ERR_BAD_ARG;
+  if (n_samples < 1 || n_samples > MATGCN_MAX_MC_SAMPLES) return MATGCN_ERR_BAD_ARG;
+  const long rowLen = (long)nodes * out_dim;
+  if (rowLen >= (1L << 31)) return MATGCN_ERR_UNSUPPORTED;
+  const McTile t = mc_tile(n_samples);
+  const long tiles = (rowLen + (1L << t.logTE) - 1) >> t.logTE;
+  if ((long)batch * out_steps > (1L << 31) / tiles) return MATGCN_ERR_UNSUPPORTED;
+  *tilesPerRow = (int)tiles;
+  *blocks = (long)batch * out_steps * tiles;
+  return MATGCN_OK;
+}
+}  // namespace
+
+int matgcn_mc_quantiles(const float* samples, int n_samples, int64_t elems, const float* probs, int n_probs, float mean,
+                        float std, float* quantiles, void* stream) {
+  if (!samples || !probs || !quantiles) return MATGCN_ERR_NULL;
+  if (n_samples < 1 || n_samples > MATGCN_MAX_MC_SAMPLES || elems < 1) return MATGCN_ERR_BAD_ARG;
+  McLevels lv;
+  RETURN_IF(mc_levels(probs, n_probs, n_samples, &lv));
+  const McTile t = mc_tile(n_samples);
+  const int64_t blocks = (elems + (1 << t.logTE) - 1) >> t.logTE;
+  if (blocks >= (1LL << 31)) return MATGCN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(k_mc_quantiles, dim3((unsigned)blocks), dim3(256), (size_t)t.ldsBytes, (hipStream_t)stream, samples,
+                     lv, n_samples, t.P, t.logTE, (long long)elems, mean, std, quantiles);
+  return launch_ok();
+}
+
+int matgcn_mc_scores_bytes(int batch, int out_steps, int nodes, int out_dim, int n_samples, int n_probs, size_t* bytes) {
+  if (!bytes) return MATGCN_ERR_NULL;
+  if (n_probs < 1 || n_probs > MATGCN_MAX_MC_QUANTILES) return MATGCN_ERR_BAD_ARG;
+  int tilesPerRow = 0;
+  long blocks = 0;
+  RETURN_IF(mc_score_grid(batch, out_steps, nodes, out_dim, n_samples, &tilesPerRow, &blocks));
+  *bytes = (size_t)blocks * (MATGCN_MC_SCORE_SUMS + n_probs) * sizeof(double);
+  return MATGCN_OK;
+}
+
+int matgcn_mc_scores(const float* samples, int n_samples, const float* y, const int32_t* label_start, int batch,
+                     int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start, float mean, float std,
+                     float null_val, float min_s, const float* probs, int n_probs, void* scratch, size_t scratch_bytes,
+                     double* sums, int accumulate, void* stream) {
+  if (!samples || !y || !probs || !scratch || !sums) return MATGCN_ERR_NULL;
+  int tilesPerRow = 0;
+  long blocks = 0;
+  RETURN_IF(mc_score_grid(batch, out_steps, nodes, out_dim, n_samples, &tilesPerRow, &blocks));
+  if (y_steps < 1 || (!label_start && y_steps < out_steps) || y_feat < 1 || y_start < 0 || y_start + out_dim > y_feat)
+    return MATGCN_ERR_BAD_ARG;
+  McLevels lv;
+  RETURN_IF(mc_levels(probs, n_probs, n_samples, &lv));
+  const int K = MATGCN_MC_SCORE_SUMS + n_probs;
+  if (scratch_bytes < (size_t)blocks * K * sizeof(double)) return MATGCN_ERR_SMALL_BUFFER;
+  const McTile t = mc_tile(n_samples);
+  McScoreArgs a;
+  a.samples = samples; a.y = y; a.labelStart = label_start;
+  a.S = n_samples; a.P = t.P; a.logTE = t.logTE;
+  a.outSteps = out_steps; a.N = nodes; a.od = out_dim; a.ySteps = y_steps; a.yFeat = y_feat; a.yStart = y_start;
+  a.tilesPerRow = tilesPerRow;
+  a.E = (long long)batch * out_steps * nodes * out_dim;
+  a.mean = mean; a.std = std; a.nullVal = null_val; a.minS = min_s;
+  a.partials = (double*)scratch;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_mc_scores, dim3((unsigned)blocks), dim3(256), (size_t)t.ldsBytes, s, a, lv);
+  CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_mc_accumulate, dim3((unsigned)out_steps), dim3(64), 0, s, a.partials, batch, out_steps, tilesPerRow,
+                     K, accumulate, sums);
   return launch_ok();
 }
 

@@ -7,6 +7,10 @@ horizon on the device (matgcn_metric_sums), ``evaluate`` reads one small table b
 per-horizon table TrafficStateExecutor.evaluate writes after re-transforming with the per-tract mean / std
 (libcity/executor/traffic_state_executor.py:293-322).
 
+``ProbabilisticEvaluator`` is its counterpart for a Monte-Carlo-dropout ensemble (model.predict_mc(keep_samples=True)):
+CRPS, interval coverage and width, the interval (Winkler) score and pinball losses per horizon, accumulated over the
+batches of a test set on the device (matgcn_mc_scores).  The reference has no such evaluator.
+
 HIP path only: CPU tensors raise.
 """
 from __future__ import annotations
@@ -16,7 +20,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib
-from .ops import metric_sums, metric_table
+from .ops import mc_scores, metric_sums, metric_table
 
 ALLOWED_METRICS = list(_lib.METRICS)
 
@@ -86,6 +90,55 @@ class DeviceEvaluator:
         for i in range(1, self.len_timeslots + 1):
             for m in self.metrics:
                 self.result[m + "@" + str(i)] = float(t[i - 1, ALLOWED_METRICS.index(m)])
+        return self.result
+
+
+class ProbabilisticEvaluator:
+    """Scores of the sample ensemble against the labels, per horizon, over every batch collected since ``clear``:
+    ``CRPS@k`` (the ensemble CRPS mean|x - l| - mean|x - x'| / 2), ``PICP@k`` (the share of labels inside
+    [first level, last level] of ``probs``), ``MPIW@k`` (the mean width of that interval), ``WINKLER@k`` (the interval
+    score at alpha = 1 - (last - first)) and ``PINBALL_<q>@k`` per level - means over the unmasked labels (null value 0,
+    |label| < ``min_s`` counted as 0: the convention of calculate_loss).  config keys: ``min_s`` (1e-4)."""
+
+    def __init__(self, config, probs=(0.05, 0.5, 0.95)):
+        self.probs = tuple(float(q) for q in probs)
+        if not 1 <= len(self.probs) <= _lib.MAX_MC_QUANTILES:
+            raise ValueError("probs: 1 .. %d levels, got %d" % (_lib.MAX_MC_QUANTILES, len(self.probs)))
+        if any(not 0.0 <= q <= 1.0 for q in self.probs) or any(a > b for a, b in zip(self.probs, self.probs[1:])):
+            raise ValueError("probs must be ascending levels in [0, 1], got %s" % (self.probs,))
+        self.min_s = float(config.get("min_s", 1e-4))
+        self.columns: List[str] = ["CRPS", "PICP", "MPIW", "WINKLER"] + ["PINBALL_%g" % q for q in self.probs]
+        self.clear()
+
+    def clear(self):
+        self.result: Dict[str, float] = {}
+        self._sums: Optional[torch.Tensor] = None
+        self.len_timeslots = 0
+
+    def collect_samples(self, samples, y, y_start: int = 0, mean=None, std=None, label_start=None):
+        """One batch: ``samples`` (S, B, out, N, od) in scaled units, ``y`` the batch's labels (B, y_steps, N, F) - or,
+        with ``label_start``, the device-resident series (T, N, F) -, both de-scaled in the kernel by x*std + mean
+        (scalars; None = identity)."""
+        if (mean is None) != (std is None):
+            raise ValueError("mean and std come as a pair")
+        self.len_timeslots = int(samples.shape[2])
+        self._sums = mc_scores(samples, y, self.probs, y_start, 0.0 if mean is None else float(mean),
+                               1.0 if std is None else float(std), null_val=0.0, min_s=self.min_s,
+                               label_start=label_start, sums=self._sums)
+
+    def table(self) -> torch.Tensor:
+        """(out, 4 + levels) float64 CPU tensor, column order ``columns``; a horizon without an unmasked label is NaN"""
+        if self._sums is None:
+            raise RuntimeError("nothing collected")
+        s = self._sums.cpu()
+        count = s[:, :1]
+        return torch.where(count > 0, s[:, 1:] / count, torch.full_like(s[:, 1:], float("nan")))
+
+    def evaluate(self) -> Dict[str, float]:
+        t = self.table()
+        for i in range(1, self.len_timeslots + 1):
+            for c, name in enumerate(self.columns):
+                self.result[name + "@" + str(i)] = float(t[i - 1, c])
         return self.result
 
 

@@ -24,7 +24,8 @@ import torch.nn as nn
 
 from . import graph_prep
 from . import hidden_pad
-from .ops import HotPath, PathSpec, diagonal_mask, masked_mae_device, masked_mae_loss, spec_from_config
+from .ops import (HotPath, PathSpec, diagonal_mask, masked_mae_device, masked_mae_loss, mc_quantiles, mc_scores,
+                  spec_from_config)
 
 try:  # inside a LibCity checkout: subclass the real plugin base so isinstance checks hold
     from libcity.model.abstract_traffic_state_model import AbstractTrafficStateModel  # type: ignore
@@ -437,6 +438,30 @@ class MultiATGCN(AbstractTrafficStateModel):
                 offset = 0
             return hp.forward_mc(source, h0, seed=seed, offset=offset, p=DROPOUT_P, samples=samples,
                                  keep_samples=keep_samples)
+
+    def predict_interval(self, batch, samples: int = 32, probs=(0.05, 0.5, 0.95), seed: Optional[int] = None):
+        """Monte-Carlo-dropout forecast with its empirical band: (mean, std, quantiles) in the units of ``predict`` -
+        mean and std what ``predict_mc`` gives for the same seed, quantiles (len(probs), B, out, N, od) the levels
+        ``probs`` (up to 8, ascending, in [0, 1]) of the ``samples`` forecasts per output element, numpy's "linear" rule
+        (matgcn_mc_quantiles).  Window and resident-series batches; seed as in ``predict_mc``."""
+        mean, std, kept = self.predict_mc(batch, samples=samples, seed=seed, keep_samples=True)
+        return mean, std, mc_quantiles(kept, probs)
+
+    def score_mc(self, batch, samples: int = 32, probs=(0.05, 0.5, 0.95), seed: Optional[int] = None, sums=None):
+        """The (out, 5 + len(probs)) float64 per-horizon sums [count, CRPS, covered, width, Winkler, pinball per level] of
+        a Monte-Carlo-dropout ensemble against the batch's labels, on de-scaled values with the mask of calculate_loss
+        (null value 0), without leaving the GPU (matgcn_mc_scores).  ``batch`` is a window batch (``X``, ``y``) or a
+        resident-series batch; ``sums`` from an earlier batch is added to.  evaluator.ProbabilisticEvaluator turns the
+        sums into CRPS / PICP / MPIW / Winkler / pinball tables."""
+        affine = self._affine_scaler()
+        if affine is None:
+            raise NotImplementedError("score_mc needs an affine scaler (StandardScaler / NoneScaler)")
+        kept = self.predict_mc(batch, samples=samples, seed=seed, keep_samples=True)[2]
+        if _is_series_batch(batch):
+            src = self._batch_source(batch)
+            return mc_scores(kept, src[0], probs, self.start_dim, affine[0], affine[1], null_val=0.0,
+                             label_start=src[1], sums=sums)
+        return mc_scores(kept, batch["y"], probs, self.start_dim, affine[0], affine[1], null_val=0.0, sums=sums)
 
     # ---- the same surface fed from the device-resident raw series (no windows, no labels materialised) ----------
     def _batch_source(self, batch):

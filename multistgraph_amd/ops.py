@@ -294,6 +294,75 @@ def metric_table(sums: torch.Tensor, swap_r2: bool = False) -> torch.Tensor:
     return table
 
 
+def _mc_probs(probs):
+    """the quantile levels as the host float array the C ABI takes"""
+    vals = [float(v) for v in probs]
+    return (C.c_float * len(vals))(*vals), len(vals)
+
+
+def _mc_samples(samples: torch.Tensor) -> torch.Tensor:
+    samples = _check_tensor(samples, "samples")
+    if samples.dim() < 2:
+        raise _lib.MatgcnError("samples has shape %s, expected (S, ...): the sample axis first" % (tuple(samples.shape),))
+    return samples
+
+
+def mc_quantiles(samples: torch.Tensor, probs: Sequence[float], mean: float = 0.0, std: float = 1.0) -> torch.Tensor:
+    """Empirical quantiles over the sample axis of the Monte-Carlo-dropout forecasts (matgcn_mc_quantiles):
+    ``samples`` (S, ...) as HotPath.forward_mc(keep_samples=True) returns them, de-scaled as x*std + mean on load;
+    ``probs`` up to 8 ascending levels in [0, 1].  Returns (len(probs), *samples.shape[1:]) - numpy's "linear" rule in
+    float32, no sorted copy of the samples anywhere."""
+    lib = _lib.load()
+    samples = _mc_samples(samples)
+    levels, nq = _mc_probs(probs)
+    s, elems = int(samples.shape[0]), samples[0].numel()
+    out = torch.empty((nq,) + tuple(samples.shape[1:]), dtype=torch.float32, device=samples.device)
+    stream = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
+    _lib.check(lib.matgcn_mc_quantiles(C.c_void_p(samples.data_ptr()), s, elems, levels, nq, float(mean), float(std),
+                                       C.c_void_p(out.data_ptr()), stream), "matgcn_mc_quantiles")
+    return out
+
+
+_mc_scratch: Dict[tuple, torch.Tensor] = {}   # (device, batch, out, nodes, od, S, levels) -> the stage-1 partials
+
+
+def mc_scores(samples: torch.Tensor, y: torch.Tensor, probs: Sequence[float], y_start: int = 0, mean: float = 0.0,
+              std: float = 1.0, null_val: float = 0.0, min_s: float = 1e-4, label_start: Optional[torch.Tensor] = None,
+              sums: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(out, 5 + len(probs)) float64 device tensor of per-horizon sums [count, CRPS, covered, width, Winkler, pinball per
+    level] of the ensemble ``samples`` (S, B, out, N, od) against the labels (matgcn_mc_scores, include/matgcn.h): labels,
+    mask and geometry as masked_mae_device (``y`` windows, or with ``label_start`` the resident series), the interval is
+    [first level, last level].  ``sums``: running sums of earlier batches to add to."""
+    lib = _lib.load()
+    samples = _mc_samples(samples)
+    if samples.dim() != 5:
+        raise _lib.MatgcnError("samples has shape %s, expected (S, B, out, N, od)" % (tuple(samples.shape),))
+    s, b, out, n, od = (int(v) for v in samples.shape)
+    y, label_start, y_steps, y_feat = _label_geometry(samples[0], y, label_start)
+    levels, nq = _mc_probs(probs)
+    need = C.c_size_t(0)
+    _lib.check(lib.matgcn_mc_scores_bytes(b, out, n, od, s, nq, C.byref(need)), "matgcn_mc_scores_bytes")
+    key = (samples.device, b, out, n, od, s, nq)
+    scratch = _mc_scratch.get(key)
+    if scratch is None:
+        if len(_mc_scratch) >= 16:
+            _mc_scratch.clear()
+        scratch = _mc_scratch[key] = torch.empty(max(1, need.value // 8), dtype=torch.float64, device=samples.device)
+    cols = _lib.MC_SCORE_SUMS + nq
+    accumulate = sums is not None
+    if sums is None:
+        sums = torch.empty(out, cols, dtype=torch.float64, device=samples.device)
+    elif tuple(sums.shape) != (out, cols) or sums.dtype != torch.float64 or not sums.is_cuda or not sums.is_contiguous():
+        raise _lib.MatgcnError("sums must be a contiguous CUDA float64 tensor of shape (%d, %d)" % (out, cols))
+    stream = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
+    _lib.check(lib.matgcn_mc_scores(C.c_void_p(samples.data_ptr()), s, C.c_void_p(y.data_ptr()),
+                                    C.c_void_p(_ptr(label_start)), b, out, n, od, y_steps, y_feat, int(y_start),
+                                    float(mean), float(std), float(null_val), float(min_s), levels, nq,
+                                    C.c_void_p(scratch.data_ptr()), C.c_size_t(scratch.numel() * 8),
+                                    C.c_void_p(sums.data_ptr()), int(accumulate), stream), "matgcn_mc_scores")
+    return sums
+
+
 class HotPath:
     """One (spec, batch) binding.  Not thread-safe; uses torch's current stream at call time."""
 
