@@ -41,6 +41,9 @@
  * Still ABI 12: quantiles and scores of a Monte-Carlo-dropout ensemble add three functions - matgcn_mc_quantiles,
  * matgcn_mc_scores_bytes, matgcn_mc_scores - and two constants; no existing symbol, signature, struct or value changed, and
  * matgcn_forward_mc launches the kernel it launched, with its arguments and bits.
+ * Still ABI 12: new names only - the device-side optimizer step adds the structs matgcn_opt_tensor and matgcn_adam and the
+ * functions matgcn_grad_norm_bytes, matgcn_grad_norm, matgcn_adam_step; no existing symbol, signature, struct or value
+ * changed, and no existing entry point launches anything else than it did.
  */
 #ifndef MATGCN_H
 #define MATGCN_H
@@ -472,6 +475,61 @@ int matgcn_mc_scores(const float* samples, int n_samples, const float* y, const 
                      int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start, float mean, float std,
                      float null_val, float min_s, const float* probs /*HOST*/, int n_probs, void* scratch,
                      size_t scratch_bytes, double* sums /* (out_steps, 5 + n_probs) */, int accumulate, void* stream);
+
+/* ---- the optimizer step: global gradient norm, clip and Adam over a table of tensors -------------------------------------
+ * What clip_grad_norm_(params, max_norm) followed by torch.optim.Adam.step() does (no amsgrad, no maximize), as three
+ * launches over every tensor at once.  The tensors are described by a HOST array of matgcn_opt_tensor, read at call time;
+ * every pointer in it is DEVICE fp32, contiguous, at any 4-byte alignment (float4 accesses where all four pointers of a
+ * tensor are 16-byte aligned, scalar ones otherwise - the same bits either way).  numel == 0 is allowed and skipped (its
+ * pointers are not looked at); matgcn_grad_norm* read `grad` and `numel` only.
+ * Nothing is allocated, work runs on the caller's stream only, no atomics, no host synchronisation, and every argument is
+ * checked on the host before anything is launched.  `grad` is NEVER written: unlike clip_grad_norm_, which scales the
+ * .grad tensors in place, the clip coefficient is applied as the gradients are read, and they keep their unclipped values.
+ * Gradients are assumed finite.  A non-finite one causes no out-of-bounds access and no hang; the results are UNSPECIFIED.
+ *
+ * Norm.  The index space is cut into chunks of 4096 elements that never straddle two tensors (each tensor is rounded up to
+ * whole chunks).  Launch 1: one workgroup per chunk squares and sums its elements in fp64 in a fixed in-workgroup order
+ * and writes one double per chunk into `scratch` (caller-owned device memory of matgcn_grad_norm_bytes = 8 bytes per chunk,
+ * less is MATGCN_ERR_SMALL_BUFFER; contents before and after are of no interest).  Launch 2: one workgroup adds the
+ * partials in ascending index in fp64 and stores total_norm = (float)sqrt(sum).  The squares are exact in fp64 and the sum
+ * carries 29 bits more than the result: the norm is the correctly rounded fp32 value up to one ulp, run-to-run identical
+ * and independent of the order the workgroups run in (and of the alignment of the tensors).
+ *
+ * Update.  Launch 3, one per at most 64 tensors: the table travels by value in the kernel arguments, so no device copy of
+ * it exists and nothing is uploaded per step; more tensors are more launches of the same kernel (of launch 1 likewise).
+ * Per element, one rounding per operation, never fused, `/` and sqrt correctly rounded - the order of torch's
+ * _single_tensor_adam:
+ *   coef = max_norm > 0 ? min(1, max_norm / (total_norm + 1e-6)) : 1        (a NaN norm gives a NaN coef, as torch's clamp)
+ *   g = grad * coef;   if (weight_decay != 0) g = g + weight_decay * p       (torch Adam's L2 form)
+ *   m = (float)(m + (1 - beta1) * (g - m))
+ *   v = (float)(beta2 * v + ((1 - beta2) * g) * g)
+ *   p = p - step_size * (m / (sqrt(v) / sqrt(bc2) + eps)),   step_size = lr / bc1, bc1 = 1 - beta1^step, bc2 = 1 - beta2^step
+ * coef, g and the two moment lines are evaluated in fp64 from the fp32 values, with 1 - beta1, 1 - beta2, beta2 and
+ * weight_decay as doubles, and each moment is rounded to fp32 once: coef is common to all elements and g enters v squared,
+ * so an fp32 coef would put its one rounding, doubled, into every v at once - measured against torch's own float64 run,
+ * the all-fp32 form of these lines left the margin the tests give (twice the gap of torch's float32 run) in 6 % of random
+ * clipped one-step cases, this form in none.  The last line runs in fp32 on the rounded moments, exactly as torch's does;
+ * step_size and sqrt(bc2) are formed on the host in double and rounded once.  Each float
+ * of matgcn_adam is read as the shortest decimal that rounds to it (0.999f as 0.999, what a caller wrote and what Python
+ * holds): 1 - beta2 is then torch's 1e-3, not the 0.99998713e-3 the float's own value would give.
+ * matgcn_adam is a host struct, read at call time.  MATGCN_ERR_BAD_ARG: n < 1, a numel < 0, lr / eps / weight_decay
+ * negative or NaN, beta1 or beta2 outside [0, 1), step < 1, max_norm NaN.  MATGCN_ERR_NULL: t, hp, a pointer of a tensor
+ * with numel > 0, total_norm of matgcn_grad_norm, or total_norm of matgcn_adam_step while max_norm > 0 (with max_norm <= 0
+ * it is not read and may be NULL).  Tensors whose step counts differ go into separate calls. */
+typedef struct matgcn_opt_tensor {   /* HOST array element; all pointers DEVICE fp32, contiguous */
+  float* param; const float* grad; float* exp_avg; float* exp_avg_sq; int64_t numel;
+} matgcn_opt_tensor;
+typedef struct matgcn_adam {         /* host struct, read at call time */
+  float lr, beta1, beta2, eps, weight_decay;  /* weight_decay: torch Adam's L2 form (g += wd*p), 0 = off */
+  float max_norm;                              /* > 0: clip to this global norm; <= 0: no clipping */
+  int64_t step;                                /* 1-based step count after this update */
+} matgcn_adam;
+
+int matgcn_grad_norm_bytes(const matgcn_opt_tensor* t, int n, size_t* bytes);
+int matgcn_grad_norm(const matgcn_opt_tensor* t, int n, void* scratch, size_t scratch_bytes,
+                     float* total_norm /* device, 1 float */, void* stream);
+int matgcn_adam_step(const matgcn_opt_tensor* t, int n, const matgcn_adam* hp,
+                     const float* total_norm /* device; required iff max_norm > 0 */, void* stream);
 
 /* ---- scheduling option ------------------------------------------------------------------------
  * The encoder runs the recurrent chains of the layers as a wavefront on internal HIP streams (created once, on

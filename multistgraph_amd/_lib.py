@@ -60,6 +60,22 @@ MAX_MC_QUANTILES = 8
 MC_SCORE_SUMS = 5   # count, CRPS, covered, width, Winkler; one pinball sum per level follows
 
 
+class OptTensor(C.Structure):
+    """matgcn_opt_tensor: one tensor of an optimizer step (device fp32 pointers)"""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("numel", C.c_int64)]
+
+
+class Adam(C.Structure):
+    """matgcn_adam: the hyperparameters of one matgcn_adam_step call"""
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("weight_decay", C.c_float), ("max_norm", C.c_float), ("step", C.c_int64)]
+
+
+OPT_CHUNK = 4096        # elements per workgroup of the optimizer kernels: matgcn_grad_norm_bytes is 8 bytes per chunk
+OPT_MAX_TENSORS = 64    # tensors per launch (the table travels in the kernel arguments)
+
+
 class Params(C.Structure):
     _fields_ = [
         ("node_emb", C.c_void_p), ("node_vec1", C.c_void_p), ("node_vec2", C.c_void_p),
@@ -129,6 +145,9 @@ _SIGNATURES = {
     "matgcn_mc_scores": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_int, _P,
                                    C.c_size_t, _P, C.c_int, _P]),
+    "matgcn_grad_norm_bytes": (C.c_int, [C.POINTER(OptTensor), C.c_int, C.POINTER(C.c_size_t)]),
+    "matgcn_grad_norm": (C.c_int, [C.POINTER(OptTensor), C.c_int, _P, C.c_size_t, _P, _P]),
+    "matgcn_adam_step": (C.c_int, [C.POINTER(OptTensor), C.c_int, C.POINTER(Adam), _P, _P]),
     "matgcn_debug_gemm": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int64), C.c_float, C.c_float, _P]),
     "matgcn_set_wavefront": (C.c_int, [C.c_int]),
     "matgcn_set_stream_pool": (C.c_int, [C.c_int]),

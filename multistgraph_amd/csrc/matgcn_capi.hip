@@ -18,6 +18,7 @@
 #include "matgcn_node16.hip"
 #include "matgcn_bwd_kernels.hip"
 #include "matgcn_mc_scores.hip"
+#include "matgcn_optim.hip"
 
 namespace {
 
@@ -1462,6 +1463,115 @@ int matgcn_mc_scores(const float* samples, int n_samples, const float* y, const 
   hipLaunchKernelGGL(k_mc_accumulate, dim3((unsigned)out_steps), dim3(64), 0, s, a.partials, batch, out_steps, tilesPerRow,
                      K, accumulate, sums);
   return launch_ok();
+}
+
+// ---- global gradient norm, clip and Adam over a table of tensors (matgcn_optim.hip) --------------------------------------
+namespace {
+// A float hyperparameter read as the decimal its caller wrote: the shortest one that rounds to the same float (0.999f ->
+// 0.999).  Any double inside the float's rounding interval is a legitimate reading of it; this one makes 1 - beta2 the
+// 1e-3 torch forms from the Python double, where the float's own value would give 0.99998713e-3 - 1.3e-5 off, a hundred
+// fp32 roundings, in every exp_avg_sq.  (The printf family and strtod follow LC_NUMERIC together, so the pair is
+// consistent under any locale.)
+double opt_decimal(float f) {
+  if (!(f == f) || f - f != 0.f) return (double)f;
+  char buf[40];
+  for (int prec = 1; prec <= 9; ++prec) {
+    snprintf(buf, sizeof buf, "%.*g", prec, (double)f);
+    const double d = strtod(buf, nullptr);
+    if ((float)d == f) return d;
+  }
+  return (double)f;
+}
+// checks every tensor; chunks = sum over the tensors of ceil(numel / OPT_CHUNK)
+int opt_check_table(const matgcn_opt_tensor* t, int n, bool norm_only, int64_t* chunks) {
+  if (!t) return MATGCN_ERR_NULL;
+  if (n < 1) return MATGCN_ERR_BAD_ARG;
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (t[i].numel < 0) return MATGCN_ERR_BAD_ARG;
+    if (t[i].numel == 0) continue;
+    if (!t[i].grad) return MATGCN_ERR_NULL;
+    if (!norm_only && (!t[i].param || !t[i].exp_avg || !t[i].exp_avg_sq)) return MATGCN_ERR_NULL;
+    total += (t[i].numel + OPT_CHUNK - 1) / OPT_CHUNK;
+    if (total >= (1LL << 31)) return MATGCN_ERR_UNSUPPORTED;
+  }
+  *chunks = total;
+  return MATGCN_OK;
+}
+// the launch table of the tensors first .. first + count - 1; returns its chunks
+int opt_fill_table(const matgcn_opt_tensor* t, int first, int count, OptTable* T) {
+  memset(T, 0, sizeof(*T));
+  T->n = count;
+  int chunks = 0;
+  for (int i = 0; i < count; ++i) {
+    const matgcn_opt_tensor& s = t[first + i];
+    T->param[i] = s.param; T->grad[i] = s.grad; T->expAvg[i] = s.exp_avg; T->expAvgSq[i] = s.exp_avg_sq;
+    T->numel[i] = s.numel;
+    chunks += (int)((s.numel + OPT_CHUNK - 1) / OPT_CHUNK);
+    T->chunkEnd[i] = chunks;
+  }
+  return chunks;
+}
+}  // namespace
+
+int matgcn_grad_norm_bytes(const matgcn_opt_tensor* t, int n, size_t* bytes) {
+  if (!bytes) return MATGCN_ERR_NULL;
+  int64_t chunks = 0;
+  RETURN_IF(opt_check_table(t, n, true, &chunks));
+  *bytes = (size_t)chunks * sizeof(double);
+  return MATGCN_OK;
+}
+
+int matgcn_grad_norm(const matgcn_opt_tensor* t, int n, void* scratch, size_t scratch_bytes, float* total_norm,
+                     void* stream) {
+  if (!total_norm) return MATGCN_ERR_NULL;
+  int64_t chunks = 0;
+  RETURN_IF(opt_check_table(t, n, true, &chunks));
+  if (chunks > 0 && !scratch) return MATGCN_ERR_NULL;
+  if (scratch_bytes < (size_t)chunks * sizeof(double)) return MATGCN_ERR_SMALL_BUFFER;
+  hipStream_t s = (hipStream_t)stream;
+  int base = 0;
+  for (int first = 0; first < n; first += OPT_MAX_TENSORS) {
+    OptTable T;
+    const int c = opt_fill_table(t, first, n - first < OPT_MAX_TENSORS ? n - first : OPT_MAX_TENSORS, &T);
+    if (c == 0) continue;
+    hipLaunchKernelGGL(k_opt_sumsq, dim3((unsigned)c), dim3(OPT_THREADS), 0, s, T, base, (double*)scratch);
+    CHECK_LAUNCH();
+    base += c;
+  }
+  hipLaunchKernelGGL(k_opt_norm_finish, dim3(1), dim3(OPT_THREADS), 0, s, (const double*)scratch, (int)chunks, total_norm);
+  return launch_ok();
+}
+
+int matgcn_adam_step(const matgcn_opt_tensor* t, int n, const matgcn_adam* hp, const float* total_norm, void* stream) {
+  if (!hp) return MATGCN_ERR_NULL;
+  int64_t chunks = 0;
+  RETURN_IF(opt_check_table(t, n, false, &chunks));
+  if (!(hp->lr >= 0.f) || !(hp->eps >= 0.f) || !(hp->weight_decay >= 0.f)) return MATGCN_ERR_BAD_ARG;   // NaN fails too
+  if (!(hp->beta1 >= 0.f && hp->beta1 < 1.f) || !(hp->beta2 >= 0.f && hp->beta2 < 1.f)) return MATGCN_ERR_BAD_ARG;
+  if (hp->step < 1 || hp->max_norm != hp->max_norm) return MATGCN_ERR_BAD_ARG;
+  if (hp->max_norm > 0.f && !total_norm) return MATGCN_ERR_NULL;
+  // the scalars of torch's _single_tensor_adam, formed in double as Python forms them; those of the fp32 part rounded once
+  const double b1 = opt_decimal(hp->beta1), b2 = opt_decimal(hp->beta2), step = (double)hp->step;
+  const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
+  OptScalars h;
+  h.w1 = 1.0 - b1;
+  h.w2 = 1.0 - b2;
+  h.beta2 = b2;
+  h.weightDecay = opt_decimal(hp->weight_decay);
+  h.stepSize = (float)(opt_decimal(hp->lr) / bc1);
+  h.bc2Sqrt = (float)sqrt(bc2);
+  h.eps = hp->eps;
+  h.maxNorm = hp->max_norm;
+  hipStream_t s = (hipStream_t)stream;
+  for (int first = 0; first < n; first += OPT_MAX_TENSORS) {
+    OptTable T;
+    const int c = opt_fill_table(t, first, n - first < OPT_MAX_TENSORS ? n - first : OPT_MAX_TENSORS, &T);
+    if (c == 0) continue;
+    hipLaunchKernelGGL(k_opt_adam, dim3((unsigned)c), dim3(OPT_THREADS), 0, s, T, h, total_norm);
+    CHECK_LAUNCH();
+  }
+  return MATGCN_OK;
 }
 
 int matgcn_set_lazy_prepare(int enabled) {

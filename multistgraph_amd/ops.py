@@ -363,6 +363,103 @@ def mc_scores(samples: torch.Tensor, y: torch.Tensor, probs: Sequence[float], y_
     return sums
 
 
+def _opt_tensor(t, name: str) -> torch.Tensor:
+    """an optimizer tensor as the C ABI wants it - the caller's own memory, so nothing is copied or converted here"""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s must be a tensor, got %s" % (name, type(t).__name__))
+    if not t.is_cuda:
+        raise ValueError("%s must live on the GPU: the optimizer step is HIP-only (no CPU fallback)" % name)
+    if t.dtype != torch.float32:
+        raise ValueError("%s must be float32, got %s" % (name, t.dtype))
+    if t.layout != torch.strided or not t.is_contiguous():
+        raise ValueError("%s must be contiguous: the kernels update it in place, a copy would be lost" % name)
+    return t
+
+
+_opt_tables: Dict[tuple, tuple] = {}    # the pointers of a tensor set -> its matgcn_opt_tensor array (a loop re-uses one)
+_norm_scratch: Dict[tuple, torch.Tensor] = {}   # (device, bytes) -> the per-chunk partials of matgcn_grad_norm
+
+
+def _opt_table(grads, params=None, exp_avgs=None, exp_avg_sqs=None):
+    """(matgcn_opt_tensor array, n, device) of a checked tensor set; grads alone for the norm"""
+    cols = [grads] if params is None else [params, grads, exp_avgs, exp_avg_sqs]
+    n = len(grads)
+    if n < 1 or any(len(c) != n for c in cols):
+        raise ValueError("the optimizer step needs at least one tensor and lists of one length, got %s"
+                         % [len(c) for c in cols])
+    try:   # everything the checks below look at, so that a hit may skip them
+        key = tuple((t.data_ptr(), t.numel(), t.dtype, t.is_contiguous()) for c in cols for t in c)
+    except (AttributeError, RuntimeError):   # not a tensor, or one without storage (sparse): named by the checks
+        key = None
+    hit = _opt_tables.get(key)
+    if hit is not None:
+        return hit
+    names = ("grads",) if params is None else ("params", "grads", "exp_avgs", "exp_avg_sqs")
+    dev = grads[0].device if isinstance(grads[0], torch.Tensor) else None
+    for nm, c in zip(names, cols):
+        for i, t in enumerate(c):
+            _opt_tensor(t, "%s[%d]" % (nm, i))
+            if t.device != dev:
+                raise ValueError("%s[%d] is on %s, grads[0] on %s" % (nm, i, t.device, dev))
+            if t.numel() != grads[i].numel():
+                raise ValueError("%s[%d] has %d elements, grads[%d] %d" % (nm, i, t.numel(), i, grads[i].numel()))
+    arr = (_lib.OptTensor * n)()
+    for i in range(n):
+        if params is not None:
+            arr[i].param, arr[i].exp_avg, arr[i].exp_avg_sq = (params[i].data_ptr(), exp_avgs[i].data_ptr(),
+                                                                exp_avg_sqs[i].data_ptr())
+        arr[i].grad, arr[i].numel = grads[i].data_ptr(), grads[i].numel()
+    if len(_opt_tables) >= 64:
+        _opt_tables.clear()
+    hit = (arr, n, dev)
+    if key is not None:
+        _opt_tables[key] = hit
+    return hit
+
+
+def grad_norm(tensors: Sequence[torch.Tensor]) -> torch.Tensor:
+    """The 2-norm over all elements of ``tensors`` as a 0-dim float32 device tensor (matgcn_grad_norm): what
+    clip_grad_norm_ returns, summed in fp64 in a fixed order - two launches, no host synchronisation."""
+    lib = _lib.load()
+    arr, n, dev = _opt_table(list(tensors))
+    need = C.c_size_t(0)
+    _lib.check(lib.matgcn_grad_norm_bytes(arr, n, C.byref(need)), "matgcn_grad_norm_bytes")
+    scratch = _norm_scratch.get((dev, need.value))
+    if scratch is None:
+        if len(_norm_scratch) >= 16:
+            _norm_scratch.clear()
+        scratch = _norm_scratch[(dev, need.value)] = torch.empty(max(1, need.value // 8), dtype=torch.float64, device=dev)
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(lib.matgcn_grad_norm(arr, n, C.c_void_p(scratch.data_ptr()), C.c_size_t(need.value),
+                                    C.c_void_p(out.data_ptr()), stream), "matgcn_grad_norm")
+    return out
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, *, lr, betas, eps, weight_decay, step, max_norm=None,
+              total_norm: Optional[torch.Tensor] = None) -> None:
+    """One Adam update of ``params`` in place (matgcn_adam_step; torch's _single_tensor_adam order in fp32), ``step`` the
+    1-based count after this update, common to all tensors.  With ``max_norm`` the gradients are scaled, as they are read,
+    by min(1, max_norm / (total_norm + 1e-6)) - ``total_norm`` is grad_norm() over every gradient of the model, not only
+    over the ones of this call; the ``grads`` themselves are never written."""
+    lib = _lib.load()
+    arr, n, dev = _opt_table(list(grads), list(params), list(exp_avgs), list(exp_avg_sqs))
+    clip = max_norm is not None and float(max_norm) > 0
+    if max_norm is not None and not clip and not float(max_norm) <= 0:
+        raise ValueError("max_norm = %r" % (max_norm,))
+    if clip:
+        if total_norm is None:
+            raise ValueError("max_norm without total_norm: pass grad_norm() over every gradient of the model")
+        _opt_tensor(total_norm, "total_norm")
+        if total_norm.numel() != 1 or total_norm.device != dev:
+            raise ValueError("total_norm must be one float on %s" % (dev,))
+    hp = _lib.Adam(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                   float(max_norm) if clip else 0.0, int(step))
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(lib.matgcn_adam_step(arr, n, C.byref(hp), C.c_void_p(total_norm.data_ptr() if clip else None), stream),
+               "matgcn_adam_step")
+
+
 class HotPath:
     """One (spec, batch) binding.  Not thread-safe; uses torch's current stream at call time."""
 

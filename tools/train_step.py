@@ -1,15 +1,18 @@
 """Training steps of the bench workload (default Baltimore 403, B=64): forward_train + backward through the plugin
 surface (calculate_loss().backward()), timed with HIP events.
-usage: train_step.py [--deterministic] [--bf16x3] [--device-dropout] [workload] [steps] [serial|wave] [batch] [fp32|bf16_mix|bf16]
+usage: train_step.py [--deterministic] [--bf16x3] [--device-dropout] [--clip] [--fused-optimizer] [workload] [steps] [serial|wave] [batch] [fp32|bf16_mix|bf16]
 (--deterministic: the model's hip_deterministic = True - the backward's sums in a fixed order, see matgcn_set_deterministic;
 the summary line then also gives the bytes the train buffer grew by)
 (--bf16x3: the model's hip_precision = "bf16x3_train" - the step's graph mixes, both directions, from three bf16 pieces,
 see matgcn_set_train_bf16x3; a hip_precision argument wins over it)
 (--device-dropout: the model's hip_dropout = "device" - the dropout in front of the head drawn inside the kernels that apply
 it, no mask tensor and no F.dropout; see matgcn_forward_train_seeded)
+(--clip: the recipe's clip_grad_norm_(parameters, 5) in front of the optimizer step;  --fused-optimizer: the step is
+multistgraph_amd.optim.ClipAdam - with --clip its own global-norm clip, max_grad_norm = 5 - in place of torch.optim.Adam;
+every step line and the summary also give the host's enqueue time of the whole step, perf_counter without a synchronisation)
 (serial: matgcn_set_wavefront(0) - every kernel alone on one stream, so a profiler's durations are the kernels' own;
 the last argument is the model's hip_precision; the last line gives the medians over the steps after the first three)"""
-import os, sys
+import os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -24,6 +27,12 @@ if bf16x3:
 device_dropout = "--device-dropout" in sys.argv
 if device_dropout:
     sys.argv.remove("--device-dropout")
+clip = "--clip" in sys.argv
+if clip:
+    sys.argv.remove("--clip")
+fused_optimizer = "--fused-optimizer" in sys.argv
+if fused_optimizer:
+    sys.argv.remove("--fused-optimizer")
 name = sys.argv[1] if len(sys.argv) > 1 else "bm403"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 w = dict(bench.WORKLOADS[name])
@@ -44,31 +53,43 @@ if len(sys.argv) > 3 and sys.argv[3] == "serial":
     _lib.load().matgcn_set_wavefront(0)
 x_np, y_np = syn.make_batch_arrays(w["batch"], w["nodes"], w["out"], 0, feat=2)
 batch = {"X": torch.from_numpy(x_np).to(dev), "y": torch.from_numpy(y_np).to(dev)}
-opt = torch.optim.Adam(model.parameters(), lr=1e-3)
+if fused_optimizer:
+    from multistgraph_amd.optim import ClipAdam
+    opt = ClipAdam(model.parameters(), lr=1e-3, max_grad_norm=5 if clip else None)
+else:
+    opt = torch.optim.Adam(model.parameters(), lr=1e-3)
 ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
 times = []
 for i in range(steps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
     opt.zero_grad()
     ev[0].record()
     loss = model.calculate_loss(batch)
     ev[1].record()
     loss.backward()
     ev[2].record()
+    if clip and not fused_optimizer:
+        torch.nn.utils.clip_grad_norm_(model.parameters(), 5)
     opt.step()
     ev[3].record()
+    host_ms = (time.perf_counter() - t0) * 1e3
     torch.cuda.synchronize()
-    times.append((ev[0].elapsed_time(ev[3]), ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])))
-    print("step %d loss %.5f  forward %.2f ms  backward %.2f ms  adam %.2f ms" % (
-        i, float(loss), ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2]), ev[2].elapsed_time(ev[3])), flush=True)
+    times.append((ev[0].elapsed_time(ev[3]), ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2]),
+                  ev[2].elapsed_time(ev[3]), host_ms))
+    print("step %d loss %.5f  forward %.2f ms  backward %.2f ms  adam %.2f ms  host enqueue %.2f ms" % (
+        i, float(loss), ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2]), ev[2].elapsed_time(ev[3]), host_ms), flush=True)
 print("train buffer %.2f GB  workspace %.2f GB  peak torch memory %.2f GB" % (
     next(iter(model._paths.values()))._train.numel() * 4 / 2**30,
     next(iter(model._paths.values())).workspace.numel() * 4 / 2**30, torch.cuda.max_memory_allocated() / 2**30))
 if len(times) > 3:
     import statistics
-    med = [statistics.median(t[k] for t in times[3:]) for k in range(3)]
-    print("median of %d steps (%s, B = %d, %s%s%s): step %.3f ms  forward %.3f ms  backward %.3f ms" % (
-        len(times) - 3, name, w["batch"], model.hip_precision, ", deterministic" if deterministic else "",
-        ", device dropout" if device_dropout else "", med[0], med[1], med[2]))
+    med = [statistics.median(t[k] for t in times[3:]) for k in range(5)]
+    print("median of %d steps (%s, B = %d, %s%s%s%s%s): step %.3f ms  forward %.3f ms  backward %.3f ms  optimizer %.3f ms  "
+          "host enqueue %.3f ms" % (
+              len(times) - 3, name, w["batch"], model.hip_precision, ", deterministic" if deterministic else "",
+              ", device dropout" if device_dropout else "", ", clip 5" if clip else "",
+              ", ClipAdam" if fused_optimizer else "", med[0], med[1], med[2], med[3], med[4]))
 if deterministic:
     import ctypes
     from multistgraph_amd import _lib
