@@ -273,6 +273,7 @@ int matgcn_masked_mae_grad(const float* pred, const float* y, const int32_t* lab
  * matgcn_metric_table turns (accumulated) sums into the table.
  *   l = y, p = pred;  first affine x*std + mean (scalar, or one pair per node: per_node) - the scaler's
  *   inverse_transform (:268-273);  second affine per node - prediction_t = prediction * All_std + All_m (:307-308);
+ *   each affine two fp32 roundings, as the reference's tensors (a fused one moves |d/l| of a label near 0);
  *   p := clamp_min where p < clamp_min (:312);  elements with l <= truth_min are left out (:316-317);
  *   l := 0 where |l| < min_s (loss.py:18, 53, 71; min_s < 0: off - the *_np functions of the re-transform do not).
  * sums per horizon: 0 elements, 1 non-NaN labels, 2 sum|p-l|, 3 sum (p-l)^2, 4 sum |(p-l)/l| (NaN terms -> 0, as

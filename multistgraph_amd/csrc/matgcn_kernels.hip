@@ -1914,6 +1914,13 @@ struct MetricArgs {
   double* partials;      // [B*out][MATGCN_METRIC_SUMS]
 };
 constexpr int METRIC_SUMS = 14;
+// x * sd + mu as two fp32 roundings, the way the reference's tensors de-scale.  hipcc would fuse the pair into one fma:
+// half an ulp of the product is a visible share of a label that de-scales to nearly 0, and of its |d / l| (MAPE).
+__device__ __forceinline__ float metric_affine(float x, float sd, float mu) {
+#pragma clang fp contract(off)
+  const float t = x * sd;
+  return t + mu;
+}
 // sums: 0 elements, 1 non-NaN labels, 2 |d|, 3 d^2, 4 |d/l| (over 1), 5 labels != 0, 6-8 the same three over 5,
 //       9 l, 10 l^2, 11 p, 12 p^2, 13 l-p
 __global__ __launch_bounds__(256) void k_metric_partial(MetricArgs a) {
@@ -1929,8 +1936,11 @@ __global__ __launch_bounds__(256) void k_metric_partial(MetricArgs a) {
   for (int idx = threadIdx.x; idx < a.N * a.od; idx += 256) {
     const int n = idx / a.od, c = idx - n * a.od;
     float l = yp[(size_t)n * a.yFeat + c], p = pp[idx];
-    if (a.std) { const float sd = a.std[a.perNode ? n : 0], mu = a.mean[a.perNode ? n : 0]; l = l * sd + mu; p = p * sd + mu; }
-    if (a.std2) { l = l * a.std2[n] + a.mean2[n]; p = p * a.std2[n] + a.mean2[n]; }
+    if (a.std) {
+      const float sd = a.std[a.perNode ? n : 0], mu = a.mean[a.perNode ? n : 0];
+      l = metric_affine(l, sd, mu); p = metric_affine(p, sd, mu);
+    }
+    if (a.std2) { l = metric_affine(l, a.std2[n], a.mean2[n]); p = metric_affine(p, a.std2[n], a.mean2[n]); }
     if (clamp && p < a.clampMin) p = a.clampMin;
     if (pick && !(l > a.truthMin)) continue;
     if (a.minS >= 0.f && fabsf(l) < a.minS) l = 0.f;
