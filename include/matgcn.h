@@ -44,6 +44,10 @@
  * Still ABI 12: new names only - the device-side optimizer step adds the structs matgcn_opt_tensor and matgcn_adam and the
  * functions matgcn_grad_norm_bytes, matgcn_grad_norm, matgcn_adam_step; no existing symbol, signature, struct or value
  * changed, and no existing entry point launches anything else than it did.
+ * Still ABI 12: new names only - the per-node evaluation tables add the functions matgcn_metric_sums_nodes_bytes,
+ * matgcn_metric_sums_nodes, matgcn_metric_table_rows, matgcn_mc_quantiles_scaled, matgcn_mc_scores_nodes_bytes and
+ * matgcn_mc_scores_nodes; no existing symbol, signature, struct or value changed, and no existing entry point launches
+ * anything else than it did, with other arguments or other bits.
  */
 #ifndef MATGCN_H
 #define MATGCN_H
@@ -302,6 +306,28 @@ int matgcn_metric_sums(const float* pred, const float* y, const int32_t* label_s
  * prediction and truth exchanged, the way traffic_state_executor.py:318-319 calls sklearn. */
 int matgcn_metric_table(const double* sums, int out_steps, int swap_r2, double* table, void* stream);
 
+/* The same 14 sums grouped per horizon AND node - the tract-by-tract view of result_plot.py:102-134 without a row per
+ * prediction element.  Per-element terms, descriptor, geometry, labels and series handling are those of
+ * matgcn_metric_sums (out_steps in 1 .. 64; series rows clamped and counted); sums is (out_steps, nodes,
+ * MATGCN_METRIC_SUMS) doubles and entry [o][n] sums over the batch rows b and the out_dim channels c in a FIXED ORDER:
+ * start from the stored value when accumulate != 0, else from 0, and add the terms one at a time in ascending (b, c).
+ * So one call over B samples and several accumulating calls over the same samples in the same order give identical
+ * bits for any finite input, and nothing depends on the order workgroups run in.  One launch: a thread owns one
+ * (horizon, node) and walks the batch itself, so there is no stage-1 scratch - matgcn_metric_sums_nodes_bytes reports 0
+ * today and callers size `scratch` by it (NULL is accepted while it is 0; a smaller buffer is
+ * MATGCN_ERR_SMALL_BUFFER).  Nothing is allocated, no atomics, the caller's stream only, every argument checked on the
+ * host before the launch. */
+int matgcn_metric_sums_nodes_bytes(int batch, int out_steps, int nodes, int out_dim, size_t* bytes);
+int matgcn_metric_sums_nodes(const float* pred, const float* y, const int32_t* label_start, int batch, int out_steps,
+                             int nodes, int out_dim, int y_steps, int y_feat, int y_start,
+                             const matgcn_metric_scale* scale, void* scratch, size_t scratch_bytes,
+                             double* sums /* (out_steps, nodes, MATGCN_METRIC_SUMS) */, int accumulate, void* stream);
+/* table (rows, MATGCN_METRICS) doubles, device: row r from sum_{f < fold} sums[f*rows + r][:], added in ascending f from
+ * 0, with exactly the arithmetic of the "single" table of matgcn_metric_table (one device function; on the same 14 sums
+ * the same bits, zero counts included).  fold = 1, rows = out_steps*nodes: the table per horizon and node; fold =
+ * out_steps, rows = nodes: the table per node over all horizons - the tract ranking.  rows, fold >= 1. */
+int matgcn_metric_table_rows(const double* sums, int rows, int fold, int swap_r2, double* table, void* stream);
+
 /* ---- training step: forward that keeps activations + backward -----------
  * Replaces torch autograd through MultiATGCN.forward as driven by TrafficStateExecutor._train_epoch
  * (libcity/executor/traffic_state_executor.py:411-422: loss = calculate_loss(batch); loss.backward()).
@@ -476,6 +502,45 @@ int matgcn_mc_scores(const float* samples, int n_samples, const float* y, const 
                      int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start, float mean, float std,
                      float null_val, float min_s, const float* probs /*HOST*/, int n_probs, void* scratch,
                      size_t scratch_bytes, double* sums /* (out_steps, 5 + n_probs) */, int accumulate, void* stream);
+
+/* Both on the re-transformed scale, per node.  The descriptor is the matgcn_metric_scale of the metric sums: every
+ * sample - and in the scores the label - takes its first affine (scalar, or one pair per node: per_node; NULL =
+ * identity) and then the per-node second affine, each an fp32 product plus an fp32 sum, never fused; samples below
+ * clamp_min are set to it BEFORE the sort (the executor's prediction_t < 0 -> 0; NaN: off).  Sort, quantile rule and
+ * roundings are those above.
+ *
+ * matgcn_mc_quantiles_scaled: matgcn_mc_quantiles with the descriptor; element g of the (.., nodes, out_dim) tensor
+ * belongs to node (g / out_dim) % nodes, elems is a multiple of nodes*out_dim.  truth_min and min_s are not used.  With
+ * a scalar affine and no clamp: the bits of matgcn_mc_quantiles.
+ *
+ * matgcn_mc_scores_nodes: the score terms of matgcn_mc_scores (same formulas and roundings) grouped per horizon and
+ * node: sums (out_steps, nodes, 5 + n_probs) doubles, out_steps in 1 .. 64.  Elements with l <= truth_min are left out
+ * (NaN: off; tested before min_s); l := 0 where |l| < min_s and the null_val mask as in matgcn_mc_scores.  Entry [o][n]
+ * starts from the stored value when accumulate != 0, else from 0, and adds the terms of its elements one at a time in
+ * ascending (b, c): one call over B samples and accumulating calls over the same samples in pieces give identical bits.
+ * With a scalar affine, no second affine, no clamp and no truth filter its rows added over the nodes are what
+ * matgcn_mc_scores counts - identically in column 0, and in every column where all partial sums are exact.
+ * Stage 1 sorts tile by tile as matgcn_mc_scores does (a tile spans several nodes, and with out_dim > 1 a node's
+ * channels can sit in two tiles) and writes the terms of every element, zeros for a masked one, into `scratch`
+ * (matgcn_mc_scores_nodes_bytes = 8*(5 + n_probs) bytes per element; less is MATGCN_ERR_SMALL_BUFFER; contents before
+ * and after are of no interest); stage 2 owns one sum per thread.  Nothing is allocated, no atomics, the caller's stream
+ * only, every argument checked on the host before anything is launched.
+ * Measured at Baltimore 403 / B = 64 / out = 24 with the re-transform, clamp 0 and truth_min 6 (MI355X,
+ * tools/node_scores_time.py, median of 20 calls, HIP events, one process; DESIGN.md sections 5b and 5d):
+ * matgcn_metric_sums_nodes 0.048 ms (matgcn_metric_sums 0.049 ms, torch terms + index_add_ 0.342 ms);  S = 32:
+ * matgcn_mc_scores_nodes 0.187 ms with 39.6 MB of scratch (matgcn_mc_scores 0.228 ms, torch.sort + terms + index_add_
+ * 1.194 ms), matgcn_mc_quantiles_scaled 0.128 ms (matgcn_mc_quantiles 0.115 ms);  S = 128: 0.982 (1.042, 6.432) and 0.831
+ * (0.817) ms.  The grouped forms were not slower than the per-horizon ones in this measurement. */
+int matgcn_mc_quantiles_scaled(const float* samples, int n_samples, int64_t elems, int nodes, int out_dim,
+                               const float* probs /*HOST*/, int n_probs, const matgcn_metric_scale* scale,
+                               float* quantiles /* (n_probs, elems) */, void* stream);
+int matgcn_mc_scores_nodes_bytes(int batch, int out_steps, int nodes, int out_dim, int n_samples, int n_probs,
+                                 size_t* bytes);
+int matgcn_mc_scores_nodes(const float* samples, int n_samples, const float* y, const int32_t* label_start, int batch,
+                           int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start,
+                           const matgcn_metric_scale* scale, float null_val, const float* probs /*HOST*/, int n_probs,
+                           void* scratch, size_t scratch_bytes, double* sums /* (out_steps, nodes, 5 + n_probs) */,
+                           int accumulate, void* stream);
 
 /* ---- the optimizer step: global gradient norm, clip and Adam over a table of tensors -------------------------------------
  * What clip_grad_norm_(params, max_norm) followed by torch.optim.Adam.step() does (no amsgrad, no maximize), as three

@@ -1361,6 +1361,45 @@ int matgcn_metric_table(const double* sums, int out_steps, int swap_r2, double* 
   return launch_ok();
 }
 
+int matgcn_metric_sums_nodes_bytes(int batch, int out_steps, int nodes, int out_dim, size_t* bytes) {
+  if (!bytes) return MATGCN_ERR_NULL;
+  if (batch < 1 || out_steps < 1 || out_steps > 64 || nodes < 1 || out_dim < 1) return MATGCN_ERR_BAD_ARG;
+  if ((long)nodes * out_steps >= (1L << 31)) return MATGCN_ERR_UNSUPPORTED;
+  *bytes = 0;      // a thread owns a (horizon, node) and walks the batch itself: no stage-1 partials
+  return MATGCN_OK;
+}
+
+int matgcn_metric_sums_nodes(const float* pred, const float* y, const int32_t* label_start, int batch, int out_steps,
+                             int nodes, int out_dim, int y_steps, int y_feat, int y_start,
+                             const matgcn_metric_scale* scale, void* scratch, size_t scratch_bytes, double* sums,
+                             int accumulate, void* stream) {
+  if (!pred || !y || !scale || !sums) return MATGCN_ERR_NULL;
+  size_t need = 0;
+  RETURN_IF(matgcn_metric_sums_nodes_bytes(batch, out_steps, nodes, out_dim, &need));
+  if (y_steps < out_steps || y_start < 0 || y_start + out_dim > y_feat) return MATGCN_ERR_BAD_ARG;
+  if ((scale->mean == nullptr) != (scale->std == nullptr) || (scale->mean2 == nullptr) != (scale->std2 == nullptr))
+    return MATGCN_ERR_BAD_ARG;
+  if (need > 0 && !scratch) return MATGCN_ERR_NULL;
+  if (scratch_bytes < need) return MATGCN_ERR_SMALL_BUFFER;
+  MetricArgs a;
+  a.pred = pred; a.y = y; a.labelStart = label_start;
+  a.mean = scale->mean; a.std = scale->std; a.mean2 = scale->mean2; a.std2 = scale->std2; a.perNode = scale->per_node;
+  a.clampMin = scale->clamp_min; a.truthMin = scale->truth_min; a.minS = scale->min_s;
+  a.outSteps = out_steps; a.N = nodes; a.od = out_dim; a.ySteps = y_steps; a.yFeat = y_feat; a.yStart = y_start;
+  a.partials = nullptr;
+  const unsigned blocks = (unsigned)(((long)out_steps * nodes + 63) / 64);
+  hipLaunchKernelGGL(k_metric_nodes, dim3(blocks), dim3(64), 0, (hipStream_t)stream, a, batch, accumulate, sums);
+  return launch_ok();
+}
+
+int matgcn_metric_table_rows(const double* sums, int rows, int fold, int swap_r2, double* table, void* stream) {
+  if (!sums || !table) return MATGCN_ERR_NULL;
+  if (rows < 1 || fold < 1) return MATGCN_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_metric_table_rows, dim3((unsigned)(((long)rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sums,
+                     rows, fold, swap_r2, table);
+  return launch_ok();
+}
+
 // ---- quantiles and probabilistic scores of a Monte-Carlo-dropout ensemble (matgcn_mc_scores.hip) -----------------------
 namespace {
 // the tile of S samples: P = S rounded up to a power of two, TE = 2^logTE elements with P * TE <= MC_TILE_FLOATS
@@ -1462,6 +1501,84 @@ int matgcn_mc_scores(const float* samples, int n_samples, const float* y, const 
   CHECK_LAUNCH();
   hipLaunchKernelGGL(k_mc_accumulate, dim3((unsigned)out_steps), dim3(64), 0, s, a.partials, batch, out_steps, tilesPerRow,
                      K, accumulate, sums);
+  return launch_ok();
+}
+
+namespace {
+// the sample-side part of the descriptor; a lone mean or std is refused
+int mc_scale(const matgcn_metric_scale* scale, McScale* sc) {
+  if (!scale) return MATGCN_ERR_NULL;
+  if ((scale->mean == nullptr) != (scale->std == nullptr) || (scale->mean2 == nullptr) != (scale->std2 == nullptr))
+    return MATGCN_ERR_BAD_ARG;
+  sc->mean = scale->mean; sc->std = scale->std; sc->mean2 = scale->mean2; sc->std2 = scale->std2;
+  sc->perNode = scale->per_node; sc->clampMin = scale->clamp_min;
+  return MATGCN_OK;
+}
+}  // namespace
+
+int matgcn_mc_quantiles_scaled(const float* samples, int n_samples, int64_t elems, int nodes, int out_dim,
+                               const float* probs, int n_probs, const matgcn_metric_scale* scale, float* quantiles,
+                               void* stream) {
+  if (!samples || !probs || !quantiles) return MATGCN_ERR_NULL;
+  McScale sc;
+  RETURN_IF(mc_scale(scale, &sc));
+  if (n_samples < 1 || n_samples > MATGCN_MAX_MC_SAMPLES || elems < 1 || nodes < 1 || out_dim < 1)
+    return MATGCN_ERR_BAD_ARG;
+  const long rowLen = (long)nodes * out_dim;
+  if (rowLen >= (1L << 31)) return MATGCN_ERR_UNSUPPORTED;
+  if (elems % rowLen != 0) return MATGCN_ERR_BAD_ARG;
+  McLevels lv;
+  RETURN_IF(mc_levels(probs, n_probs, n_samples, &lv));
+  const McTile t = mc_tile(n_samples);
+  const int64_t blocks = (elems + (1 << t.logTE) - 1) >> t.logTE;
+  if (blocks >= (1LL << 31)) return MATGCN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(k_mc_quantiles_scaled, dim3((unsigned)blocks), dim3(256), (size_t)t.ldsBytes, (hipStream_t)stream,
+                     samples, lv, n_samples, t.P, t.logTE, (long long)elems, (int)rowLen, out_dim, sc, quantiles);
+  return launch_ok();
+}
+
+int matgcn_mc_scores_nodes_bytes(int batch, int out_steps, int nodes, int out_dim, int n_samples, int n_probs,
+                                 size_t* bytes) {
+  if (!bytes) return MATGCN_ERR_NULL;
+  if (n_probs < 1 || n_probs > MATGCN_MAX_MC_QUANTILES || out_steps > 64) return MATGCN_ERR_BAD_ARG;
+  int tilesPerRow = 0;
+  long blocks = 0;
+  RETURN_IF(mc_score_grid(batch, out_steps, nodes, out_dim, n_samples, &tilesPerRow, &blocks));
+  // one term per element and sum: stage 2 adds them one at a time
+  *bytes = (size_t)batch * out_steps * nodes * out_dim * (MATGCN_MC_SCORE_SUMS + n_probs) * sizeof(double);
+  return MATGCN_OK;
+}
+
+int matgcn_mc_scores_nodes(const float* samples, int n_samples, const float* y, const int32_t* label_start, int batch,
+                           int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start,
+                           const matgcn_metric_scale* scale, float null_val, const float* probs, int n_probs,
+                           void* scratch, size_t scratch_bytes, double* sums, int accumulate, void* stream) {
+  if (!samples || !y || !probs || !scratch || !sums) return MATGCN_ERR_NULL;
+  McNodeArgs a;
+  RETURN_IF(mc_scale(scale, &a.sc));
+  if (out_steps > 64) return MATGCN_ERR_BAD_ARG;
+  int tilesPerRow = 0;
+  long blocks = 0;
+  RETURN_IF(mc_score_grid(batch, out_steps, nodes, out_dim, n_samples, &tilesPerRow, &blocks));
+  if (y_steps < 1 || (!label_start && y_steps < out_steps) || y_feat < 1 || y_start < 0 || y_start + out_dim > y_feat)
+    return MATGCN_ERR_BAD_ARG;
+  McLevels lv;
+  RETURN_IF(mc_levels(probs, n_probs, n_samples, &lv));
+  const int K = MATGCN_MC_SCORE_SUMS + n_probs;
+  a.E = (long long)batch * out_steps * nodes * out_dim;
+  if (scratch_bytes < (size_t)a.E * K * sizeof(double)) return MATGCN_ERR_SMALL_BUFFER;
+  const McTile t = mc_tile(n_samples);
+  a.samples = samples; a.y = y; a.labelStart = label_start;
+  a.S = n_samples; a.P = t.P; a.logTE = t.logTE;
+  a.outSteps = out_steps; a.N = nodes; a.od = out_dim; a.ySteps = y_steps; a.yFeat = y_feat; a.yStart = y_start;
+  a.tilesPerRow = tilesPerRow;
+  a.truthMin = scale->truth_min; a.minS = scale->min_s; a.nullVal = null_val;
+  a.terms = (double*)scratch;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_mc_scores_nodes, dim3((unsigned)blocks), dim3(256), (size_t)t.ldsBytes, s, a, lv);
+  CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_mc_accumulate_nodes, dim3(blocks_for((size_t)out_steps * nodes * K)), dim3(256), 0, s, a.terms, batch,
+                     out_steps, nodes, out_dim, K, accumulate, sums);
   return launch_ok();
 }
 

@@ -1923,6 +1923,27 @@ __device__ __forceinline__ float metric_affine(float x, float sd, float mu) {
 }
 // sums: 0 elements, 1 non-NaN labels, 2 |d|, 3 d^2, 4 |d/l| (over 1), 5 labels != 0, 6-8 the same three over 5,
 //       9 l, 10 l^2, 11 p, 12 p^2, 13 l-p
+// The terms of one element - raw label l and prediction p of node n - added onto s[], one add per sum: both groupings
+// of the sums (per horizon, per horizon and node) are this function, so their per-element terms cannot differ.
+__device__ __forceinline__ void metric_add_element(const MetricArgs& a, bool clamp, bool pick, int n, float l, float p,
+                                                   double* s) {
+  if (a.std) {
+    const float sd = a.std[a.perNode ? n : 0], mu = a.mean[a.perNode ? n : 0];
+    l = metric_affine(l, sd, mu); p = metric_affine(p, sd, mu);
+  }
+  if (a.std2) { l = metric_affine(l, a.std2[n], a.mean2[n]); p = metric_affine(p, a.std2[n], a.mean2[n]); }
+  if (clamp && p < a.clampMin) p = a.clampMin;
+  if (pick && !(l > a.truthMin)) return;
+  if (a.minS >= 0.f && fabsf(l) < a.minS) l = 0.f;
+  const float d = p - l, ad = fabsf(d), sq = d * d, ap = fabsf(d / l);
+  const bool valid = l == l, nz = l != 0.f;          // NaN != 0 holds, as in labels.ne(0)
+  s[0] += 1.0;
+  if (valid) { s[1] += 1.0; s[2] += ad == ad ? ad : 0.f; s[3] += sq == sq ? sq : 0.f; s[4] += ap == ap ? ap : 0.f; }
+  if (nz) { s[5] += 1.0; s[6] += ad == ad ? ad : 0.f; s[7] += sq == sq ? sq : 0.f; s[8] += ap == ap ? ap : 0.f; }
+  const double ld = l, pd = p;
+  s[9] += ld; s[10] += ld * ld; s[11] += pd; s[12] += pd * pd; s[13] += ld - pd;
+}
+
 __global__ __launch_bounds__(256) void k_metric_partial(MetricArgs a) {
   __shared__ double red[4][METRIC_SUMS];
   const int b = blockIdx.x / a.outSteps, o = blockIdx.x - b * a.outSteps;
@@ -1935,22 +1956,7 @@ __global__ __launch_bounds__(256) void k_metric_partial(MetricArgs a) {
   const bool clamp = a.clampMin == a.clampMin, pick = a.truthMin == a.truthMin;
   for (int idx = threadIdx.x; idx < a.N * a.od; idx += 256) {
     const int n = idx / a.od, c = idx - n * a.od;
-    float l = yp[(size_t)n * a.yFeat + c], p = pp[idx];
-    if (a.std) {
-      const float sd = a.std[a.perNode ? n : 0], mu = a.mean[a.perNode ? n : 0];
-      l = metric_affine(l, sd, mu); p = metric_affine(p, sd, mu);
-    }
-    if (a.std2) { l = metric_affine(l, a.std2[n], a.mean2[n]); p = metric_affine(p, a.std2[n], a.mean2[n]); }
-    if (clamp && p < a.clampMin) p = a.clampMin;
-    if (pick && !(l > a.truthMin)) continue;
-    if (a.minS >= 0.f && fabsf(l) < a.minS) l = 0.f;
-    const float d = p - l, ad = fabsf(d), sq = d * d, ap = fabsf(d / l);
-    const bool valid = l == l, nz = l != 0.f;          // NaN != 0 holds, as in labels.ne(0)
-    s[0] += 1.0;
-    if (valid) { s[1] += 1.0; s[2] += ad == ad ? ad : 0.f; s[3] += sq == sq ? sq : 0.f; s[4] += ap == ap ? ap : 0.f; }
-    if (nz) { s[5] += 1.0; s[6] += ad == ad ? ad : 0.f; s[7] += sq == sq ? sq : 0.f; s[8] += ap == ap ? ap : 0.f; }
-    const double ld = l, pd = p;
-    s[9] += ld; s[10] += ld * ld; s[11] += pd; s[12] += pd * pd; s[13] += ld - pd;
+    metric_add_element(a, clamp, pick, n, yp[(size_t)n * a.yFeat + c], pp[idx], s);
   }
 #pragma unroll
   for (int k = 0; k < METRIC_SUMS; ++k) {
@@ -1974,10 +1980,54 @@ __global__ __launch_bounds__(64) void k_metric_accumulate(const double* __restri
   sums[o * METRIC_SUMS + k] = (accumulate ? sums[o * METRIC_SUMS + k] : 0.0) + v;
 }
 
+// The same sums grouped per (horizon, node): thread (o, n) walks the batch itself and adds the terms of its elements one
+// at a time in ascending (b, c), onto the stored sums when accumulate is set - the value is a chain of adds in an order
+// the data alone fixes, so one call over B rows and accumulating calls over the same rows in pieces give the same bits.
+// No scratch, no second stage; lanes of a wave hold consecutive nodes of one horizon (coalesced for od = 1).
+__global__ __launch_bounds__(64) void k_metric_nodes(MetricArgs a, int B, int accumulate, double* __restrict__ sums) {
+  const int idx = blockIdx.x * 64 + threadIdx.x;
+  if (idx >= a.outSteps * a.N) return;
+  const int o = idx / a.N, n = idx - o * a.N;
+  double s[METRIC_SUMS];
+#pragma unroll
+  for (int k = 0; k < METRIC_SUMS; ++k) s[k] = accumulate ? sums[(size_t)idx * METRIC_SUMS + k] : 0.0;
+  const bool clamp = a.clampMin == a.clampMin, pick = a.truthMin == a.truthMin;
+  for (int b = 0; b < B; ++b) {
+    const size_t yrow = a.labelStart ? series_row((long)a.labelStart[b] + o, a.ySteps) : (size_t)b * a.ySteps + o;
+    const float* yp = a.y + (yrow * a.N + n) * a.yFeat + a.yStart;
+    const float* pp = a.pred + (((size_t)b * a.outSteps + o) * a.N + n) * a.od;
+    for (int c = 0; c < a.od; ++c) metric_add_element(a, clamp, pick, n, yp[c], pp[c], s);
+  }
+#pragma unroll
+  for (int k = 0; k < METRIC_SUMS; ++k) sums[(size_t)idx * METRIC_SUMS + k] = s[k];
+}
+
+// one row of the table from its 14 sums; m: MAE, MAPE, MSE, RMSE, masked_MAE, masked_MAPE, masked_MSE, masked_RMSE, R2,
+// EVAR (the order of TrafficStateEvaluator.json).  swap: R2 / EVAR with prediction and truth exchanged, as
+// traffic_state_executor.py:318-319 hands them to sklearn.
+__device__ __forceinline__ void metric_row(const double* s, int swap, double* t) {
+  const double n = s[0];
+  // mask / mean(mask) then mean: sum over the kept elements / their count; nothing kept -> nan -> 0 (loss.py:24-27)
+  t[0] = s[1] > 0 ? s[2] / s[1] : 0.0;
+  t[1] = s[1] > 0 ? s[4] / s[1] : 0.0;
+  t[2] = s[1] > 0 ? s[3] / s[1] : 0.0;
+  t[3] = sqrt(t[2]);
+  t[4] = s[5] > 0 ? s[6] / s[5] : 0.0;
+  t[5] = s[5] > 0 ? s[8] / s[5] : 0.0;
+  t[6] = s[5] > 0 ? s[7] / s[5] : 0.0;
+  t[7] = sqrt(t[6]);
+  // sklearn r2_score(y_true, y_pred) = 1 - sum (t-p)^2 / sum (t - mean t)^2, explained_variance_score = 1 - Var(t-p)/Var(t)
+  // (the residual sum leaves NaN labels out; sklearn refuses such input anyway)
+  const double s1 = swap ? s[11] : s[9], s2 = swap ? s[12] : s[10];
+  const double ssTot = n > 0 ? s2 - s1 * s1 / n : 0.0, res = s[3];
+  const double varD = n > 0 ? res / n - (s[13] / n) * (s[13] / n) : 0.0;
+  const double varT = n > 0 ? ssTot / n : 0.0;
+  t[8] = ssTot != 0.0 ? 1.0 - res / ssTot : (res == 0.0 ? 1.0 : 0.0);
+  t[9] = varT != 0.0 ? 1.0 - varD / varT : (varD == 0.0 ? 1.0 : 0.0);
+}
+
 // table[mode][o][m]: mode 0 "single" = horizon o alone, mode 1 "average" = horizons 0..o (traffic_state_evaluator.py:
-// 46-121); m: MAE, MAPE, MSE, RMSE, masked_MAE, masked_MAPE, masked_MSE, masked_RMSE, R2, EVAR (the order of
-// TrafficStateEvaluator.json).  swap: R2 / EVAR with prediction and truth exchanged, as traffic_state_executor.py:
-// 318-319 hands them to sklearn.
+// 46-121); columns as metric_row.
 __global__ __launch_bounds__(64) void k_metric_table(const double* __restrict__ sums, int outSteps, int swap,
                                                      double* __restrict__ table) {
   const int o = threadIdx.x;
@@ -1987,26 +2037,21 @@ __global__ __launch_bounds__(64) void k_metric_table(const double* __restrict__ 
     for (int k = 0; k < METRIC_SUMS; ++k) s[k] = 0.0;
     for (int q = mode ? 0 : o; q <= o; ++q)
       for (int k = 0; k < METRIC_SUMS; ++k) s[k] += sums[q * METRIC_SUMS + k];
-    double* t = table + ((size_t)mode * outSteps + o) * 10;
-    const double n = s[0];
-    // mask / mean(mask) then mean: sum over the kept elements / their count; nothing kept -> nan -> 0 (loss.py:24-27)
-    t[0] = s[1] > 0 ? s[2] / s[1] : 0.0;
-    t[1] = s[1] > 0 ? s[4] / s[1] : 0.0;
-    t[2] = s[1] > 0 ? s[3] / s[1] : 0.0;
-    t[3] = sqrt(t[2]);
-    t[4] = s[5] > 0 ? s[6] / s[5] : 0.0;
-    t[5] = s[5] > 0 ? s[8] / s[5] : 0.0;
-    t[6] = s[5] > 0 ? s[7] / s[5] : 0.0;
-    t[7] = sqrt(t[6]);
-    // sklearn r2_score(y_true, y_pred) = 1 - sum (t-p)^2 / sum (t - mean t)^2, explained_variance_score = 1 - Var(t-p)/Var(t)
-    // (the residual sum leaves NaN labels out; sklearn refuses such input anyway)
-    const double s1 = swap ? s[11] : s[9], s2 = swap ? s[12] : s[10];
-    const double ssTot = n > 0 ? s2 - s1 * s1 / n : 0.0, res = s[3];
-    const double varD = n > 0 ? res / n - (s[13] / n) * (s[13] / n) : 0.0;
-    const double varT = n > 0 ? ssTot / n : 0.0;
-    t[8] = ssTot != 0.0 ? 1.0 - res / ssTot : (res == 0.0 ? 1.0 : 0.0);
-    t[9] = varT != 0.0 ? 1.0 - varD / varT : (varD == 0.0 ? 1.0 : 0.0);
+    metric_row(s, swap, table + ((size_t)mode * outSteps + o) * 10);
   }
+}
+
+// table[r][m] from sum_{f < fold} sums[f * rows + r][.], added in ascending f from 0 - with fold = 1 the arithmetic of
+// k_metric_table's "single" mode, add of the zero included
+__global__ __launch_bounds__(256) void k_metric_table_rows(const double* __restrict__ sums, int rows, int fold, int swap,
+                                                           double* __restrict__ table) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  double s[METRIC_SUMS];
+  for (int k = 0; k < METRIC_SUMS; ++k) s[k] = 0.0;
+  for (int f = 0; f < fold; ++f)
+    for (int k = 0; k < METRIC_SUMS; ++k) s[k] += sums[((size_t)f * rows + r) * METRIC_SUMS + k];
+  metric_row(s, swap, table + (size_t)r * 10);
 }
 
 // gradient of result[0] w.r.t. pred: upstream * std * sign(p - l) * mask / sum(mask)   (torch: d|x| = sign(x), 0 at 0;

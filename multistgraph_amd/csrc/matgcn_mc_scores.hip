@@ -1,5 +1,6 @@
 // matgcn_mc_scores.hip - empirical quantiles and probabilistic scores of a Monte-Carlo-dropout ensemble
-// (matgcn_mc_quantiles / matgcn_mc_scores, include/matgcn.h).  Included by matgcn_capi.hip.
+// (matgcn_mc_quantiles / matgcn_mc_scores, and on the re-transformed scale matgcn_mc_quantiles_scaled / per (horizon,
+// node) matgcn_mc_scores_nodes; include/matgcn.h).  Included by matgcn_capi.hip.
 //
 // Input: the sample-major tensor matgcn_forward_mc writes to samples_out, samples (S, E), E = B * out * N * od.
 // One sort core serves both entry points: a workgroup of 256 threads takes a tile of TE consecutive elements and all S
@@ -66,18 +67,10 @@ struct McLevels {
 
 __device__ __forceinline__ int mc_row(int s) { return s ^ ((s >> 1) & 1); }
 
-// Loads the tile (columns e0 .. e0 + nValid - 1 of `samples`, all S rows), de-scaled, and sorts every column ascending.
-// Called by all 256 threads; ends with a barrier.
-__device__ __forceinline__ void mc_sort_tile(float* __restrict__ x, const float* __restrict__ samples, int S, int P,
-                                             int logTE, size_t E, size_t e0, int nValid, float mean, float std) {
+// Sorts every column of the loaded tile ascending (bitonic network over the P rows).  Called by all 256 threads; begins
+// and ends with a barrier.
+__device__ __forceinline__ void mc_sort_network(float* __restrict__ x, int P, int logTE) {
   const int TE = 1 << logTE, tid = threadIdx.x;
-  for (int idx = tid; idx < (P << logTE); idx += 256) {
-    const int s = idx >> logTE, e = idx & (TE - 1);
-    float v = __builtin_inff();
-    if (e >= nValid) v = 0.f;
-    else if (s < S) v = mc_affine(samples[(size_t)s * E + e0 + e], std, mean);
-    x[(mc_row(s) << logTE) + e] = v;
-  }
   __syncthreads();
   const int pairs = (P >> 1) << logTE;
   for (int k = 2; k <= P; k <<= 1) {
@@ -97,6 +90,60 @@ __device__ __forceinline__ void mc_sort_tile(float* __restrict__ x, const float*
   }
 }
 
+// Loads the tile (columns e0 .. e0 + nValid - 1 of `samples`, all S rows), de-scaled, and sorts every column ascending.
+// Called by all 256 threads; ends with a barrier.
+__device__ __forceinline__ void mc_sort_tile(float* __restrict__ x, const float* __restrict__ samples, int S, int P,
+                                             int logTE, size_t E, size_t e0, int nValid, float mean, float std) {
+  const int TE = 1 << logTE, tid = threadIdx.x;
+  for (int idx = tid; idx < (P << logTE); idx += 256) {
+    const int s = idx >> logTE, e = idx & (TE - 1);
+    float v = __builtin_inff();
+    if (e >= nValid) v = 0.f;
+    else if (s < S) v = mc_affine(samples[(size_t)s * E + e0 + e], std, mean);
+    x[(mc_row(s) << logTE) + e] = v;
+  }
+  mc_sort_network(x, P, logTE);
+}
+
+// The descriptor of the node-grouped entry points (matgcn_metric_scale without the label-only fields): first affine
+// (scalar or one pair per node; null = identity), second affine per node, clamp from below (NaN: off).
+struct McScale {
+  const float* mean; const float* std;
+  const float* mean2; const float* std2;
+  int perNode;
+  float clampMin;
+};
+// the affines of node n, each two fp32 roundings
+__device__ __forceinline__ float mc_descale_node(const McScale& sc, int n, float v) {
+  if (sc.std) v = mc_affine(v, sc.std[sc.perNode ? n : 0], sc.mean[sc.perNode ? n : 0]);
+  if (sc.std2) v = mc_affine(v, sc.std2[n], sc.mean2[n]);
+  return v;
+}
+
+// mc_sort_tile with the descriptor in place of the two scalars.  256 is a multiple of TE, so a thread loads one column
+// e = tid & (TE - 1) only: `node` is that column's node (read where e < nValid only) and its affines are fetched once.
+__device__ __forceinline__ void mc_sort_tile_scaled(float* __restrict__ x, const float* __restrict__ samples, int S, int P,
+                                                    int logTE, size_t E, size_t e0, int nValid, int node,
+                                                    const McScale& sc) {
+  const int TE = 1 << logTE, tid = threadIdx.x, e = tid & (TE - 1);
+  const bool live = e < nValid, clamp = sc.clampMin == sc.clampMin;
+  float sd = 1.f, mu = 0.f, sd2 = 1.f, mu2 = 0.f;
+  if (live && sc.std) { sd = sc.std[sc.perNode ? node : 0]; mu = sc.mean[sc.perNode ? node : 0]; }
+  if (live && sc.std2) { sd2 = sc.std2[node]; mu2 = sc.mean2[node]; }
+  for (int s = tid >> logTE; s < P; s += 256 >> logTE) {
+    float v = __builtin_inff();
+    if (!live) v = 0.f;
+    else if (s < S) {
+      v = samples[(size_t)s * E + e0 + e];
+      if (sc.std) v = mc_affine(v, sd, mu);
+      if (sc.std2) v = mc_affine(v, sd2, mu2);
+      if (clamp && v < sc.clampMin) v = sc.clampMin;
+    }
+    x[(mc_row(s) << logTE) + e] = v;
+  }
+  mc_sort_network(x, P, logTE);
+}
+
 __device__ __forceinline__ float mc_quantile(const float* x, int logTE, int e, const McLevels& lv, int k) {
   return mc_lerp(x[(mc_row(lv.lo[k]) << logTE) + e], x[(mc_row(lv.hi[k]) << logTE) + e], lv.g[k]);
 }
@@ -111,6 +158,23 @@ __global__ __launch_bounds__(256) void k_mc_quantiles(const float* __restrict__ 
   const long long left = E - (long long)e0;
   const int nValid = left < TE ? (int)left : TE;
   mc_sort_tile(mcTile, samples, S, P, logTE, (size_t)E, e0, nValid, mean, std);
+  for (int idx = threadIdx.x; idx < (lv.n << logTE); idx += 256) {
+    const int k = idx >> logTE, e = idx & (TE - 1);
+    if (e < nValid) out[(size_t)k * E + e0 + e] = mc_quantile(mcTile, logTE, e, lv, k);
+  }
+}
+
+// k_mc_quantiles with the descriptor: element g of the (.., N, od) tensor belongs to node (g / od) % N
+__global__ __launch_bounds__(256) void k_mc_quantiles_scaled(const float* __restrict__ samples, McLevels lv, int S, int P,
+                                                             int logTE, long long E, int rowLen, int od, McScale sc,
+                                                             float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) float mcTile[];
+  const int TE = 1 << logTE;
+  const size_t e0 = (size_t)blockIdx.x << logTE;
+  const long long left = E - (long long)e0;
+  const int nValid = left < TE ? (int)left : TE;
+  const int node = (int)((e0 + (threadIdx.x & (TE - 1))) % (size_t)rowLen) / od;
+  mc_sort_tile_scaled(mcTile, samples, S, P, logTE, (size_t)E, e0, nValid, node, sc);
   for (int idx = threadIdx.x; idx < (lv.n << logTE); idx += 256) {
     const int k = idx >> logTE, e = idx & (TE - 1);
     if (e < nValid) out[(size_t)k * E + e0 + e] = mc_quantile(mcTile, logTE, e, lv, k);
@@ -214,4 +278,112 @@ __global__ __launch_bounds__(64) void k_mc_accumulate(const double* __restrict__
     for (int t = 0; t < tilesPerRow; ++t) v += p[(size_t)t * K];
   }
   sums[o * K + k] = (accumulate ? sums[o * K + k] : 0.0) + v;
+}
+
+// ---- the same scores grouped per (horizon, node) (matgcn_mc_scores_nodes) ------------------------------------------------
+// A tile of consecutive elements of a (b, horizon) row spans several nodes, and with od > 1 a node's channels can sit in
+// two tiles, so stage 1 keeps k_mc_scores' grid - one sort per tile, every sample read once - and hands the 5 + n terms
+// of every element (zeros for a masked one) to stage 2, which owns one (horizon, node, sum) per thread and adds its
+// terms one at a time in ascending (b, c) onto the stored value: a chain of adds whose order the data alone fixes.
+struct McNodeArgs {
+  const float* samples;   // (S, B, out, N, od)
+  const float* y;         // as McScoreArgs
+  const int* labelStart;
+  int S, P, logTE;
+  int outSteps, N, od, ySteps, yFeat, yStart, tilesPerRow;
+  long long E;
+  McScale sc;
+  float truthMin, minS, nullVal;
+  double* terms;          // [E][5 + n]
+};
+
+__global__ __launch_bounds__(256) void k_mc_scores_nodes(McNodeArgs a, McLevels lv) {
+  extern __shared__ __attribute__((aligned(16))) float mcTile[];
+  const int logTE = a.logTE, TE = 1 << logTE, tid = threadIdx.x;
+  const int rowLen = a.N * a.od;
+  const int row = blockIdx.x / a.tilesPerRow, t = blockIdx.x - row * a.tilesPerRow;
+  const int b = row / a.outSteps, o = row - b * a.outSteps;
+  const int r0 = t << logTE;
+  const int nValid = min(TE, rowLen - r0);
+  const size_t e0 = (size_t)row * rowLen + r0;
+  const int e = tid & (TE - 1);
+  const int r = r0 + e, n = r / a.od, c = r - n * a.od;   // a node of the row where e < nValid
+  const bool inRow = e < nValid;
+  mc_sort_tile_scaled(mcTile, a.samples, a.S, a.P, logTE, (size_t)a.E, e0, nValid, n, a.sc);
+
+  float l = 0.f;
+  bool keep = false;
+  if (inRow) {
+    const size_t yrow = a.labelStart ? series_row((long)a.labelStart[b] + o, a.ySteps) : (size_t)b * a.ySteps + o;
+    l = mc_descale_node(a.sc, n, a.y[(yrow * a.N + n) * a.yFeat + a.yStart + c]);
+    keep = !(a.truthMin == a.truthMin) || l > a.truthMin;
+    if (fabsf(l) < a.minS) l = 0.f;
+    keep = keep && (a.nullVal != a.nullVal ? l == l : l != a.nullVal);
+  }
+  // from here to the terms v[]: the statements of k_mc_scores, which stays as it was (sharing them through inline
+  // functions cost that kernel 18 scalar-register spills); tests hold the two kernels' sums together
+  const int slot = tid >> logTE, slots = 256 >> logTE;
+  const double ld = (double)l;
+  double sAbs = 0.0, sWgt = 0.0;
+  for (int i = slot; i < a.S; i += slots) {
+    const double xi = (double)mcTile[(mc_row(i) << logTE) + e];
+    sAbs += fabs(xi - ld);
+    sWgt += mc_mul((double)(2 * i - a.S + 1), xi);      // exact: an integer below 2^11 times an fp32 value
+  }
+  float qv[MC_MAX_PROBS];
+#pragma unroll
+  for (int k = 0; k < MC_MAX_PROBS; ++k) qv[k] = (slot == 0 && k < lv.n) ? mc_quantile(mcTile, logTE, e, lv, k) : 0.f;
+  __syncthreads();                                      // the sorted tile has been read: its floats become the scratch
+  double* red = reinterpret_cast<double*>(mcTile);
+  red[2 * tid] = sAbs; red[2 * tid + 1] = sWgt;
+  __syncthreads();
+  if (tid >= TE || !inRow) return;                      // slot 0 holds every element of the tile
+  double v[MC_MAX_SUMS];
+#pragma unroll
+  for (int k = 0; k < MC_MAX_SUMS; ++k) v[k] = 0.0;
+  if (keep) {
+    double A = 0.0, W = 0.0;
+    for (int s = 0; s < slots; ++s) { A += red[2 * ((s << logTE) + e)]; W += red[2 * ((s << logTE) + e) + 1]; }
+    const double Sd = (double)a.S;
+    float qFirst = 0.f, qLast = 0.f;
+#pragma unroll
+    for (int k = 0; k < MC_MAX_PROBS; ++k) {
+      if (k == 0) qFirst = qv[k];
+      if (k == lv.n - 1) qLast = qv[k];
+    }
+    const double width = (double)qLast - (double)qFirst;
+    v[0] = 1.0;
+    v[1] = A / Sd - W / (Sd * Sd);
+    v[2] = (qFirst <= l && l <= qLast) ? 1.0 : 0.0;
+    v[3] = width;
+    v[4] = mc_axpy(mc_axpy(width, lv.winkler, fmax((double)qFirst - ld, 0.0)), lv.winkler, fmax(ld - (double)qLast, 0.0));
+#pragma unroll
+    for (int k = 0; k < MC_MAX_PROBS; ++k) {
+      if (k < lv.n) {
+        const double d = ld - (double)qv[k];
+        v[MC_SCORE_SUMS + k] = fmax(mc_mul(lv.q[k], d), mc_mul(lv.q[k] - 1.0, d));
+      }
+    }
+  }
+  const int K = MC_SCORE_SUMS + lv.n;
+  double* out = a.terms + (e0 + e) * K;
+#pragma unroll
+  for (int k = 0; k < MC_MAX_SUMS; ++k)
+    if (k < K) out[k] = v[k];
+}
+
+// stage 2: thread (o, n, k): sums[o][n][k] = (stored or 0) + the terms of its elements, one add each, ascending (b, c)
+__global__ __launch_bounds__(256) void k_mc_accumulate_nodes(const double* __restrict__ terms, int B, int outSteps, int N,
+                                                             int od, int K, int accumulate, double* __restrict__ sums) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)outSteps * N * K) return;
+  const int k = (int)(idx % K);
+  const size_t on = idx / K;
+  const int n = (int)(on % N), o = (int)(on / N);
+  double v = accumulate ? sums[idx] : 0.0;
+  for (int b = 0; b < B; ++b) {
+    const double* p = terms + ((((size_t)b * outSteps + o) * N + n) * od) * K + k;
+    for (int c = 0; c < od; ++c) v += p[(size_t)c * K];
+  }
+  sums[idx] = v;
 }

@@ -20,7 +20,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib
-from .ops import mc_scores, metric_sums, metric_table
+from .ops import mc_scores, mc_scores_nodes, metric_sums, metric_sums_nodes, metric_table, metric_table_rows
 
 ALLOWED_METRICS = list(_lib.METRICS)
 
@@ -101,11 +101,7 @@ class ProbabilisticEvaluator:
     |label| < ``min_s`` counted as 0: the convention of calculate_loss).  config keys: ``min_s`` (1e-4)."""
 
     def __init__(self, config, probs=(0.05, 0.5, 0.95)):
-        self.probs = tuple(float(q) for q in probs)
-        if not 1 <= len(self.probs) <= _lib.MAX_MC_QUANTILES:
-            raise ValueError("probs: 1 .. %d levels, got %d" % (_lib.MAX_MC_QUANTILES, len(self.probs)))
-        if any(not 0.0 <= q <= 1.0 for q in self.probs) or any(a > b for a, b in zip(self.probs, self.probs[1:])):
-            raise ValueError("probs must be ascending levels in [0, 1], got %s" % (self.probs,))
+        self.probs = _check_probs(probs)
         self.min_s = float(config.get("min_s", 1e-4))
         self.columns: List[str] = ["CRPS", "PICP", "MPIW", "WINKLER"] + ["PINBALL_%g" % q for q in self.probs]
         self.clear()
@@ -140,6 +136,116 @@ class ProbabilisticEvaluator:
             for c, name in enumerate(self.columns):
                 self.result[name + "@" + str(i)] = float(t[i - 1, c])
         return self.result
+
+
+def _check_probs(probs):
+    probs = tuple(float(q) for q in probs)
+    if not 1 <= len(probs) <= _lib.MAX_MC_QUANTILES:
+        raise ValueError("probs: 1 .. %d levels, got %d" % (_lib.MAX_MC_QUANTILES, len(probs)))
+    if any(not 0.0 <= q <= 1.0 for q in probs) or any(a > b for a, b in zip(probs, probs[1:])):
+        raise ValueError("probs must be ascending levels in [0, 1], got %s" % (probs,))
+    return probs
+
+
+class NodeEvaluator:
+    """The tract-by-tract view of a test set (result_plot.py:102-134) without a row per prediction element: the sums of
+    ``DeviceEvaluator(streaming=True)`` and of ``ProbabilisticEvaluator`` kept per (horizon, node) on the device
+    (matgcn_metric_sums_nodes / matgcn_mc_scores_nodes), over every batch collected since ``clear``.  Batches add up in a
+    fixed order: any split of the test set into batches gives the same bits.
+
+    ``group_mean`` / ``group_std`` (one value per node, as a pair): the re-transform of traffic_state_executor.py:293-322
+    - values go through x * All_std + All_m after the scaler, predictions and samples below 0 become 0, tiny labels are
+    not zeroed, nothing is masked but NaN labels, and R2 / EVAR exchange prediction and truth as ``groupstd_table``
+    does.  Without them: the conventions of the two per-horizon evaluators (``min_s`` of the config, null value 0 for the
+    scores).  ``s_small``: only elements whose (re-transformed) truth exceeds it take part (None: all).  ``probs``: the
+    levels of the probabilistic scores (None: ``collect_samples`` is not available)."""
+
+    def __init__(self, config, probs=None, group_mean=None, group_std=None, s_small=None):
+        if (group_mean is None) != (group_std is None):
+            raise ValueError("group_mean and group_std come as a pair")
+        self.probs = None if probs is None else _check_probs(probs)
+        self.group = None if group_mean is None else (group_mean, group_std)
+        self.truth_min = float("nan") if s_small is None else float(s_small)
+        self.clamp_min = float("nan") if self.group is None else 0.0
+        self.min_s = float(config.get("min_s", 1e-4)) if self.group is None else -1.0
+        self.null_val = 0.0 if self.group is None else float("nan")
+        self.swap_r2 = self.group is not None
+        self.score_columns: List[str] = [] if self.probs is None else (
+            ["CRPS", "PICP", "MPIW", "WINKLER"] + ["PINBALL_%g" % q for q in self.probs])
+        self.clear()
+
+    def clear(self):
+        self._metric_sums: Optional[torch.Tensor] = None     # (out, N, 14)
+        self._score_sums: Optional[torch.Tensor] = None      # (out, N, 5 + levels)
+
+    def _scale(self, mean, std):
+        if (mean is None) != (std is None):
+            raise ValueError("mean and std come as a pair")
+        gm, gs = self.group if self.group is not None else (None, None)
+        return dict(mean=mean, std=std, group_mean=gm, group_std=gs, clamp_min=self.clamp_min, truth_min=self.truth_min,
+                    min_s=self.min_s)
+
+    def collect_scaled(self, pred, y, y_start: int = 0, mean=None, std=None, label_start=None):
+        """One batch of point forecasts: arguments as ``DeviceEvaluator.collect_scaled``."""
+        self._metric_sums = metric_sums_nodes(pred, y, y_start, label_start=label_start, sums=self._metric_sums,
+                                              **self._scale(mean, std))
+
+    def collect_samples(self, samples, y, y_start: int = 0, mean=None, std=None, label_start=None):
+        """One batch of an ensemble: arguments as ``ProbabilisticEvaluator.collect_samples`` (mean / std may be per node)."""
+        if self.probs is None:
+            raise RuntimeError("this evaluator was built without probs: no probabilistic scores")
+        self._score_sums = mc_scores_nodes(samples, y, self.probs, y_start, null_val=self.null_val,
+                                           label_start=label_start, sums=self._score_sums, **self._scale(mean, std))
+
+    def _need(self, sums, what):
+        if sums is None:
+            raise RuntimeError("nothing collected: call %s first" % what)
+        return sums
+
+    # ---- the ten metrics (column order ALLOWED_METRICS), float64 CPU tensors
+    def node_horizon_table(self) -> torch.Tensor:
+        """(out, N, 10)"""
+        s = self._need(self._metric_sums, "collect_scaled")
+        return metric_table_rows(s, 1, self.swap_r2).reshape(s.shape[0], s.shape[1], -1).cpu()
+
+    def node_table(self) -> torch.Tensor:
+        """(N, 10): every node over all horizons"""
+        s = self._need(self._metric_sums, "collect_scaled")
+        return metric_table_rows(s, int(s.shape[0]), self.swap_r2).cpu()
+
+    def horizon_table(self) -> torch.Tensor:
+        """(out, 10): every horizon over all nodes, the nodes' sums added in ascending node order"""
+        s = self._need(self._metric_sums, "collect_scaled")
+        return metric_table_rows(s.transpose(0, 1).contiguous(), int(s.shape[1]), self.swap_r2).cpu()
+
+    # ---- the probabilistic scores (column order score_columns), float64 CPU tensors, NaN where nothing was counted
+    @staticmethod
+    def _ratios(s):
+        count = s[..., :1]
+        return torch.where(count > 0, s[..., 1:] / count, torch.full_like(s[..., 1:], float("nan")))
+
+    def node_horizon_scores(self) -> torch.Tensor:
+        """(out, N, 4 + levels)"""
+        return self._ratios(self._need(self._score_sums, "collect_samples").cpu())
+
+    def node_scores(self) -> torch.Tensor:
+        """(N, 4 + levels)"""
+        return self._ratios(self._need(self._score_sums, "collect_samples").cpu().sum(0))
+
+    def horizon_scores(self) -> torch.Tensor:
+        """(out, 4 + levels)"""
+        return self._ratios(self._need(self._score_sums, "collect_samples").cpu().sum(1))
+
+    def rank(self, metric: str = "MAPE") -> torch.Tensor:
+        """Node indices by ``metric`` of ``node_table`` in ascending order (ties by index), nodes without a kept element
+        - absent from the reference's groupby - and NaN values last: the ranking of result_plot.py:128."""
+        if metric not in ALLOWED_METRICS:
+            raise ValueError("the metric {} is not allowed in TrafficStateEvaluator".format(str(metric)))
+        values = self.node_table()[:, ALLOWED_METRICS.index(metric)].clone()
+        values[self._metric_sums[:, :, 0].cpu().sum(0) == 0] = float("nan")
+        nan = torch.isnan(values)
+        order = torch.argsort(torch.where(nan, torch.full_like(values, float("inf")), values), stable=True)
+        return torch.cat([order[~nan[order]], order[nan[order]]])
 
 
 def groupstd_table(pred, y, group_mean, group_std, y_start: int = 0, mean=None, std=None, label_start=None,

@@ -24,8 +24,8 @@ import torch.nn as nn
 
 from . import graph_prep
 from . import hidden_pad
-from .ops import (HotPath, PathSpec, diagonal_mask, masked_mae_device, masked_mae_loss, mc_quantiles, mc_scores,
-                  spec_from_config)
+from .ops import (HotPath, PathSpec, diagonal_mask, masked_mae_device, masked_mae_loss, mc_quantiles, mc_quantiles_scaled,
+                  mc_scores, spec_from_config)
 
 try:  # inside a LibCity checkout: subclass the real plugin base so isinstance checks hold
     from libcity.model.abstract_traffic_state_model import AbstractTrafficStateModel  # type: ignore
@@ -439,13 +439,24 @@ class MultiATGCN(AbstractTrafficStateModel):
             return hp.forward_mc(source, h0, seed=seed, offset=offset, p=DROPOUT_P, samples=samples,
                                  keep_samples=keep_samples)
 
-    def predict_interval(self, batch, samples: int = 32, probs=(0.05, 0.5, 0.95), seed: Optional[int] = None):
+    def predict_interval(self, batch, samples: int = 32, probs=(0.05, 0.5, 0.95), seed: Optional[int] = None,
+                         group_mean=None, group_std=None, clamp_min: Optional[float] = None):
         """Monte-Carlo-dropout forecast with its empirical band: (mean, std, quantiles) in the units of ``predict`` -
         mean and std what ``predict_mc`` gives for the same seed, quantiles (len(probs), B, out, N, od) the levels
         ``probs`` (up to 8, ascending, in [0, 1]) of the ``samples`` forecasts per output element, numpy's "linear" rule
-        (matgcn_mc_quantiles).  Window and resident-series batches; seed as in ``predict_mc``."""
+        (matgcn_mc_quantiles).  Window and resident-series batches; seed as in ``predict_mc``.
+        With ``group_mean`` / ``group_std`` (one value per node, a pair) or ``clamp_min`` the band alone moves to the
+        re-transformed scale: every sample goes through the scaler's inverse, then x * group_std + group_mean, and is
+        set to ``clamp_min`` where below it, before the quantiles are taken (matgcn_mc_quantiles_scaled; needs an affine
+        scaler) - the band in visits."""
         mean, std, kept = self.predict_mc(batch, samples=samples, seed=seed, keep_samples=True)
-        return mean, std, mc_quantiles(kept, probs)
+        if group_mean is None and group_std is None and clamp_min is None:
+            return mean, std, mc_quantiles(kept, probs)
+        affine = self._affine_scaler()
+        if affine is None:
+            raise NotImplementedError("a re-transformed band needs an affine scaler (StandardScaler / NoneScaler)")
+        return mean, std, mc_quantiles_scaled(kept, probs, affine[0], affine[1], group_mean, group_std,
+                                              float("nan") if clamp_min is None else clamp_min)
 
     def score_mc(self, batch, samples: int = 32, probs=(0.05, 0.5, 0.95), seed: Optional[int] = None, sums=None):
         """The (out, 5 + len(probs)) float64 per-horizon sums [count, CRPS, covered, width, Winkler, pinball per level] of
@@ -462,6 +473,21 @@ class MultiATGCN(AbstractTrafficStateModel):
             return mc_scores(kept, src[0], probs, self.start_dim, affine[0], affine[1], null_val=0.0,
                              label_start=src[1], sums=sums)
         return mc_scores(kept, batch["y"], probs, self.start_dim, affine[0], affine[1], null_val=0.0, sums=sums)
+
+    def score_mc_nodes(self, batch, evaluator, samples: int = 32, seed: Optional[int] = None):
+        """``score_mc`` per node: one Monte-Carlo-dropout ensemble of the batch reduced into ``evaluator``
+        (evaluator.NodeEvaluator built with ``probs``) - its scores per (horizon, node), on the evaluator's scale
+        (matgcn_mc_scores_nodes).  Window and resident-series batches.  Returns the samples (S, B, out, N, od), scaled."""
+        affine = self._affine_scaler()
+        if affine is None:
+            raise NotImplementedError("score_mc_nodes needs an affine scaler (StandardScaler / NoneScaler)")
+        kept = self.predict_mc(batch, samples=samples, seed=seed, keep_samples=True)[2]
+        if _is_series_batch(batch):
+            src = self._batch_source(batch)
+            evaluator.collect_samples(kept, src[0], self.start_dim, affine[0], affine[1], label_start=src[1])
+        else:
+            evaluator.collect_samples(kept, batch["y"], self.start_dim, affine[0], affine[1])
+        return kept
 
     # ---- the same surface fed from the device-resident raw series (no windows, no labels materialised) ----------
     def _batch_source(self, batch):
@@ -583,6 +609,11 @@ class MultiATGCN(AbstractTrafficStateModel):
             pred = self.predict(batch)
             evaluator.collect_scaled(pred, batch["y"], self.start_dim, affine[0], affine[1])
         return pred
+
+    def collect_node_metrics(self, evaluator, batch):
+        """``collect_metrics`` per node: the same batch reduced into an evaluator.NodeEvaluator - the ten metrics per
+        (horizon, node) on its scale (matgcn_metric_sums_nodes).  Returns the prediction (scaled)."""
+        return self.collect_metrics(evaluator, batch)
 
     def gradient_exchange(self):
         """(bucket, leftovers) for the gradient exchange of data-parallel training after ``loss.backward()``:

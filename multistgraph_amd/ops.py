@@ -239,6 +239,29 @@ def _affine_arg(v, n, device, name):
     return t.contiguous(), int(t.numel() == n and n > 1)
 
 
+def _metric_scale(n, device, mean, std, group_mean, group_std, clamp_min, truth_min, min_s):
+    """(matgcn_metric_scale, the device tensors its pointers refer to - keep them alive across the call)"""
+    sc = _lib.MetricScale()
+    keep = []
+    if (mean is None) != (std is None) or (group_mean is None) != (group_std is None):
+        raise _lib.MatgcnError("mean / std (and group_mean / group_std) come in pairs")
+    if mean is not None:
+        m, pn = _affine_arg(mean, n, device, "mean")
+        sd, pn2 = _affine_arg(std, n, device, "std")
+        if pn != pn2:       # broadcast the scalar one
+            m, sd = (m.expand(n).contiguous() if not pn else m), (sd.expand(n).contiguous() if not pn2 else sd)
+        keep += [m, sd]
+        sc.mean, sc.std, sc.per_node = m.data_ptr(), sd.data_ptr(), int(pn or pn2)
+    if group_mean is not None:
+        gm, _ = _affine_arg(group_mean, n, device, "group_mean")
+        gs, _ = _affine_arg(group_std, n, device, "group_std")
+        gm, gs = gm.expand(n).contiguous(), gs.expand(n).contiguous()
+        keep += [gm, gs]
+        sc.mean2, sc.std2 = gm.data_ptr(), gs.data_ptr()
+    sc.clamp_min, sc.truth_min, sc.min_s = float(clamp_min), float(truth_min), float(min_s)
+    return sc, keep
+
+
 def metric_sums(pred: torch.Tensor, y: torch.Tensor, y_start: int = 0, mean=None, std=None, group_mean=None,
                 group_std=None, clamp_min: float = float("nan"), truth_min: float = float("nan"), min_s: float = 1e-4,
                 label_start: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -250,24 +273,7 @@ def metric_sums(pred: torch.Tensor, y: torch.Tensor, y_start: int = 0, mean=None
     pred = _check_tensor(pred, "pred")
     b, out, n, od = pred.shape
     y, label_start, y_steps, y_feat = _label_geometry(pred, y, label_start)
-    sc = _lib.MetricScale()
-    keep = []
-    if (mean is None) != (std is None) or (group_mean is None) != (group_std is None):
-        raise _lib.MatgcnError("mean / std (and group_mean / group_std) come in pairs")
-    if mean is not None:
-        m, pn = _affine_arg(mean, n, pred.device, "mean")
-        sd, pn2 = _affine_arg(std, n, pred.device, "std")
-        if pn != pn2:       # broadcast the scalar one
-            m, sd = (m.expand(n).contiguous() if not pn else m), (sd.expand(n).contiguous() if not pn2 else sd)
-        keep += [m, sd]
-        sc.mean, sc.std, sc.per_node = m.data_ptr(), sd.data_ptr(), int(pn or pn2)
-    if group_mean is not None:
-        gm, _ = _affine_arg(group_mean, n, pred.device, "group_mean")
-        gs, _ = _affine_arg(group_std, n, pred.device, "group_std")
-        gm, gs = gm.expand(n).contiguous(), gs.expand(n).contiguous()
-        keep += [gm, gs]
-        sc.mean2, sc.std2 = gm.data_ptr(), gs.data_ptr()
-    sc.clamp_min, sc.truth_min, sc.min_s = float(clamp_min), float(truth_min), float(min_s)
+    sc, keep = _metric_scale(n, pred.device, mean, std, group_mean, group_std, clamp_min, truth_min, min_s)
     partials = torch.empty(b * out * _lib.METRIC_SUMS, dtype=torch.float64, device=pred.device)
     accumulate = sums is not None
     if sums is None:
@@ -291,6 +297,60 @@ def metric_table(sums: torch.Tensor, swap_r2: bool = False) -> torch.Tensor:
     stream = C.c_void_p(torch.cuda.current_stream(sums.device).cuda_stream)
     _lib.check(_lib.load().matgcn_metric_table(C.c_void_p(sums.data_ptr()), out, int(bool(swap_r2)),
                                                C.c_void_p(table.data_ptr()), stream), "matgcn_metric_table")
+    return table
+
+
+def _sums_arg(sums, shape, device):
+    """(sums to write, accumulate flag): a fresh tensor, or the caller's running sums after a check"""
+    if sums is None:
+        return torch.empty(shape, dtype=torch.float64, device=device), 0
+    if tuple(sums.shape) != tuple(shape) or sums.dtype != torch.float64 or not sums.is_cuda or not sums.is_contiguous():
+        raise _lib.MatgcnError("sums must be a contiguous CUDA float64 tensor of shape %s" % (tuple(shape),))
+    return sums, 1
+
+
+def metric_sums_nodes(pred: torch.Tensor, y: torch.Tensor, y_start: int = 0, mean=None, std=None, group_mean=None,
+                      group_std=None, clamp_min: float = float("nan"), truth_min: float = float("nan"),
+                      min_s: float = 1e-4, label_start: Optional[torch.Tensor] = None,
+                      sums: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(out, N, 14) float64 device tensor: the sums of ``metric_sums`` per horizon AND node (matgcn_metric_sums_nodes),
+    every entry added up over batch and channel in a fixed order - feeding a test set batch by batch through ``sums``
+    gives the bits of one call over all of it."""
+    lib = _lib.load()
+    pred = _check_tensor(pred, "pred")
+    if pred.dim() != 4:
+        raise _lib.MatgcnError("pred has shape %s, expected (B, out, N, od)" % (tuple(pred.shape),))
+    b, out, n, od = (int(v) for v in pred.shape)
+    y, label_start, y_steps, y_feat = _label_geometry(pred, y, label_start)
+    sc, keep = _metric_scale(n, pred.device, mean, std, group_mean, group_std, clamp_min, truth_min, min_s)
+    need = C.c_size_t(0)
+    _lib.check(lib.matgcn_metric_sums_nodes_bytes(b, out, n, od, C.byref(need)), "matgcn_metric_sums_nodes_bytes")
+    scratch = torch.empty(need.value // 8, dtype=torch.float64, device=pred.device) if need.value else None
+    sums, accumulate = _sums_arg(sums, (out, n, _lib.METRIC_SUMS), pred.device)
+    stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
+    _lib.check(lib.matgcn_metric_sums_nodes(C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()),
+                                            C.c_void_p(_ptr(label_start)), b, out, n, od, y_steps, y_feat, int(y_start),
+                                            C.byref(sc), C.c_void_p(_ptr(scratch)), C.c_size_t(need.value),
+                                            C.c_void_p(sums.data_ptr()), accumulate, stream), "matgcn_metric_sums_nodes")
+    del keep
+    return sums
+
+
+def metric_table_rows(sums: torch.Tensor, fold: int = 1, swap_r2: bool = False) -> torch.Tensor:
+    """(rows, 10) float64 device tensor from metric sums (..., 14) whose leading axes flatten to fold * rows: row r is
+    the table of sum_{f < fold} sums[f * rows + r] (matgcn_metric_table_rows) - ``fold`` = 1 on (out, N, 14) sums: one
+    row per (horizon, node); ``fold`` = out: one row per node over all horizons.  Metric order _lib.METRICS."""
+    if not sums.is_cuda or sums.dtype != torch.float64 or sums.dim() < 2 or sums.shape[-1] != _lib.METRIC_SUMS:
+        raise _lib.MatgcnError("sums must be a CUDA float64 tensor of shape (..., %d)" % _lib.METRIC_SUMS)
+    sums = sums.contiguous()
+    total, fold = sums.numel() // _lib.METRIC_SUMS, int(fold)
+    if fold < 1 or total < 1 or total % fold:
+        raise _lib.MatgcnError("fold = %d does not divide the %d rows of sums" % (fold, total))
+    rows = total // fold
+    table = torch.empty(rows, len(_lib.METRICS), dtype=torch.float64, device=sums.device)
+    stream = C.c_void_p(torch.cuda.current_stream(sums.device).cuda_stream)
+    _lib.check(_lib.load().matgcn_metric_table_rows(C.c_void_p(sums.data_ptr()), rows, fold, int(bool(swap_r2)),
+                                                    C.c_void_p(table.data_ptr()), stream), "matgcn_metric_table_rows")
     return table
 
 
@@ -360,6 +420,61 @@ def mc_scores(samples: torch.Tensor, y: torch.Tensor, probs: Sequence[float], y_
                                     float(mean), float(std), float(null_val), float(min_s), levels, nq,
                                     C.c_void_p(scratch.data_ptr()), C.c_size_t(scratch.numel() * 8),
                                     C.c_void_p(sums.data_ptr()), int(accumulate), stream), "matgcn_mc_scores")
+    return sums
+
+
+def mc_quantiles_scaled(samples: torch.Tensor, probs: Sequence[float], mean=None, std=None, group_mean=None,
+                        group_std=None, clamp_min: float = float("nan")) -> torch.Tensor:
+    """``mc_quantiles`` on the re-transformed scale (matgcn_mc_quantiles_scaled): ``samples`` (S, ..., N, od), every
+    sample de-scaled by mean / std (scalars or one pair per node), then by the per-node group_mean / group_std, and set
+    to ``clamp_min`` where below it, before the sort.  Returns (len(probs), *samples.shape[1:])."""
+    lib = _lib.load()
+    samples = _mc_samples(samples)
+    if samples.dim() < 3:
+        raise _lib.MatgcnError("samples has shape %s, expected (S, ..., N, od)" % (tuple(samples.shape),))
+    levels, nq = _mc_probs(probs)
+    s, elems, n, od = int(samples.shape[0]), samples[0].numel(), int(samples.shape[-2]), int(samples.shape[-1])
+    sc, keep = _metric_scale(n, samples.device, mean, std, group_mean, group_std, clamp_min, float("nan"), -1.0)
+    out = torch.empty((nq,) + tuple(samples.shape[1:]), dtype=torch.float32, device=samples.device)
+    stream = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
+    _lib.check(lib.matgcn_mc_quantiles_scaled(C.c_void_p(samples.data_ptr()), s, elems, n, od, levels, nq, C.byref(sc),
+                                              C.c_void_p(out.data_ptr()), stream), "matgcn_mc_quantiles_scaled")
+    del keep
+    return out
+
+
+def mc_scores_nodes(samples: torch.Tensor, y: torch.Tensor, probs: Sequence[float], y_start: int = 0, mean=None,
+                    std=None, group_mean=None, group_std=None, clamp_min: float = float("nan"),
+                    truth_min: float = float("nan"), null_val: float = 0.0, min_s: float = 1e-4,
+                    label_start: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(out, N, 5 + len(probs)) float64 device tensor: the sums of ``mc_scores`` per horizon AND node, on the scale of
+    ``metric_sums_nodes`` (matgcn_mc_scores_nodes) - samples and labels de-scaled by mean / std and the per-node
+    group_mean / group_std, samples clamped from below before the sort, labels <= ``truth_min`` left out.  Fixed order
+    of summation: feeding batches through ``sums`` gives the bits of one call over all of them."""
+    lib = _lib.load()
+    samples = _mc_samples(samples)
+    if samples.dim() != 5:
+        raise _lib.MatgcnError("samples has shape %s, expected (S, B, out, N, od)" % (tuple(samples.shape),))
+    s, b, out, n, od = (int(v) for v in samples.shape)
+    y, label_start, y_steps, y_feat = _label_geometry(samples[0], y, label_start)
+    levels, nq = _mc_probs(probs)
+    sc, keep = _metric_scale(n, samples.device, mean, std, group_mean, group_std, clamp_min, truth_min, min_s)
+    need = C.c_size_t(0)
+    _lib.check(lib.matgcn_mc_scores_nodes_bytes(b, out, n, od, s, nq, C.byref(need)), "matgcn_mc_scores_nodes_bytes")
+    key = ("nodes", samples.device, b, out, n, od, s, nq)
+    scratch = _mc_scratch.get(key)
+    if scratch is None:
+        if len(_mc_scratch) >= 16:
+            _mc_scratch.clear()
+        scratch = _mc_scratch[key] = torch.empty(max(1, need.value // 8), dtype=torch.float64, device=samples.device)
+    sums, accumulate = _sums_arg(sums, (out, n, _lib.MC_SCORE_SUMS + nq), samples.device)
+    stream = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
+    _lib.check(lib.matgcn_mc_scores_nodes(C.c_void_p(samples.data_ptr()), s, C.c_void_p(y.data_ptr()),
+                                          C.c_void_p(_ptr(label_start)), b, out, n, od, y_steps, y_feat, int(y_start),
+                                          C.byref(sc), float(null_val), levels, nq, C.c_void_p(scratch.data_ptr()),
+                                          C.c_size_t(scratch.numel() * 8), C.c_void_p(sums.data_ptr()), accumulate,
+                                          stream), "matgcn_mc_scores_nodes")
+    del keep
     return sums
 
 
