@@ -48,6 +48,9 @@
  * matgcn_metric_sums_nodes, matgcn_metric_table_rows, matgcn_mc_quantiles_scaled, matgcn_mc_scores_nodes_bytes and
  * matgcn_mc_scores_nodes; no existing symbol, signature, struct or value changed, and no existing entry point launches
  * anything else than it did, with other arguments or other bits.
+ * Still ABI 12: new names only - the training objectives add the enum MATGCN_LOSS_*, the struct matgcn_loss_desc and the
+ * functions matgcn_loss_bytes, matgcn_loss and matgcn_loss_grad; matgcn_masked_mae / matgcn_masked_mae_grad are what they
+ * were, and no existing symbol, signature, struct or value changed.
  */
 #ifndef MATGCN_H
 #define MATGCN_H
@@ -268,6 +271,57 @@ int matgcn_masked_mae_grad(const float* pred, const float* y, const int32_t* lab
                            int nodes, int out_dim, int y_steps, int y_feat, int y_start, float mean, float std,
                            float null_val, float min_s, const float* partials, const float* upstream, float* d_pred,
                            void* stream);
+
+/* ---- the executor's training objectives, value and gradient (matgcn_loss.hip) ---------------------------------------
+ * TrafficStateExecutor._build_train_loss (libcity/executor/traffic_state_executor.py:200-250) offers eleven
+ * differentiable objectives; they are seven kinds here (the `masked_*` names are the first four with null_val = 0):
+ *   MAE, MSE, RMSE, MAPE   loss.masked_{mae,mse,rmse,mape}_torch (libcity/model/loss.py:17-90) - the MASKED kinds:
+ *                          l := 0 where |l| < min_s;  m = (l != null_val) [null_val NaN: m = !isnan(l)];
+ *                          value = sum(t*m) / sum(m);  a term that is NaN after masking adds 0 and gets gradient 0, an
+ *                          infinite one stays infinite (MAPE on an unmasked zero label), nothing kept gives 0.
+ *   LOGCOSH, HUBER, QUANTILE   loss.log_cosh_loss, huber_loss, quantile_loss (loss.py:32-51): the plain mean over all
+ *                          B*out*N*od elements - no min_s, no mask (both fields ignored); a NaN label makes the value NaN.
+ * With l = y*std + mean, p = pred*std + mean (two fp32 roundings each, like the reference's tensors), d = p - l (fp32):
+ *   kind       term t                                               g = dt/dp
+ *   MAE        |d|                                                  sign(d), 0 at 0
+ *   MSE        d^2                                                  2 d
+ *   RMSE       as MSE; the value is sqrt(mse)                       2 d / (2 rmse); ALL gradients 0 when rmse == 0
+ *                                                                   (torch divides 0 by 0 there and gives NaN)
+ *   MAPE       |d / l|                                              sign(d) / |l|
+ *   LOGCOSH    |d| + log1p(exp(-2|d|)) - ln 2                       tanh(d)
+ *   HUBER      0.5 d^2 if |d| <= delta else delta |d| - 0.5 delta^2  d if |d| <= delta else delta sign(d)
+ *   QUANTILE   delta (l - p) if l >= p else (1 - delta)(p - l)      -delta if l >= p else 1 - delta
+ * LOGCOSH is the one deliberate departure from the reference's float32 bits: its log(cosh(d)) overflows to inf in float32
+ * once |d| passes about 89, which de-scaled visit counts do routinely; the form above is the same function and stays finite.
+ * Terms, sums, quotient and square root are fp64 and every result is rounded to float32 once:
+ *   result[0] = the objective over all horizons (what the executor trains on), result[1 + k] = the same over horizon k.
+ * Geometry arguments as the masked-MAE pair above (label_start != NULL: y is the raw series; out_steps in 1 .. 64).
+ * scratch: caller-owned device memory of the size the bytes query below reports - two doubles (term sum, count) per
+ * (b, horizon) slab from stage 1, then the count over all horizons and the fp64 mse, which stage 2 keeps for the gradient;
+ * every word read is written first by the same call.  Two launches, fixed summation order, no atomics: two calls give the
+ * same bits.  The gradient call - d_pred (B, out, N, od) = upstream[0] * std * g * m / count, formed in fp64 and rounded
+ * once - takes the scratch its value call left (the unmasked kinds read nothing from it: their count is the element
+ * count) and the same geometry and descriptor; `upstream` is the device scalar autograd hands down.
+ * Every argument is checked on the host before any launch: a kind outside the enum, a delta that is not finite, a
+ * QUANTILE delta outside (0, 1) or a HUBER delta <= 0 is MATGCN_ERR_BAD_ARG (delta is ignored by the other kinds only in
+ * the arithmetic), a short scratch MATGCN_ERR_SMALL_BUFFER, index spaces of 2^31 or more MATGCN_ERR_UNSUPPORTED.  Nothing
+ * is allocated; only the caller's stream is used. */
+enum { MATGCN_LOSS_MAE = 0, MATGCN_LOSS_MSE, MATGCN_LOSS_RMSE, MATGCN_LOSS_MAPE,
+       MATGCN_LOSS_LOGCOSH, MATGCN_LOSS_HUBER, MATGCN_LOSS_QUANTILE };
+typedef struct matgcn_loss_desc {
+  int32_t kind;       /* MATGCN_LOSS_* */
+  float mean, std;    /* the scaler's affine x*std + mean */
+  float null_val;     /* MASKED kinds: the label value left out (NaN: NaN labels) */
+  float min_s;        /* MASKED kinds: |l| < min_s -> 0 */
+  float delta;        /* HUBER: the knee (> 0); QUANTILE: the level (0 < delta < 1); finite for every kind */
+} matgcn_loss_desc;
+int matgcn_loss_bytes(int batch, int out_steps, size_t* bytes);
+int matgcn_loss(const float* pred, const float* y, const int32_t* label_start, int batch, int out_steps, int nodes,
+                int out_dim, int y_steps, int y_feat, int y_start, const matgcn_loss_desc* desc, void* scratch,
+                size_t scratch_bytes, float* result /* 1 + out_steps */, void* stream);
+int matgcn_loss_grad(const float* pred, const float* y, const int32_t* label_start, int batch, int out_steps, int nodes,
+                     int out_dim, int y_steps, int y_feat, int y_start, const matgcn_loss_desc* desc, const void* scratch,
+                     size_t scratch_bytes, const float* upstream, float* d_pred, void* stream);
 
 /* ---- the evaluator's metric table on the device ------------------------------------
  * TrafficStateEvaluator.collect (libcity/evaluator/traffic_state_evaluator.py:34-121: ten metrics per horizon, modes

@@ -93,8 +93,17 @@ class MetricScale(C.Structure):
                 ("std2", C.c_void_p), ("clamp_min", C.c_float), ("truth_min", C.c_float), ("min_s", C.c_float)]
 
 
+class LossDesc(C.Structure):
+    """matgcn_loss_desc: one training objective (kind, the scaler's affine, mask rule, delta)"""
+    _fields_ = [("kind", C.c_int32), ("mean", C.c_float), ("std", C.c_float), ("null_val", C.c_float),
+                ("min_s", C.c_float), ("delta", C.c_float)]
+
+
+# MATGCN_LOSS_*: the first four are the masked kinds (loss.masked_*_torch)
+LOSS_MAE, LOSS_MSE, LOSS_RMSE, LOSS_MAPE, LOSS_LOGCOSH, LOSS_HUBER, LOSS_QUANTILE = range(7)
+
 METRIC_SUMS = 14
-METRICS = ("MAE", "MAPE", "MSE", "RMSE", "masked_MAE", "masked_MAPE", "masked_MSE", "masked_RMSE", "R2", "EVAR")
+METRICS =("MAE", "MAPE", "MSE", "RMSE", "masked_MAE", "masked_MAPE", "masked_MSE", "masked_RMSE", "R2", "EVAR")
 
 # every symbol include/matgcn.h declares, with its argument types
 _P = C.c_void_p
@@ -124,6 +133,11 @@ _SIGNATURES = {
                                     C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
     "matgcn_masked_mae_grad": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P]),
+    "matgcn_loss_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "matgcn_loss": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                              C.POINTER(LossDesc), _P, C.c_size_t, _P, _P]),
+    "matgcn_loss_grad": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.POINTER(LossDesc), _P, C.c_size_t, _P, _P, _P]),
     "matgcn_metric_sums": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(MetricScale), _P, _P, C.c_int, _P]),
     "matgcn_metric_table": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),

@@ -19,6 +19,7 @@
 #include "matgcn_bwd_kernels.hip"
 #include "matgcn_mc_scores.hip"
 #include "matgcn_optim.hip"
+#include "matgcn_loss.hip"
 
 namespace {
 
@@ -1328,6 +1329,85 @@ int matgcn_masked_mae_grad(const float* pred, const float* y, const int32_t* lab
   hipLaunchKernelGGL(k_mae_grad, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, pred, y, label_start,
                      out_steps, nodes, out_dim, y_steps, y_feat, y_start, mean, std, null_val, min_s,
                      partials + 2 * (size_t)batch * out_steps, upstream, total, d_pred);
+  return launch_ok();
+}
+
+// ---- the executor's training objectives (matgcn_loss.hip) ---------------------------------------------------------------
+namespace {
+int loss_check(int batch, int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start,
+               const matgcn_loss_desc* desc, size_t scratch_bytes, LossArgs* a) {
+  size_t need = 0;
+  RETURN_IF(matgcn_loss_bytes(batch, out_steps, &need));
+  if (nodes < 1 || out_dim < 1 || y_steps < out_steps || y_start < 0 || y_start + (long)out_dim > y_feat)
+    return MATGCN_ERR_BAD_ARG;
+  if (desc->kind < MATGCN_LOSS_MAE || desc->kind > MATGCN_LOSS_QUANTILE) return MATGCN_ERR_BAD_ARG;
+  const float dl = desc->delta;
+  if (!(dl - dl == 0.f)) return MATGCN_ERR_BAD_ARG;                                  // inf and NaN
+  if (desc->kind == MATGCN_LOSS_QUANTILE && !(dl > 0.f && dl < 1.f)) return MATGCN_ERR_BAD_ARG;
+  if (desc->kind == MATGCN_LOSS_HUBER && !(dl > 0.f)) return MATGCN_ERR_BAD_ARG;
+  if ((long)nodes * out_dim >= (1L << 31)) return MATGCN_ERR_UNSUPPORTED;
+  if (((long)batch * out_steps * nodes * out_dim + 255) / 256 >= (1L << 31)) return MATGCN_ERR_UNSUPPORTED;
+  if (scratch_bytes < need) return MATGCN_ERR_SMALL_BUFFER;
+  a->outSteps = out_steps; a->N = nodes; a->od = out_dim; a->ySteps = y_steps; a->yFeat = y_feat; a->yStart = y_start;
+  a->mean = desc->mean; a->std = desc->std; a->nullVal = desc->null_val; a->minS = desc->min_s; a->delta = dl;
+  return MATGCN_OK;
+}
+}  // namespace
+
+// the kernels of kind K: the first four kinds are the masked ones
+#define LOSS_KIND_SWITCH(kind, WHAT)                       \
+  switch (kind) {                                          \
+    case MATGCN_LOSS_MAE: WHAT(MATGCN_LOSS_MAE, 1) break;           \
+    case MATGCN_LOSS_MSE: WHAT(MATGCN_LOSS_MSE, 1) break;           \
+    case MATGCN_LOSS_RMSE: WHAT(MATGCN_LOSS_RMSE, 1) break;         \
+    case MATGCN_LOSS_MAPE: WHAT(MATGCN_LOSS_MAPE, 1) break;         \
+    case MATGCN_LOSS_LOGCOSH: WHAT(MATGCN_LOSS_LOGCOSH, 0) break;   \
+    case MATGCN_LOSS_HUBER: WHAT(MATGCN_LOSS_HUBER, 0) break;       \
+    default: WHAT(MATGCN_LOSS_QUANTILE, 0) break;                   \
+  }
+
+int matgcn_loss_bytes(int batch, int out_steps, size_t* bytes) {
+  if (!bytes) return MATGCN_ERR_NULL;
+  if (batch < 1 || out_steps < 1 || out_steps > 64) return MATGCN_ERR_BAD_ARG;
+  if ((long)batch * out_steps >= (1L << 31)) return MATGCN_ERR_UNSUPPORTED;
+  *bytes = (2 * (size_t)batch * out_steps + 2) * sizeof(double);
+  return MATGCN_OK;
+}
+
+int matgcn_loss(const float* pred, const float* y, const int32_t* label_start, int batch, int out_steps, int nodes,
+                int out_dim, int y_steps, int y_feat, int y_start, const matgcn_loss_desc* desc, void* scratch,
+                size_t scratch_bytes, float* result, void* stream) {
+  if (!pred || !y || !desc || !scratch || !result) return MATGCN_ERR_NULL;
+  LossArgs a;
+  RETURN_IF(loss_check(batch, out_steps, nodes, out_dim, y_steps, y_feat, y_start, desc, scratch_bytes, &a));
+  a.pred = pred; a.y = y; a.labelStart = label_start;
+  hipStream_t s = (hipStream_t)stream;
+  double* sc = (double*)scratch;
+  const dim3 slabs((unsigned)(batch * out_steps));
+#define LOSS_PARTIAL(K, M) hipLaunchKernelGGL((k_loss_partial<K, M>), slabs, dim3(LOSS_THREADS), 0, s, a, sc);
+  LOSS_KIND_SWITCH(desc->kind, LOSS_PARTIAL)
+#undef LOSS_PARTIAL
+  CHECK_LAUNCH();
+#define LOSS_FINAL(K, M) hipLaunchKernelGGL((k_loss_final<K>), dim3(1), dim3(64), 0, s, sc, batch, out_steps, result);
+  LOSS_KIND_SWITCH(desc->kind, LOSS_FINAL)
+#undef LOSS_FINAL
+  return launch_ok();
+}
+
+int matgcn_loss_grad(const float* pred, const float* y, const int32_t* label_start, int batch, int out_steps, int nodes,
+                     int out_dim, int y_steps, int y_feat, int y_start, const matgcn_loss_desc* desc, const void* scratch,
+                     size_t scratch_bytes, const float* upstream, float* d_pred, void* stream) {
+  if (!pred || !y || !desc || !scratch || !upstream || !d_pred) return MATGCN_ERR_NULL;
+  LossArgs a;
+  RETURN_IF(loss_check(batch, out_steps, nodes, out_dim, y_steps, y_feat, y_start, desc, scratch_bytes, &a));
+  a.pred = pred; a.y = y; a.labelStart = label_start;
+  const size_t total = (size_t)batch * out_steps * nodes * out_dim;
+  const double* kept = (const double*)scratch + 2 * (size_t)batch * out_steps;
+#define LOSS_GRAD(K, M)                                                                                          \
+  hipLaunchKernelGGL((k_loss_grad<K, M>), dim3(blocks_for(total)), dim3(LOSS_THREADS), 0, (hipStream_t)stream, a, kept, \
+                     upstream, total, d_pred);
+  LOSS_KIND_SWITCH(desc->kind, LOSS_GRAD)
+#undef LOSS_GRAD
   return launch_ok();
 }
 

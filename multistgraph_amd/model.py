@@ -25,7 +25,8 @@ import torch.nn as nn
 from . import graph_prep
 from . import hidden_pad
 from .ops import (HotPath, PathSpec, diagonal_mask, masked_mae_device, masked_mae_loss, mc_quantiles, mc_quantiles_scaled,
-                  mc_scores, spec_from_config)
+                  mc_scores, spec_from_config, train_loss_desc, train_loss_device)
+from .ops import train_loss as train_loss_autograd
 
 try:  # inside a LibCity checkout: subclass the real plugin base so isinstance checks hold
     from libcity.model.abstract_traffic_state_model import AbstractTrafficStateModel  # type: ignore
@@ -208,6 +209,16 @@ class MultiATGCN(AbstractTrafficStateModel):
         if self.hip_dropout not in HIP_DROPOUTS:
             raise ValueError("hip_dropout = %r: expected one of %s" % (self.hip_dropout, ", ".join(HIP_DROPOUTS)))
         self._dropout_counter = 0
+        # config['hip_train_loss']: "none" (default) - calculate_loss / calculate_loss_series are the reference's masked MAE;
+        # one of the executor's eleven differentiable objectives (ops.TRAIN_LOSSES: mae, mse, rmse, mape, logcosh, huber,
+        # quantile, masked_mae, masked_mse, masked_rmse, masked_mape) - both return that objective instead, value and
+        # gradient on the device (matgcn_loss / matgcn_loss_grad), so the reference's executor with `train_loss: none` trains
+        # on it unchanged.  config['hip_train_loss_delta']: huber's knee / quantile's level (None: the reference's defaults,
+        # 1.0 and 0.25).  Attributes like the three above: checkpoints are unchanged.
+        self.hip_train_loss = str(get("hip_train_loss", "none")).lower()
+        self.hip_train_loss_delta = get("hip_train_loss_delta", None)
+        if self.hip_train_loss != "none":
+            train_loss_desc(self.hip_train_loss, 0.0, 1.0, self.hip_train_loss_delta)   # ValueError on a bad name or delta
         self.batch_size = get("batch_size", 64)
         self.device = get("device", torch.device("cpu"))
         config["num_nodes"] = self.num_nodes  # the reference writes this back (:233)
@@ -575,6 +586,8 @@ class MultiATGCN(AbstractTrafficStateModel):
         src = self._series_source(series, label_start, rel_steps, trusted=_checked)
         pred = self._run(src, int(src[1].shape[0]), series.device)
         ls = src[1]
+        if self.hip_train_loss != "none":
+            return self._objective(pred, series, self.hip_train_loss, self.hip_train_loss_delta, ls)
         affine = self._affine_scaler()
         if affine is not None and series.dtype == torch.float32:
             if pred.requires_grad:
@@ -668,6 +681,8 @@ class MultiATGCN(AbstractTrafficStateModel):
             return self.calculate_loss_series(src[0], src[1], src[2], _checked=True)
         y_true = batch["y"]
         y_predicted = self.predict(batch)
+        if self.hip_train_loss != "none":
+            return self._objective(y_predicted, y_true, self.hip_train_loss, self.hip_train_loss_delta)
         affine = self._affine_scaler()
         if affine is not None and y_true.is_cuda and y_true.dtype == torch.float32 and y_predicted.requires_grad:
             return masked_mae_loss(y_predicted, y_true, self.start_dim, affine[0], affine[1], null_val=0.0)
@@ -676,6 +691,32 @@ class MultiATGCN(AbstractTrafficStateModel):
         y_true = self._scaler.inverse_transform(y_true[..., self.start_dim:self.end_dim])
         y_predicted = self._scaler.inverse_transform(y_predicted)
         return masked_mae(y_predicted, y_true, 0)
+
+    def _objective(self, pred, y, name, delta, label_start=None):
+        """the executor's objective ``name`` of a prediction on the device: ``y`` the label windows, or with label_start
+        the resident series; with autograd when the prediction carries a graph"""
+        affine = self._affine_scaler()
+        if affine is None:
+            raise NotImplementedError("train_loss needs an affine scaler (StandardScaler / NoneScaler)")
+        fn = train_loss_autograd if pred.requires_grad else train_loss_device
+        out = fn(pred, y, self.start_dim, affine[0], affine[1], name, delta, label_start)
+        return out if pred.requires_grad else out[0]
+
+    def train_loss(self, batch, name, delta=None):
+        """One of the executor's eleven differentiable training objectives (TrafficStateExecutor._build_train_loss,
+        traffic_state_executor.py:200-250; ops.TRAIN_LOSSES) of a window batch (``X``, ``y``) or a resident-series batch
+        (``series``, ``label_start``): predict, de-scale, mask and reduce in a fixed order on the device (matgcn_loss); with
+        gradients enabled the result backpropagates through matgcn_loss_grad into the HIP backward.  ``delta``: huber's
+        knee / quantile's level (None: 1.0 / 0.25, the reference's defaults).  The label channels start at ``start_dim``,
+        as in calculate_loss."""
+        train_loss_desc(name, 0.0, 1.0, delta)      # refuse a bad name or delta before any kernel runs
+        if self._affine_scaler() is None:
+            raise NotImplementedError("train_loss needs an affine scaler (StandardScaler / NoneScaler)")
+        if _is_series_batch(batch):
+            src = self._batch_source(batch)
+            pred = self._run(src, int(src[1].shape[0]), src[0].device)
+            return self._objective(pred, src[0], name, delta, src[1])
+        return self._objective(self.predict(batch), batch["y"], name, delta)
 
     def horizon_mae(self, batch):
         """(out,) device tensor MAE@1..MAE@out in the evaluator's "single" mode on de-scaled values

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
@@ -229,6 +230,99 @@ def masked_mae_loss(pred: torch.Tensor, y: torch.Tensor, y_start: int, mean: flo
     """The calculate_loss scalar with autograd support: the device reduction forward, matgcn_masked_mae_grad backward.
     With label_start, y is the raw series and the targets are gathered on the device."""
     return _MaskedMAE.apply(pred, y, y_start, mean, std, null_val, min_s, label_start)
+
+
+# The executor's differentiable training objectives (TrafficStateExecutor._build_train_loss, traffic_state_executor.py:
+# 200-250): name -> (kind, null_val, default delta).  mae / mse / rmse / mape are loss.masked_*_torch with their default
+# null value NaN, the masked_* names the same functions with null_val = 0; logcosh / huber / quantile are plain means.
+_NAN = float("nan")
+TRAIN_LOSSES = {
+    "mae": (_lib.LOSS_MAE, _NAN, 0.0), "mse": (_lib.LOSS_MSE, _NAN, 0.0), "rmse": (_lib.LOSS_RMSE, _NAN, 0.0),
+    "mape": (_lib.LOSS_MAPE, _NAN, 0.0),
+    "logcosh": (_lib.LOSS_LOGCOSH, _NAN, 0.0), "huber": (_lib.LOSS_HUBER, _NAN, 1.0),
+    "quantile": (_lib.LOSS_QUANTILE, _NAN, 0.25),
+    "masked_mae": (_lib.LOSS_MAE, 0.0, 0.0), "masked_mse": (_lib.LOSS_MSE, 0.0, 0.0),
+    "masked_rmse": (_lib.LOSS_RMSE, 0.0, 0.0), "masked_mape": (_lib.LOSS_MAPE, 0.0, 0.0),
+}
+TRAIN_LOSS_MIN_S = 1e-4     # loss.masked_*_torch: |label| < min_s -> 0 (the unmasked kinds have no such rule)
+NOT_DIFFERENTIABLE_LOSSES = ("r2", "evar")
+
+
+def train_loss_desc(name: str, mean: float, std: float, delta=None) -> "_lib.LossDesc":
+    """the matgcn_loss_desc of the executor's objective ``name`` (a key of TRAIN_LOSSES)"""
+    key = str(name).lower()
+    if key in NOT_DIFFERENTIABLE_LOSSES:
+        raise ValueError("train loss %r is a CPU sklearn score in the reference (loss.r2_score_torch / "
+                         "explained_variance_score_torch): it is not differentiable and cannot be trained on" % name)
+    if key not in TRAIN_LOSSES:
+        raise ValueError("train loss %r: expected one of %s" % (name, ", ".join(TRAIN_LOSSES)))
+    kind, null_val, default_delta = TRAIN_LOSSES[key]
+    masked = kind <= _lib.LOSS_MAPE
+    delta = float(default_delta if delta is None else delta)
+    if not math.isfinite(delta) or (kind == _lib.LOSS_HUBER and not delta > 0.0) or \
+            (kind == _lib.LOSS_QUANTILE and not 0.0 < delta < 1.0):
+        raise ValueError("train loss %r: delta = %r (huber needs delta > 0, quantile 0 < delta < 1)" % (name, delta))
+    return _lib.LossDesc(kind, float(mean), float(std), null_val, TRAIN_LOSS_MIN_S if masked else 0.0, delta)
+
+
+def _loss_call(pred, y, y_start, desc, label_start=None):
+    lib = _lib.load()
+    pred = _check_tensor(pred, "pred")
+    if pred.dim() != 4:
+        raise _lib.MatgcnError("pred has shape %s, expected (B, out, N, od)" % (tuple(pred.shape),))
+    b, out, n, od = pred.shape
+    y, label_start, y_steps, y_feat = _label_geometry(pred, y, label_start)
+    need = C.c_size_t()
+    _lib.check(lib.matgcn_loss_bytes(b, out, C.byref(need)), "matgcn_loss_bytes")
+    scratch = torch.empty(need.value // 8, dtype=torch.float64, device=pred.device)
+    result = torch.empty(1 + out, dtype=torch.float32, device=pred.device)
+    stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
+    _lib.check(lib.matgcn_loss(C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(label_start)),
+                               b, out, n, od, y_steps, y_feat, int(y_start), C.byref(desc),
+                               C.c_void_p(scratch.data_ptr()), need.value, C.c_void_p(result.data_ptr()), stream),
+               "matgcn_loss")
+    return pred, y, scratch, result, label_start
+
+
+def train_loss_device(pred: torch.Tensor, y: torch.Tensor, y_start: int, mean: float, std: float, name: str,
+                      delta=None, label_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(1 + out,) tensor [the executor's objective ``name`` over all horizons, the same per horizon] computed on the
+    device by matgcn_loss (de-scale + mask + fixed-order reduction).  Geometry as masked_mae_device: ``y`` windows, or
+    with label_start the raw series whose targets are gathered on the device."""
+    return _loss_call(pred, y, y_start, train_loss_desc(name, mean, std, delta), label_start)[3]
+
+
+class _TrainLoss(torch.autograd.Function):
+    """one of the executor's objectives on the device with its gradient (matgcn_loss / matgcn_loss_grad)."""
+
+    @staticmethod
+    def forward(ctx, pred, y, y_start, desc, label_start):
+        pred_c, y_c, scratch, result, ls = _loss_call(pred.detach(), y, y_start, desc, label_start)
+        ctx.save_for_backward(pred_c, y_c, scratch)
+        ctx.label_start, ctx.y_start, ctx.desc = ls, int(y_start), desc
+        return result[0].clone()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        pred, y, scratch = ctx.saved_tensors
+        b, out, n, od = pred.shape
+        ls = ctx.label_start
+        y_steps, y_feat = (int(y.shape[1]), int(y.shape[3])) if ls is None else (int(y.shape[0]), int(y.shape[2]))
+        d_pred = torch.empty_like(pred)
+        up = upstream.detach().to(torch.float32).reshape(1).contiguous()
+        stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
+        _lib.check(_lib.load().matgcn_loss_grad(
+            C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(ls)), b, out, n, od, y_steps, y_feat,
+            ctx.y_start, C.byref(ctx.desc), C.c_void_p(scratch.data_ptr()), scratch.numel() * 8,
+            C.c_void_p(up.data_ptr()), C.c_void_p(d_pred.data_ptr()), stream), "matgcn_loss_grad")
+        return d_pred, None, None, None, None
+
+
+def train_loss(pred: torch.Tensor, y: torch.Tensor, y_start: int, mean: float, std: float, name: str, delta=None,
+               label_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The scalar of the executor's objective ``name`` with autograd support: matgcn_loss forward, matgcn_loss_grad
+    backward.  With label_start, y is the raw series and the targets are gathered on the device."""
+    return _TrainLoss.apply(pred, y, y_start, train_loss_desc(name, mean, std, delta), label_start)
 
 
 def _affine_arg(v, n, device, name):
