@@ -51,6 +51,9 @@
  * Still ABI 12: new names only - the training objectives add the enum MATGCN_LOSS_*, the struct matgcn_loss_desc and the
  * functions matgcn_loss_bytes, matgcn_loss and matgcn_loss_grad; matgcn_masked_mae / matgcn_masked_mae_grad are what they
  * were, and no existing symbol, signature, struct or value changed.
+ * Still ABI 12: new names only - conformal calibration of the Monte-Carlo-dropout band adds the functions
+ * matgcn_mc_conformity, matgcn_conformal_quantile and matgcn_conformal_coverage; no existing symbol, signature, struct or
+ * value changed, and no existing entry point launches anything else than it did.
  */
 #ifndef MATGCN_H
 #define MATGCN_H
@@ -595,6 +598,60 @@ int matgcn_mc_scores_nodes(const float* samples, int n_samples, const float* y, 
                            const matgcn_metric_scale* scale, float null_val, const float* probs /*HOST*/, int n_probs,
                            void* scratch, size_t scratch_bytes, double* sums /* (out_steps, nodes, 5 + n_probs) */,
                            int accumulate, void* stream);
+
+/* ---- split conformal calibration of the band -----------------------------------------------------------------------------
+ * The ensemble carries the head's uncertainty only, so its band [Q_first, Q_last] is too narrow.  Split conformal
+ * calibration widens it by one rank statistic of held-out conformity scores per group, which gives the band's nominal
+ * coverage on exchangeable data without retraining.  Three entry points: the scores of a batch, the margin per group from
+ * a store of scores, and how often a margin held.  Nothing is allocated, no global atomics, no scratch, the caller's
+ * stream only, every argument checked on the host before anything is launched; every result is run-to-run identical.
+ *
+ * matgcn_mc_conformity: arguments as matgcn_mc_scores_nodes (out_steps in 1 .. 64) with `scores` (B, out, N, od) floats
+ * in place of scratch and sums; n_probs >= 2 (fewer is MATGCN_ERR_BAD_ARG).  Tile, sort, quantile rule, de-scaling of
+ * label and samples, clamp, truth_min, min_s and the null_val mask are exactly those of matgcn_mc_scores_nodes.  Per
+ * element the conformalized-quantile-regression score
+ *   s = max(Q_first - l, l - Q_last),   each difference one fp32 rounding
+ * (negative inside the band, 0 on its edge); a masked or filtered element stores a quiet NaN, so EVERY element of
+ * `scores` is written.  Non-finite samples: as above, that element's score is unspecified.  A caller appends batch after
+ * batch into a window-major store (rows_capacity, out, N*od) by passing store + rows_filled*out*N*od.
+ *
+ * matgcn_conformal_quantile: scores is such a store, (rows, out_steps, cols) with cols = N*od; rows beyond rows - 1 are
+ * never read.  grouping 0: one group per horizon (margin, count: out_steps entries); grouping 1: one per (horizon,
+ * column) (out_steps*cols entries).  Group g holds the non-NaN scores of its columns in rows 0 .. rows-1:
+ *   n = their number;   k = max(1, ceil((double)(n + 1) * coverage)), one fp64 product;
+ *   margin[g] = the k-th smallest of them when k <= n, else +inf (n = 0 included);   count[g] = n.
+ * coverage in (0, 1], anything else (NaN included) is MATGCN_ERR_BAD_ARG; a caller calibrating the band of levels q_first,
+ * q_last passes (double)q_last - (double)q_first, the convention of the Winkler score above.  The selection is exact: a
+ * radix select over order-preserving 32-bit keys (u ^ 0xFFFFFFFF for negative floats, u | 0x80000000 otherwise; -0 sorts
+ * before +0), four 8-bit passes over 256-bin histograms in LDS built with LDS integer adds, all four in one launch.
+ * grouping 1: a workgroup owns 64 adjacent columns of one horizon (coalesced row reads, 64 x 256 bins = 64 KB);
+ * grouping 0: one workgroup per horizon walks rows x cols.  Every loop bound is a host-known count and only integer
+ * counts are accumulated, so no input value can change a trip count and no result depends on execution order.
+ * Counts are 32-bit: rows (grouping 1) or rows*cols (grouping 0) of 2^31 - 4096 or more is MATGCN_ERR_UNSUPPORTED.
+ *
+ * matgcn_conformal_coverage: counts (groups, 2) int64 = [n, covered] per group of the same store and grouping, covered =
+ * the non-NaN scores with s <= margin[g], compared in fp32 (a score equal to the margin is covered; under a +inf margin
+ * every valid score is) - the coverage of the calibrated band in the conformal definition.  Overwritten, or added to
+ * when accumulate != 0: a test split streamed batch by batch.  Integer sums only.
+ * Argument checks of the last two: counts >= 1, out_steps in 1 .. 64, grouping in {0, 1}, non-null pointers,
+ * rows*out_steps*cols within int64.
+ * Measured at Baltimore 403 / B = 64 / out = 24 with the re-transform, clamp 0 and truth_min 6 (MI355X,
+ * tools/conformal_time.py, one process, routes alternating three times, median of 20 calls, HIP events; DESIGN.md section
+ * 5d.1): matgcn_mc_conformity 0.137 ms at S = 32 and 0.909 ms at S = 128 (matgcn_mc_scores_nodes 0.176 / 0.979 ms,
+ * torch.sort + the same arithmetic 0.485 / 4.744 ms, same scores); on a store of 540 rows (20.9 MB)
+ * matgcn_conformal_quantile 0.343 ms per horizon (torch.kthvalue per horizon, its rank read back each time: 19.96 ms)
+ * and 0.224 ms per element (torch.sort per group 0.417 ms); matgcn_conformal_coverage over one batch 0.031 / 0.017 ms
+ * (torch compare + sum 0.054 / 0.046 ms).  Every gap is above twice the spread of the visits (at most 0.009 ms). */
+int matgcn_mc_conformity(const float* samples, int n_samples, const float* y, const int32_t* label_start, int batch,
+                         int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start,
+                         const matgcn_metric_scale* scale, float null_val, const float* probs /*HOST*/, int n_probs,
+                         float* scores /* (batch, out_steps, nodes, out_dim) */, void* stream);
+int matgcn_conformal_quantile(const float* scores, int64_t rows, int out_steps, int cols /* N*od */,
+                              int grouping /* 0: per horizon, 1: per (horizon, column) */, double coverage,
+                              float* margin /* (groups) */, int32_t* count /* (groups) */, void* stream);
+int matgcn_conformal_coverage(const float* scores, int64_t rows, int out_steps, int cols, int grouping,
+                              const float* margin /* (groups) */, int64_t* counts /* (groups, 2): n, covered */,
+                              int accumulate, void* stream);
 
 /* ---- the optimizer step: global gradient norm, clip and Adam over a table of tensors -------------------------------------
  * What clip_grad_norm_(params, max_norm) followed by torch.optim.Adam.step() does (no amsgrad, no maximize), as three

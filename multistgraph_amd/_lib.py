@@ -170,6 +170,10 @@ _SIGNATURES = {
     "matgcn_mc_scores_nodes": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.POINTER(MetricScale), C.c_float, C.POINTER(C.c_float), C.c_int, _P,
                                          C.c_size_t, _P, C.c_int, _P]),
+    "matgcn_mc_conformity": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.POINTER(MetricScale), C.c_float, C.POINTER(C.c_float), C.c_int, _P, _P]),
+    "matgcn_conformal_quantile": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P]),
+    "matgcn_conformal_coverage": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
     "matgcn_grad_norm_bytes":(C.c_int, [C.POINTER(OptTensor), C.c_int, C.POINTER(C.c_size_t)]),
     "matgcn_grad_norm": (C.c_int, [C.POINTER(OptTensor), C.c_int, _P, C.c_size_t, _P, _P]),
     "matgcn_adam_step": (C.c_int, [C.POINTER(OptTensor), C.c_int, C.POINTER(Adam), _P, _P]),

@@ -18,6 +18,7 @@
 #include "matgcn_node16.hip"
 #include "matgcn_bwd_kernels.hip"
 #include "matgcn_mc_scores.hip"
+#include "matgcn_conformal.hip"
 #include "matgcn_optim.hip"
 #include "matgcn_loss.hip"
 
@@ -1659,6 +1660,84 @@ int matgcn_mc_scores_nodes(const float* samples, int n_samples, const float* y, 
   CHECK_LAUNCH();
   hipLaunchKernelGGL(k_mc_accumulate_nodes, dim3(blocks_for((size_t)out_steps * nodes * K)), dim3(256), 0, s, a.terms, batch,
                      out_steps, nodes, out_dim, K, accumulate, sums);
+  return launch_ok();
+}
+
+// ---- split conformal calibration of the band (matgcn_conformal.hip) -------------------------------------------------------
+int matgcn_mc_conformity(const float* samples, int n_samples, const float* y, const int32_t* label_start, int batch,
+                         int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start,
+                         const matgcn_metric_scale* scale, float null_val, const float* probs, int n_probs, float* scores,
+                         void* stream) {
+  if (!samples || !y || !probs || !scores) return MATGCN_ERR_NULL;
+  McConformityArgs a;
+  RETURN_IF(mc_scale(scale, &a.sc));
+  if (out_steps > 64 || n_probs < 2) return MATGCN_ERR_BAD_ARG;
+  int tilesPerRow = 0;
+  long blocks = 0;
+  RETURN_IF(mc_score_grid(batch, out_steps, nodes, out_dim, n_samples, &tilesPerRow, &blocks));
+  if (y_steps < 1 || (!label_start && y_steps < out_steps) || y_feat < 1 || y_start < 0 || y_start + out_dim > y_feat)
+    return MATGCN_ERR_BAD_ARG;
+  McLevels all, lv;
+  RETURN_IF(mc_levels(probs, n_probs, n_samples, &all));
+  // the kernel reads the outer two levels only
+  memset(&lv, 0, sizeof(lv));
+  lv.n = 2;
+  const int src[2] = {0, n_probs - 1};
+  for (int k = 0; k < 2; ++k) {
+    lv.lo[k] = all.lo[src[k]]; lv.hi[k] = all.hi[src[k]]; lv.g[k] = all.g[src[k]]; lv.q[k] = all.q[src[k]];
+  }
+  lv.winkler = all.winkler;
+  const McTile t = mc_tile(n_samples);
+  a.samples = samples; a.y = y; a.labelStart = label_start;
+  a.S = n_samples; a.P = t.P; a.logTE = t.logTE;
+  a.outSteps = out_steps; a.N = nodes; a.od = out_dim; a.ySteps = y_steps; a.yFeat = y_feat; a.yStart = y_start;
+  a.tilesPerRow = tilesPerRow;
+  a.E = (long long)batch * out_steps * nodes * out_dim;
+  a.truthMin = scale->truth_min; a.minS = scale->min_s; a.nullVal = null_val;
+  a.scores = scores;
+  hipLaunchKernelGGL(k_mc_conformity, dim3((unsigned)blocks), dim3(256), (size_t)t.ldsBytes, (hipStream_t)stream, a, lv);
+  return launch_ok();
+}
+
+namespace {
+// the store (rows, out_steps, cols) of the two calibration entry points: counts >= 1, out_steps in 1 .. 64, the element
+// count inside int64; what a 32-bit index or count of the kernels cannot hold is MATGCN_ERR_UNSUPPORTED
+int conf_store(int64_t rows, int out_steps, int cols, int grouping) {
+  if (rows < 1 || out_steps < 1 || out_steps > 64 || cols < 1 || (grouping != 0 && grouping != 1)) return MATGCN_ERR_BAD_ARG;
+  const int64_t rowElems = (int64_t)out_steps * cols;                 // < 2^37
+  if (rows > INT64_MAX / rowElems) return MATGCN_ERR_BAD_ARG;
+  const int64_t walk = grouping ? rows : rows * (int64_t)cols;        // what one group's count and row index run over
+  if (rows > INT32_MAX || walk > (int64_t)INT32_MAX - 4 * CONF_ROW_THREADS) return MATGCN_ERR_UNSUPPORTED;
+  return MATGCN_OK;
+}
+}  // namespace
+
+int matgcn_conformal_quantile(const float* scores, int64_t rows, int out_steps, int cols, int grouping, double coverage,
+                              float* margin, int32_t* count, void* stream) {
+  if (!scores || !margin || !count) return MATGCN_ERR_NULL;
+  RETURN_IF(conf_store(rows, out_steps, cols, grouping));
+  if (!(coverage > 0.0 && coverage <= 1.0)) return MATGCN_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (grouping)
+    hipLaunchKernelGGL(k_conformal_select_cols, dim3((unsigned)((cols + CONF_COLS - 1) / CONF_COLS), (unsigned)out_steps),
+                       dim3(256), 0, s, scores, (int)rows, out_steps, cols, coverage, margin, count);
+  else
+    hipLaunchKernelGGL(k_conformal_select_rows, dim3((unsigned)out_steps), dim3(CONF_ROW_THREADS), 0, s, scores, (int)rows,
+                       out_steps, cols, coverage, margin, count);
+  return launch_ok();
+}
+
+int matgcn_conformal_coverage(const float* scores, int64_t rows, int out_steps, int cols, int grouping, const float* margin,
+                              int64_t* counts, int accumulate, void* stream) {
+  if (!scores || !margin || !counts) return MATGCN_ERR_NULL;
+  RETURN_IF(conf_store(rows, out_steps, cols, grouping));
+  hipStream_t s = (hipStream_t)stream;
+  if (grouping)
+    hipLaunchKernelGGL(k_conformal_coverage_cols, dim3(blocks_for((size_t)out_steps * cols)), dim3(256), 0, s, scores,
+                       (int)rows, out_steps, cols, margin, accumulate, (long long*)counts);
+  else
+    hipLaunchKernelGGL(k_conformal_coverage_rows, dim3((unsigned)out_steps), dim3(256), 0, s, scores, (int)rows, out_steps,
+                       cols, margin, accumulate, (long long*)counts);
   return launch_ok();
 }
 

@@ -11,6 +11,10 @@ per-horizon table TrafficStateExecutor.evaluate writes after re-transforming wit
 CRPS, interval coverage and width, the interval (Winkler) score and pinball losses per horizon, accumulated over the
 batches of a test set on the device (matgcn_mc_scores).  The reference has no such evaluator.
 
+``ConformalCalibrator`` makes that ensemble's band mean what its levels say: split conformal calibration from the
+conformity scores of a held-out split, kept, ranked and applied on the device (matgcn_mc_conformity,
+matgcn_conformal_quantile, matgcn_conformal_coverage).
+
 HIP path only: CPU tensors raise.
 """
 from __future__ import annotations
@@ -20,7 +24,8 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib
-from .ops import mc_scores, mc_scores_nodes, metric_sums, metric_sums_nodes, metric_table, metric_table_rows
+from .ops import (conformal_coverage, conformal_quantile, mc_conformity, mc_scores, mc_scores_nodes, metric_sums,
+                  metric_sums_nodes, metric_table, metric_table_rows)
 
 ALLOWED_METRICS = list(_lib.METRICS)
 
@@ -246,6 +251,212 @@ class NodeEvaluator:
         nan = torch.isnan(values)
         order = torch.argsort(torch.where(nan, torch.full_like(values, float("inf")), values), stable=True)
         return torch.cat([order[~nan[order]], order[nan[order]]])
+
+
+def _f32(v) -> float:
+    """the double of the float32 nearest to v: what the kernels see of a level"""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def _same_scalar(a, b) -> bool:
+    """two optional floats, None and NaN both meaning "off" """
+    a = float("nan") if a is None else float(a)
+    b = float("nan") if b is None else float(b)
+    return a == b or (a != a and b != b)
+
+
+def _same_vector(a, b) -> bool:
+    """two optional per-node (or scalar) float32 vectors"""
+    if a is None or b is None:
+        return a is None and b is None
+    a, b = (torch.as_tensor(v, dtype=torch.float32).detach().reshape(-1).cpu() for v in (a, b))
+    return a.shape == b.shape and torch.equal(a, b)
+
+
+class ConformalCalibrator:
+    """Split conformal calibration of the Monte-Carlo-dropout band [first level, last level] of ``probs``: conformity
+    scores s = max(Q_first - l, l - Q_last) of a held-out split are collected into a store on the device
+    (matgcn_mc_conformity), ``fit`` takes per group the k-th smallest of the n valid ones, k = ceil((n + 1) * coverage)
+    with coverage = last level - first level (matgcn_conformal_quantile), and ``apply`` widens a band by that margin:
+    on windows exchangeable with the calibration split the widened band covers with probability >= coverage.
+    ``grouping``: "horizon" - one margin per horizon - or "element" - one per (horizon, node, channel).  A group with
+    fewer than k valid scores gets the margin +inf (an honest "not enough data"; ``infinite_margins`` counts them).
+
+    Scale as ``NodeEvaluator``: with ``group_mean`` / ``group_std`` the re-transform, clamp at 0, NaN null value, no
+    ``min_s``; without them the config's ``min_s`` and null value 0.  ``s_small`` leaves out labels at or below it.  The
+    scaler's affine is the one of the first ``collect_samples`` call; bands passed to ``apply`` must be on that scale.
+    Only ``evaluate`` / ``coverage_table`` / ``state_dict`` read the device."""
+
+    def __init__(self, config, probs=(0.05, 0.5, 0.95), grouping="horizon", group_mean=None, group_std=None, s_small=None,
+                 capacity: int = 256):
+        if (group_mean is None) != (group_std is None):
+            raise ValueError("group_mean and group_std come as a pair")
+        self.probs = _check_probs(probs)
+        if len(self.probs) < 2:
+            raise ValueError("a band needs at least two levels, got %s" % (self.probs,))
+        self.coverage = _f32(self.probs[-1]) - _f32(self.probs[0])
+        if not 0.0 < self.coverage <= 1.0:
+            raise ValueError("the outer levels %g, %g span no band" % (self.probs[0], self.probs[-1]))
+        if grouping not in ("horizon", "element"):
+            raise ValueError("grouping must be 'horizon' or 'element', got %r" % (grouping,))
+        if int(capacity) < 1:
+            raise ValueError("capacity must be at least 1 row")
+        self.grouping = grouping
+        self.capacity = int(capacity)
+        self.group = None if group_mean is None else (group_mean, group_std)
+        self.truth_min = float("nan") if s_small is None else float(s_small)
+        self.clamp_min = float("nan") if self.group is None else 0.0
+        self.min_s = float(config.get("min_s", 1e-4)) if self.group is None else -1.0
+        self.null_val = 0.0 if self.group is None else float("nan")
+        self.affine = None                                    # (mean, std) of the scaler, set by the first batch
+        self.margin: Optional[torch.Tensor] = None            # (out,) or (out, N, od) float32
+        self.count: Optional[torch.Tensor] = None             # the same shape, int32
+        self.clear()
+
+    def clear(self):
+        """forget the calibration scores and the test counts (a fitted margin stays)"""
+        self.result: Dict[str, float] = {}
+        self._store: Optional[torch.Tensor] = None            # (capacity, out, N, od) scores, rows 0 .. _rows - 1 filled
+        self._rows = 0
+        self._batch_scores: Optional[torch.Tensor] = None     # the scores of one test batch
+        self._test_counts: Optional[torch.Tensor] = None      # (*group, 2) int64
+        self.len_timeslots = 0
+
+    def _scores(self, samples, y, y_start, mean, std, label_start, out):
+        if (mean is None) != (std is None):
+            raise ValueError("mean and std come as a pair")
+        on_device = any(isinstance(v, torch.Tensor) and v.is_cuda for v in (mean, std) + tuple(self.affine or ()))
+        if self.affine is None:
+            self.affine = (mean, std)
+        elif not on_device and not (_same_vector(self.affine[0], mean) and _same_vector(self.affine[1], std)):
+            # (device tensors are taken on trust here: comparing them would read the device on every batch)
+            raise ValueError("this calibrator collects on the scale mean, std = %s, got %s" % (self.affine, (mean, std)))
+        gm, gs = self.group if self.group is not None else (None, None)
+        return mc_conformity(samples, y, self.probs, y_start, mean, std, gm, gs, self.clamp_min, self.truth_min,
+                             self.min_s, self.null_val, label_start, out=out)
+
+    def collect_samples(self, samples, y, y_start: int = 0, mean=None, std=None, label_start=None):
+        """One calibration batch: arguments as ``NodeEvaluator.collect_samples``.  Appends its B rows of scores to the
+        store, which doubles its capacity when full."""
+        b, shape = int(samples.shape[1]), tuple(int(v) for v in samples.shape[2:])
+        if self._store is not None and tuple(self._store.shape[1:]) != shape:
+            raise ValueError("batch of shape %s after batches of shape %s" % (shape, tuple(self._store.shape[1:])))
+        need, have = self._rows + b, 0 if self._store is None else int(self._store.shape[0])
+        if need > have:
+            grown = max(have, self.capacity)
+            while grown < need:
+                grown *= 2
+            store = torch.empty((grown,) + shape, dtype=torch.float32, device=samples.device)
+            if self._rows:
+                store[:self._rows].copy_(self._store[:self._rows])
+            self._store = store
+        self._scores(samples, y, y_start, mean, std, label_start, self._store[self._rows:need])
+        self._rows = need
+        self.len_timeslots = shape[0]
+
+    def fit(self):
+        """margin and count per group from the scores collected so far, as device tensors"""
+        if self._store is None:
+            raise RuntimeError("nothing collected: call collect_samples first")
+        self.margin, self.count = conformal_quantile(self._store, self._rows, self.grouping, self.coverage)
+        self._test_counts = None
+        return self.margin, self.count
+
+    def _fitted(self):
+        if self.margin is None:
+            raise RuntimeError("not fitted: call fit (or load_state_dict) first")
+        return self.margin
+
+    def apply(self, quantiles: torch.Tensor) -> torch.Tensor:
+        """A copy of ``quantiles`` (levels, ..., out, N, od) with the first level lowered and the last raised by the
+        margin (one float32 rounding each; inner levels untouched), the two then held at the calibrator's clamp."""
+        margin = self._fitted().to(quantiles.device)
+        if quantiles.shape[0] != len(self.probs) or quantiles.dim() < 4:
+            raise ValueError("quantiles of shape %s are not %d levels of (..., out, N, od)" % (tuple(quantiles.shape),
+                                                                                               len(self.probs)))
+        m = margin.reshape(-1, 1, 1) if self.grouping == "horizon" else margin
+        out = quantiles.clone()
+        out[0] = quantiles[0] - m
+        out[-1] = quantiles[-1] + m
+        if self.clamp_min == self.clamp_min:
+            out[0].clamp_(min=self.clamp_min)
+            out[-1].clamp_(min=self.clamp_min)
+        return out
+
+    def check_call(self, probs, affine, group_mean, group_std, clamp_min):
+        """ValueError unless a band of levels ``probs`` on the scale (affine, group pair, clamp) is one this calibrator's
+        margin applies to"""
+        if _check_probs(probs) != self.probs:
+            raise ValueError("the calibrator was built for the levels %s, the call asks for %s" % (self.probs, tuple(probs)))
+        mine = self.affine if self.affine is not None else (None, None)
+        theirs = affine if affine is not None else (None, None)
+        ident = lambda pair: (0.0, 1.0) if pair[0] is None else pair
+        if not (_same_vector(ident(mine)[0], ident(theirs)[0]) and _same_vector(ident(mine)[1], ident(theirs)[1])):
+            raise ValueError("the calibrator's scores are on the scale mean, std = %s, the band on %s" % (mine, theirs))
+        gm, gs = self.group if self.group is not None else (None, None)
+        if not (_same_vector(gm, group_mean) and _same_vector(gs, group_std) and _same_scalar(self.clamp_min, clamp_min)):
+            raise ValueError("the calibrator's re-transform (group_mean / group_std, clamp_min = %s) differs from the call's"
+                             % (self.clamp_min,))
+
+    def collect_test_samples(self, samples, y, y_start: int = 0, mean=None, std=None, label_start=None):
+        """One test batch: counts per group how many of its valid scores the fitted margin covers."""
+        margin = self._fitted().to(samples.device)
+        shape = tuple(int(v) for v in samples.shape[1:])
+        if self._batch_scores is None or tuple(self._batch_scores.shape) != shape:
+            self._batch_scores = torch.empty(shape, dtype=torch.float32, device=samples.device)
+        scores = self._scores(samples, y, y_start, mean, std, label_start, self._batch_scores)
+        self._test_counts = conformal_coverage(scores, shape[0], self.grouping, margin.contiguous(), self._test_counts)
+        self.len_timeslots = shape[1]
+
+    def coverage_table(self) -> torch.Tensor:
+        """PICP of the calibrated band per group, (out,) or (out, N, od) float64 on the CPU; NaN without a valid label"""
+        if self._test_counts is None:
+            raise RuntimeError("nothing collected: call collect_test_samples first")
+        c = self._test_counts.cpu().double()
+        return torch.where(c[..., 0] > 0, c[..., 1] / c[..., 0], torch.full_like(c[..., 0], float("nan")))
+
+    def infinite_margins(self) -> torch.Tensor:
+        """(out,) int64 on the CPU: the groups of each horizon whose margin is +inf (k > n)"""
+        inf = torch.isinf(self._fitted()).cpu()
+        return inf.reshape(inf.shape[0], -1).sum(1)
+
+    def evaluate(self) -> Dict[str, float]:
+        """``PICP@k`` of the calibrated band per horizon (element groups pooled) and ``INF_MARGINS@k``"""
+        if self._test_counts is None:
+            raise RuntimeError("nothing collected: call collect_test_samples first")
+        c = self._test_counts.cpu()
+        c = c.reshape(c.shape[0], -1, 2).sum(1).double()
+        inf = self.infinite_margins()
+        for i in range(c.shape[0]):
+            self.result["PICP@%d" % (i + 1)] = float(c[i, 1] / c[i, 0]) if c[i, 0] > 0 else float("nan")
+            self.result["INF_MARGINS@%d" % (i + 1)] = int(inf[i])
+        return self.result
+
+    def state_dict(self) -> Dict[str, object]:
+        cpu = lambda v: None if v is None else torch.as_tensor(v, dtype=torch.float32).detach().cpu().clone()
+        gm, gs = self.group if self.group is not None else (None, None)
+        am, asd = self.affine if self.affine is not None else (None, None)
+        return {"margin": None if self.margin is None else self.margin.detach().cpu().clone(),
+                "count": None if self.count is None else self.count.detach().cpu().clone(),
+                "probs": tuple(self.probs), "grouping": self.grouping,
+                "scale": {"mean": cpu(am), "std": cpu(asd), "group_mean": cpu(gm), "group_std": cpu(gs),
+                          "clamp_min": self.clamp_min, "truth_min": self.truth_min, "min_s": self.min_s,
+                          "null_val": self.null_val}}
+
+    def load_state_dict(self, state):
+        probs = _check_probs(state["probs"])
+        if len(probs) < 2 or state["grouping"] not in ("horizon", "element"):
+            raise ValueError("not a calibrator state: probs %s, grouping %r" % (probs, state["grouping"]))
+        sc = state["scale"]
+        self.probs, self.grouping = probs, state["grouping"]
+        self.coverage = _f32(probs[-1]) - _f32(probs[0])
+        self.group = None if sc["group_mean"] is None else (sc["group_mean"], sc["group_std"])
+        self.affine = None if sc["mean"] is None else (sc["mean"], sc["std"])
+        self.clamp_min, self.truth_min = float(sc["clamp_min"]), float(sc["truth_min"])
+        self.min_s, self.null_val = float(sc["min_s"]), float(sc["null_val"])
+        self.margin = None if state["margin"] is None else state["margin"].clone()
+        self.count = None if state["count"] is None else state["count"].clone()
+        self.clear()
 
 
 def groupstd_table(pred, y, group_mean, group_std, y_start: int = 0, mean=None, std=None, label_start=None,

@@ -451,7 +451,7 @@ class MultiATGCN(AbstractTrafficStateModel):
                                  keep_samples=keep_samples)
 
     def predict_interval(self, batch, samples: int = 32, probs=(0.05, 0.5, 0.95), seed: Optional[int] = None,
-                         group_mean=None, group_std=None, clamp_min: Optional[float] = None):
+                         group_mean=None, group_std=None, clamp_min: Optional[float] = None, calibrator=None):
         """Monte-Carlo-dropout forecast with its empirical band: (mean, std, quantiles) in the units of ``predict`` -
         mean and std what ``predict_mc`` gives for the same seed, quantiles (len(probs), B, out, N, od) the levels
         ``probs`` (up to 8, ascending, in [0, 1]) of the ``samples`` forecasts per output element, numpy's "linear" rule
@@ -459,15 +459,26 @@ class MultiATGCN(AbstractTrafficStateModel):
         With ``group_mean`` / ``group_std`` (one value per node, a pair) or ``clamp_min`` the band alone moves to the
         re-transformed scale: every sample goes through the scaler's inverse, then x * group_std + group_mean, and is
         set to ``clamp_min`` where below it, before the quantiles are taken (matgcn_mc_quantiles_scaled; needs an affine
-        scaler) - the band in visits."""
-        mean, std, kept = self.predict_mc(batch, samples=samples, seed=seed, keep_samples=True)
-        if group_mean is None and group_std is None and clamp_min is None:
-            return mean, std, mc_quantiles(kept, probs)
-        affine = self._affine_scaler()
-        if affine is None:
+        scaler) - the band in visits.
+        ``calibrator`` (a fitted evaluator.ConformalCalibrator; None: the empirical band as it is): the outer two
+        levels are widened by its margin (``calibrator.apply``).  Its levels and its scale must be those of this call
+        - the scaler's affine (the identity for the band in the units of ``predict``), the group pair and the clamp -,
+        anything else is a ValueError."""
+        plain = group_mean is None and group_std is None and clamp_min is None
+        affine = None if plain else self._affine_scaler()
+        if not plain and affine is None:
             raise NotImplementedError("a re-transformed band needs an affine scaler (StandardScaler / NoneScaler)")
-        return mean, std, mc_quantiles_scaled(kept, probs, affine[0], affine[1], group_mean, group_std,
-                                              float("nan") if clamp_min is None else clamp_min)
+        if calibrator is not None:
+            if calibrator.margin is None:
+                raise ValueError("the calibrator is not fitted: call calibrate_mc over a held-out split, then fit()")
+            calibrator.check_call(probs, affine, group_mean, group_std, clamp_min)
+        mean, std, kept = self.predict_mc(batch, samples=samples, seed=seed, keep_samples=True)
+        if plain:
+            band = mc_quantiles(kept, probs)
+        else:
+            band = mc_quantiles_scaled(kept, probs, affine[0], affine[1], group_mean, group_std,
+                                       float("nan") if clamp_min is None else clamp_min)
+        return mean, std, band if calibrator is None else calibrator.apply(band)
 
     def score_mc(self, batch, samples: int = 32, probs=(0.05, 0.5, 0.95), seed: Optional[int] = None, sums=None):
         """The (out, 5 + len(probs)) float64 per-horizon sums [count, CRPS, covered, width, Winkler, pinball per level] of
@@ -498,6 +509,23 @@ class MultiATGCN(AbstractTrafficStateModel):
             evaluator.collect_samples(kept, src[0], self.start_dim, affine[0], affine[1], label_start=src[1])
         else:
             evaluator.collect_samples(kept, batch["y"], self.start_dim, affine[0], affine[1])
+        return kept
+
+    def calibrate_mc(self, batch, calibrator, samples: int = 32, seed: Optional[int] = None, test: bool = False):
+        """One Monte-Carlo-dropout ensemble of a held-out batch into ``calibrator`` (evaluator.ConformalCalibrator): its
+        conformity scores join the calibration store (matgcn_mc_conformity), or - ``test`` - are counted against the
+        fitted margin (matgcn_conformal_coverage).  Window and resident-series batches.  Returns the samples
+        (S, B, out, N, od), scaled."""
+        affine = self._affine_scaler()
+        if affine is None:
+            raise NotImplementedError("calibrate_mc needs an affine scaler (StandardScaler / NoneScaler)")
+        kept = self.predict_mc(batch, samples=samples, seed=seed, keep_samples=True)[2]
+        collect = calibrator.collect_test_samples if test else calibrator.collect_samples
+        if _is_series_batch(batch):
+            src = self._batch_source(batch)
+            collect(kept, src[0], self.start_dim, affine[0], affine[1], label_start=src[1])
+        else:
+            collect(kept, batch["y"], self.start_dim, affine[0], affine[1])
         return kept
 
     # ---- the same surface fed from the device-resident raw series (no windows, no labels materialised) ----------

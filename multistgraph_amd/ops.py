@@ -572,6 +572,90 @@ def mc_scores_nodes(samples: torch.Tensor, y: torch.Tensor, probs: Sequence[floa
     return sums
 
 
+def mc_conformity(samples: torch.Tensor, y: torch.Tensor, probs: Sequence[float], y_start: int = 0, mean=None, std=None,
+                  group_mean=None, group_std=None, clamp_min: float = float("nan"), truth_min: float = float("nan"),
+                  min_s: float = 1e-4, null_val: float = 0.0, label_start: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B, out, N, od) float32 device tensor of conformity scores max(Q_first - l, l - Q_last) of the ensemble ``samples``
+    (S, B, out, N, od) against the labels, on the scale and with the label filters of ``mc_scores_nodes``
+    (matgcn_mc_conformity); NaN where the label is masked or filtered out.  ``probs``: at least two levels, the outer two
+    are the band.  ``out``: the tensor to write - a slice of a caller's store of scores."""
+    lib = _lib.load()
+    samples = _mc_samples(samples)
+    if samples.dim() != 5:
+        raise _lib.MatgcnError("samples has shape %s, expected (S, B, out, N, od)" % (tuple(samples.shape),))
+    s, b, steps, n, od = (int(v) for v in samples.shape)
+    y, label_start, y_steps, y_feat = _label_geometry(samples[0], y, label_start)
+    levels, nq = _mc_probs(probs)
+    sc, keep = _metric_scale(n, samples.device, mean, std, group_mean, group_std, clamp_min, truth_min, min_s)
+    if out is None:
+        out = torch.empty(b, steps, n, od, dtype=torch.float32, device=samples.device)
+    elif (tuple(out.shape) != (b, steps, n, od) or out.dtype != torch.float32 or out.device != samples.device
+          or not out.is_contiguous()):
+        raise _lib.MatgcnError("out must be a contiguous CUDA float32 tensor of shape %s" % ((b, steps, n, od),))
+    stream = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
+    _lib.check(lib.matgcn_mc_conformity(C.c_void_p(samples.data_ptr()), s, C.c_void_p(y.data_ptr()),
+                                        C.c_void_p(_ptr(label_start)), b, steps, n, od, y_steps, y_feat, int(y_start),
+                                        C.byref(sc), float(null_val), levels, nq, C.c_void_p(out.data_ptr()), stream),
+               "matgcn_mc_conformity")
+    del keep
+    return out
+
+
+CONFORMAL_GROUPINGS = {"horizon": 0, "element": 1}
+
+
+def _conformal_store(scores: torch.Tensor, rows: int, grouping):
+    """(scores, rows, out, cols, grouping code, shape of a per-group result) of a store of scores (capacity, out, ...)"""
+    scores = _check_tensor(scores, "scores")
+    if scores.dim() < 3:
+        raise _lib.MatgcnError("scores has shape %s, expected (rows, out, N, od)" % (tuple(scores.shape),))
+    rows = int(rows)
+    if not 1 <= rows <= int(scores.shape[0]):
+        raise _lib.MatgcnError("rows = %d outside the store's 1 .. %d" % (rows, int(scores.shape[0])))
+    code = CONFORMAL_GROUPINGS.get(grouping, grouping)
+    if code not in (0, 1):
+        raise _lib.MatgcnError("grouping must be 'horizon' (0) or 'element' (1), got %r" % (grouping,))
+    steps = int(scores.shape[1])
+    return scores, rows, steps, scores[0, 0].numel(), code, tuple(scores.shape[1:]) if code else (steps,)
+
+
+def conformal_quantile(scores: torch.Tensor, rows: int, grouping, coverage: float):
+    """(margin float32, count int32), device tensors of shape (out,) - ``grouping`` "horizon" / 0 - or (out, N, od) -
+    "element" / 1 - from the first ``rows`` rows of a store of conformity scores (capacity, out, N, od): count = the non-NaN
+    scores of the group, margin = their k-th smallest, k = max(1, ceil((count + 1) * coverage)), +inf where k > count
+    (matgcn_conformal_quantile: an exact radix select on the device)."""
+    scores, rows, steps, cols, code, shape = _conformal_store(scores, rows, grouping)
+    margin = torch.empty(shape, dtype=torch.float32, device=scores.device)
+    count = torch.empty(shape, dtype=torch.int32, device=scores.device)
+    stream = C.c_void_p(torch.cuda.current_stream(scores.device).cuda_stream)
+    _lib.check(_lib.load().matgcn_conformal_quantile(C.c_void_p(scores.data_ptr()), rows, steps, cols, code,
+                                                     float(coverage), C.c_void_p(margin.data_ptr()),
+                                                     C.c_void_p(count.data_ptr()), stream), "matgcn_conformal_quantile")
+    return margin, count
+
+
+def conformal_coverage(scores: torch.Tensor, rows: int, grouping, margin: torch.Tensor,
+                       counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(*group shape, 2) int64 device tensor [valid scores, valid scores <= margin] per group over the first ``rows``
+    rows of ``scores`` (matgcn_conformal_coverage); ``counts`` from earlier batches is added to."""
+    scores, rows, steps, cols, code, shape = _conformal_store(scores, rows, grouping)
+    margin = _check_tensor(margin, "margin")
+    if tuple(margin.shape) != shape:
+        raise _lib.MatgcnError("margin has shape %s, expected %s" % (tuple(margin.shape), shape))
+    accumulate = counts is not None
+    if counts is None:
+        counts = torch.empty(shape + (2,), dtype=torch.int64, device=scores.device)
+    elif (tuple(counts.shape) != shape + (2,) or counts.dtype != torch.int64 or not counts.is_cuda
+          or not counts.is_contiguous()):
+        raise _lib.MatgcnError("counts must be a contiguous CUDA int64 tensor of shape %s" % (shape + (2,),))
+    stream = C.c_void_p(torch.cuda.current_stream(scores.device).cuda_stream)
+    _lib.check(_lib.load().matgcn_conformal_coverage(C.c_void_p(scores.data_ptr()), rows, steps, cols, code,
+                                                     C.c_void_p(margin.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                                     int(accumulate), stream), "matgcn_conformal_coverage")
+    return counts
+
+
 def _opt_tensor(t, name: str) -> torch.Tensor:
     """an optimizer tensor as the C ABI wants it - the caller's own memory, so nothing is copied or converted here"""
     if not isinstance(t, torch.Tensor):
