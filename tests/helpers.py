@@ -73,6 +73,8 @@ with open(os.path.join(GOLDEN_DIR, "edge_index.json")) as fh:
     EDGE_INDEX = json.load(fh)     # shape-edge cases (make_edge_golden.py): an index of their own, not part of FULL
 EDGE = sorted(EDGE_INDEX)
 EDGE_GRAD = sorted(k for k in EDGE if EDGE_INDEX[k]["grad"])
+# the gradient cases that differ from each other by shape alone (the generator marks the default configuration)
+EDGE_SHAPE_GRAD = [k for k in EDGE_GRAD if EDGE_INDEX[k]["default_config"]]
 
 
 class EdgeCase:
@@ -86,29 +88,55 @@ class EdgeCase:
         m = self.meta = EDGE_INDEX[name]
         self.n, self.b, self.out, self.feat, self.seed = m["nodes"], m["batch"], m["out"], m["feat"], m["seed"]
         self.adjtype, self.adpadj, self.cheb = m["adjtype"], m["adpadj"], m["cheb"]
+        self.layers, self.od, self.embed, self.ext, self.has_h0 = m["layers"], m["end_dim"], m["embed"], m["ext"], m["h0"]
+        assert self.feat == self.od + self.ext
         self.gold = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
         self.grad_gold = np.load(os.path.join(GOLDEN_DIR, "edge_grad_%s.npz" % name[5:])) if m["grad"] else None
-        self.data_feature = syn.make_data_feature(self.n, self.seed, m["city"], ext_dim=self.feat - 1)
+        self.data_feature = dict(syn.make_data_feature(self.n, self.seed, m["city"], ext_dim=self.ext),
+                                 output_dim=self.od, feature_dim=self.feat)
         self.mats = np.stack(graph_prep.build_static_supports(self.data_feature["adj_mx"], self.data_feature["coordinate"],
                                                               None, self.adjtype), 0)
-        self.shapes = syn.param_shapes(self.n, out_steps=self.out, feat_in=self.feat,
-                                       k_total=syn.k_total_for(self.adjtype, self.adpadj, self.cheb))
+        self.shapes = syn.param_shapes(self.n, out_steps=self.out, feat_in=self.feat, out_dim=self.od,
+                                       k_total=syn.k_total_for(self.adjtype, self.adpadj, self.cheb), layers=self.layers,
+                                       embed_dim_node=self.embed)
         self.state = syn.closed_form_state(self.shapes, self.seed)
         self.x, self.y = syn.make_batch_arrays(self.b, self.n, self.out, self.seed, feat=self.feat)
+        if self.od > 1:   # channels [flow 0 .. flow od-1 | time of day]
+            self.x = np.ascontiguousarray(np.concatenate([self.x[..., :1], self.x[..., 2:], self.x[..., 1:2]], -1))
+
+    def _channels(self):
+        """ext (0 / 1 / 8 / 13 input channels next to the flow) as the three config switches"""
+        return dict(add_time_in_day=self.ext > 0, add_day_in_week=self.ext in (8, 13), load_dynamic=self.ext == 13)
 
     def config(self, device="cpu"):
-        return dict(input_window=24, output_window=self.out, add_time_in_day=True, add_day_in_week=False,
-                    load_dynamic=False, adjtype=self.adjtype, adpadj=self.adpadj, cheb_order=self.cheb, embed_dim_node=20,
-                    embed_dim_adj=20, rnn_units=64, num_layers=2, device=torch.device(device), batch_size=self.b,
-                    start_dim=0, end_dim=1)
+        return dict(input_window=24, output_window=self.out, adjtype=self.adjtype, adpadj=self.adpadj,
+                    cheb_order=self.cheb, embed_dim_node=self.embed, embed_dim_adj=20, rnn_units=64,
+                    num_layers=self.layers, device=torch.device(device), batch_size=self.b, start_dim=0, end_dim=self.od,
+                    **self._channels())
 
     def oracle_cfg(self):
-        return dict(adjtype=self.adjtype, adpadj=self.adpadj, cheb_order=self.cheb, num_layers=2, rnn_units=64,
+        return dict(adjtype=self.adjtype, adpadj=self.adpadj, cheb_order=self.cheb, num_layers=self.layers, rnn_units=64,
                     len_closeness=48, len_period=24, len_trend=24, output_window=self.out, input_window=24,
-                    add_time_in_day=True, add_day_in_week=False, load_dynamic=False, start_dim=0, end_dim=1)
+                    start_dim=0, end_dim=self.od, **self._channels())
+
+    def spec_and_static(self):
+        """(PathSpec, static supports (K, N, N) as a CPU tensor or None) of the HIP path: the reference keeps the static
+        supports next to an adaptive one in 'multi' mode only (MultiATGCN.py:90-93)"""
+        from multistgraph_amd.ops import diagonal_mask, spec_from_config
+        use_static = self.adpadj == "none" or self.adjtype == "multi"
+        st = torch.from_numpy(self.mats) if use_static else None
+        spec = spec_from_config(self.config(), self.data_feature, self.n, min(self.n, 20), st.shape[0] if use_static else 0,
+                                diagonal_mask(st) if use_static else 0)
+        return spec, st
+
+    def h0(self):
+        """the seeded (N, H) initial state of an `h0` case (every layer and sample starts from it), else None"""
+        if not self.has_h0:
+            return None
+        return (0.1 * np.random.default_rng(11).standard_normal((self.n, 64))).astype(np.float32)
 
     def d_out(self):
-        return np.random.default_rng(9).standard_normal((self.b, self.out, self.n, 1)).astype(np.float32)
+        return np.random.default_rng(9).standard_normal((self.b, self.out, self.n, self.od)).astype(np.float32)
 
     def checksum_errors(self, gold=None):
         """what of the regenerated inputs, parameters and static supports misses the fixture's checksums (static_sums

@@ -484,6 +484,10 @@ def test_full_size_directional_derivative(lib_built):
     # temporal-head layouts of the reference's first sweep that have no reference fixture (run_model_parameter.py:6-7):
     # closeness + trend without a period block, closeness + period without trend, two period heads
     (21, 2, 2, {"lens": (1, 0, 1)}), (21, 3, 2, {"lens": (1, 1, 0)}), (19, 2, 2, {"lens": (1, 2, 1)}),
+    # out_channels = output_window * output_dim on either side of the head kernels' 32-channel tile and at their cap:
+    # 32 (the last of NTc 1), 33 (the first of NTc 2: one channel in the second tile), 64 (the cap; 65 is refused -
+    # test_host_logic.py)
+    (21, 2, 2, {"out": 32}), (21, 2, 2, {"out": 33}), (21, 3, 2, {"out": 32, "end_dim": 2}),
 ])
 def test_backward_on_synthetic_shapes_outside_the_golden_set(n, b, layers, flags, lib_built):
     """N a multiple of 16 (no padding rows anywhere), a batch that is not a multiple of the 64-row tile, and 1 / 3 / 4
@@ -498,8 +502,9 @@ def test_backward_on_synthetic_shapes_outside_the_golden_set(n, b, layers, flags
     od, ext = flags.get("end_dim", 1), flags.get("ext", 1)
     emb = flags.get("embed", 20)
     lens = flags.get("lens", (2, 1, 1))
-    abl = {k: v for k, v in flags.items() if k not in ("cheb_order", "adjtype", "adpadj", "end_dim", "ext", "embed", "lens")}
-    cfg = dict(input_window=24, output_window=6, add_time_in_day=ext > 0, add_day_in_week=ext in (8, 13),
+    out = flags.get("out", 6)     # output_window: out_channels = out * end_dim picks the head kernels' channel tiles
+    abl = {k: v for k, v in flags.items() if k not in ("cheb_order", "adjtype", "adpadj", "end_dim", "ext", "embed", "lens", "out")}
+    cfg = dict(input_window=24, output_window=out, add_time_in_day=ext > 0, add_day_in_week=ext in (8, 13),
                load_dynamic=ext == 13,
                adjtype=adjtype, adpadj=adpadj, cheb_order=cheb, embed_dim_node=emb, embed_dim_adj=20, rnn_units=64,
                num_layers=layers, device=torch.device("cpu"), batch_size=b, start_dim=0, end_dim=od, **abl)
@@ -507,10 +512,10 @@ def test_backward_on_synthetic_shapes_outside_the_golden_set(n, b, layers, flags
     mats = graph_prep.build_static_supports(df["adj_mx"], df["coordinate"], None, adjtype)
     use_static = adpadj == "none" or adjtype == "multi"
     st = torch.from_numpy(np.stack(mats, 0))
-    shapes = syn.param_shapes(n, out_steps=6, feat_in=od + ext, out_dim=od, k_total=syn.k_total_for(adjtype, adpadj, cheb),
+    shapes = syn.param_shapes(n, out_steps=out, feat_in=od + ext, out_dim=od, k_total=syn.k_total_for(adjtype, adpadj, cheb),
                               layers=layers, embed_dim_node=emb, len_ts=sum(lens), **abl)
     state_np = syn.closed_form_state(shapes, 3)
-    x_np, _ = syn.make_batch_arrays(b, n, 6, 3, feat=od + ext, x_steps=24 * sum(lens))
+    x_np, _ = syn.make_batch_arrays(b, n, out, 3, feat=od + ext, x_steps=24 * sum(lens))
     if od > 1:   # channels [flow 0 .. flow od-1 | time of day]
         x_np = np.ascontiguousarray(np.concatenate([x_np[..., :1], x_np[..., 2:], x_np[..., 1:2]], -1))
     spec = spec_from_config(cfg, df, n, min(n, 20), st.shape[0] if use_static else 0,
@@ -519,10 +524,10 @@ def test_backward_on_synthetic_shapes_outside_the_golden_set(n, b, layers, flags
     state = {k: torch.from_numpy(v).to(dev) for k, v in state_np.items()}
     hp.bind(state, st.to(dev) if use_static else None)
     rng = np.random.default_rng(9)
-    d_out = rng.standard_normal((b, 6, n, od)).astype(np.float32)
+    d_out = rng.standard_normal((b, out, n, od)).astype(np.float32)
     p = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in state_np.items()}
     ocfg = dict(adjtype=adjtype, adpadj=adpadj, cheb_order=cheb, num_layers=layers, rnn_units=64, len_closeness=24 * lens[0],
-                len_period=24 * lens[1], len_trend=24 * lens[2], output_window=6, input_window=24, add_time_in_day=ext > 0,
+                len_period=24 * lens[1], len_trend=24 * lens[2], output_window=out, input_window=24, add_time_in_day=ext > 0,
                 add_day_in_week=ext in (8, 13), load_dynamic=ext == 13, start_dim=0, end_dim=od, **abl)
     y = orc.forward(torch.tensor(x_np, dtype=torch.float64), p, [m.double() for m in st] if use_static else [], ocfg,
                     faithful=False)

@@ -19,6 +19,10 @@ from test_train_precision import ATOMIC_TOL, D_H0, _errors, _fixture_mask, _path
 GRAD_TOL = 1e-4
 CASES = ["tiny_multi_uni_c2", "tiny_multi_bid_c2", "tiny_multi_uni_dyn7", "tiny_multi_uni_c2_static", "dc237_out12"]
 EDGES = ["edge_n257_b33", "edge_n64_b17", "edge_n1039_b3"]
+# stacks the ordered reductions scale with (test_shape_edges.py has the table): Ks 6 on the unfused chain pair - its blend
+# shares come from (B * Np + 63) / 64 workgroups, its pool gradients entry by entry -, Ks 0 (no mix, no adjacency
+# gradient), 14 input channels (the widest narrow residual weight gradient)
+CONFIG_EDGES = ["edge_c3_n65_b5", "edge_ident_c3_n65_b5", "edge_ext13_n65_b7"]
 HID = "hid48_gcnoff"
 
 
@@ -155,7 +159,7 @@ def _edge_run(name):
         bad.update({k: e for k, e in errs.items() if e > GRAD_TOL})
         return bad
 
-    return _Run(p.hp, p.state, p.x, torch.from_numpy(p.c.d_out()).to(p.dev), gold=gold, errors=errors)
+    return _Run(p.hp, p.state, p.x, torch.from_numpy(p.c.d_out()).to(p.dev), h0=p.h0, gold=gold, errors=errors)
 
 
 def _hid_run(monkeypatch):
@@ -201,7 +205,7 @@ def _assert_same_bits(a, b):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", CASES + EDGES)
+@pytest.mark.parametrize("name", CASES + EDGES + CONFIG_EDGES)
 def test_three_deterministic_backwards_have_equal_bits(name, runs):
     r = runs(name)
     first = r.backward()
@@ -225,7 +229,7 @@ def test_padded_dense_cells_have_equal_bits(lib_built, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", CASES + EDGES)
+@pytest.mark.parametrize("name", CASES + EDGES + CONFIG_EDGES)
 def test_deterministic_gradients_match_the_fixture_and_the_default(name, runs):
     """the metric and tolerance of test_backward_matches_reference_autograd (edge cases: of
     test_training_step_matches_the_float64_autograd), and 1e-4 max-normalised against the default backward on the same

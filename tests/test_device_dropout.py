@@ -31,18 +31,23 @@ class _Bound:
     def __init__(self, nodes, batch, **flags):
         from multistgraph_amd import graph_prep, synthetic as syn
         from multistgraph_amd.ops import HotPath, diagonal_mask, spec_from_config
+        flags = dict(flags)
+        self.out = out = flags.pop("out", OUT)          # output_window
+        self.od = od = flags.pop("end_dim", 1)          # flow channels: out_channels = out * od
         self.n, self.b, self.flags = nodes, batch, flags
         self.dev = dev = torch.device("cuda:0")
         seed = 3
-        df = syn.make_data_feature(nodes, seed, "DC", ext_dim=1)
-        cfg = dict(input_window=24, output_window=OUT, add_time_in_day=True, add_day_in_week=False, load_dynamic=False,
+        df = dict(syn.make_data_feature(nodes, seed, "DC", ext_dim=1), output_dim=od, feature_dim=od + 1)
+        cfg = dict(input_window=24, output_window=out, add_time_in_day=True, add_day_in_week=False, load_dynamic=False,
                    adjtype="multi", adpadj="unidirection", cheb_order=2, embed_dim_node=20, embed_dim_adj=20, rnn_units=64,
-                   num_layers=2, device=dev, batch_size=batch, start_dim=0, end_dim=1)
+                   num_layers=2, device=dev, batch_size=batch, start_dim=0, end_dim=od)
         cfg.update(flags)
-        shapes = syn.param_shapes(nodes, out_steps=OUT, feat_in=2, k_total=syn.k_total_for("multi", "unidirection", 2),
-                                  **flags)
+        shapes = syn.param_shapes(nodes, out_steps=out, feat_in=od + 1, out_dim=od,
+                                  k_total=syn.k_total_for("multi", "unidirection", 2), **flags)
         state = syn.closed_form_state(shapes, seed)
-        x, _ = syn.make_batch_arrays(batch, nodes, OUT, seed, feat=2)
+        x, _ = syn.make_batch_arrays(batch, nodes, out, seed, feat=od + 1)
+        if od > 1:   # channels [flow 0 .. flow od-1 | time of day]
+            x = np.ascontiguousarray(np.concatenate([x[..., :1], x[..., 2:], x[..., 1:2]], -1))
         self.x = torch.from_numpy(x).to(dev)
         self.head_steps = 1 if flags.get("fnn_off") else 24
         if flags.get("rnn_units", 64) < 64:
@@ -72,7 +77,7 @@ class _Bound:
         return (torch.from_numpy(series).to(self.dev), torch.from_numpy(pick).to(self.dev), rel)
 
     def d_out(self):
-        g = np.random.default_rng(9).standard_normal((self.b, OUT, self.n, 1)).astype(np.float32)
+        g = np.random.default_rng(9).standard_normal((self.b, self.out, self.n, self.od)).astype(np.float32)
         return torch.from_numpy(g).to(self.dev)
 
     def h0(self):
@@ -218,7 +223,8 @@ def test_a_backward_with_another_offset_differs(bound):
 
 
 # ---- 4. Monte-Carlo dropout --------------------------------------------------------------------------------------------
-MC_CASES = [(65, 16, {}), (21, 129, {"fnn_off": True})]
+# the last: out_channels = 24 * 2 = 48, the second 32-channel tile of k_head_mc (NTc 2) with two interleaved output channels
+MC_CASES = [(65, 16, {}), (21, 129, {"fnn_off": True}), (65, 3, {"out": 24, "end_dim": 2})]
 
 
 def _mc_reference(p, samples, offset):
@@ -240,7 +246,7 @@ def test_forward_mc_samples_mean_and_std(nodes, batch, flags, bound):
     S, offset = 8, 2 ** 32 + 5
     mean, std, samples = p.hp.forward_mc(p.x, seed=SEED, offset=offset, p=P, samples=S, keep_samples=True)
     want = _mc_reference(p, S, offset)
-    assert samples.shape == want.shape == (S, batch, OUT, nodes, 1)
+    assert samples.shape == want.shape == (S, batch, p.out, nodes, p.od)
     for s in range(S):
         err = max_norm_err(samples[s].cpu().numpy(), want[s].cpu().numpy())
         assert err <= FWD_TOL, (s, err)

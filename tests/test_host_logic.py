@@ -159,6 +159,53 @@ def test_size_queries_and_argument_checks(lib_built):
     assert lib.matgcn_workspace_bytes(C.byref(spec.dims(2048)), C.byref(nb)) == -3
 
 
+@pytest.mark.parametrize("name,np_,ks", [
+    ("edge_c3_n65_b5", 80, 6), ("edge_c3bi_n257_b3", 272, 6), ("edge_c3none_n80_b17", 80, 4), ("edge_c4_n65_b3", 80, 9),
+    ("edge_c1_n65_b17_l3", 80, 1), ("edge_oduni_n65_b3", 80, 1), ("edge_dist_n65_b33_l1", 80, 1),
+    ("edge_ident_c3_n65_b5", 80, 0), ("edge_ext13_n65_b7", 80, 3), ("edge_ext8_n48_b17", 48, 3),
+    ("edge_ext0_n65_b16", 80, 3), ("edge_od2_out24_n65_b3", 80, 3), ("edge_l4_n48_b3", 48, 3),
+    ("edge_emb8_n65_b3", 80, 3), ("edge_emb40_n65_b3", 80, 3)])
+def test_plans_of_the_configuration_edge_cases(name, np_, ks, lib_built):
+    """the dense slots (Ks) and padded rows (Np) the table of test_shape_edges.py quotes for its configuration cases, as
+    make_plan derives them; every case is accepted by all three size queries"""
+    from helpers import EdgeCase
+    from multistgraph_amd import _lib
+    lib = _lib.load()
+    c = EdgeCase(name)
+    spec, _ = c.spec_and_static()
+    d = spec.dims(c.b)
+    lay, nb = (C.c_int64 * 4)(), C.c_size_t()
+    assert lib.matgcn_supports_layout(C.byref(d), C.byref(lay)) == 0
+    assert (int(lay[2]), int(lay[3])) == (np_, ks)
+    for query in (lib.matgcn_prepared_bytes, lib.matgcn_workspace_bytes, lib.matgcn_train_bytes):
+        assert query(C.byref(d), C.byref(nb)) == 0 and nb.value > 0
+
+
+def test_head_channel_cap_and_stack_cap_are_refused_by_the_size_queries(lib_built):
+    """out_channels = output_window * output_dim: 64 is the cap of the head kernels (two 32-channel tiles), 65 is
+    MATGCN_ERR_UNSUPPORTED; cheb_order 5 on multi / unidirection is a reference stack of 1 + 4 * 4 = 17 entries, one
+    past MATGCN_MAX_STACK, while cheb_order 4 (13) is accepted - both from matgcn_workspace_bytes, before any launch"""
+    from helpers import EdgeCase
+    from multistgraph_amd import _lib
+    from multistgraph_amd.ops import spec_from_config
+    lib = _lib.load()
+    c = EdgeCase("edge_n48_b3")
+    nb = C.c_size_t()
+
+    def status(**over):
+        cfg = dict(c.config(), **over)
+        spec = spec_from_config(cfg, c.data_feature, c.n, min(c.n, 20), 3, 0b100)
+        d = spec.dims(c.b)
+        return [q(C.byref(d), C.byref(nb)) for q in (lib.matgcn_workspace_bytes, lib.matgcn_prepared_bytes,
+                                                     lib.matgcn_train_bytes)]
+
+    assert status(output_window=64) == [0, 0, 0]
+    assert status(output_window=65) == [-3, -3, -3]           # MATGCN_ERR_UNSUPPORTED
+    assert status(cheb_order=4) == [0, 0, 0]
+    assert status(cheb_order=5) == [-3, -3, -3]
+    assert lib.matgcn_error_string(-3) == b"configuration not supported by this build"
+
+
 def test_diagonal_supports_are_detected_on_the_host():
     # no static features: the similarity Laplacian is exactly -I (MultiATGCN.py:244-250) -> bit 2 of the mask
     from multistgraph_amd.model import MultiATGCN

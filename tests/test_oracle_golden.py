@@ -129,7 +129,7 @@ def test_edge_fixtures_match_their_regenerated_inputs(stem):
     assert name in EDGE_INDEX and (EDGE_INDEX[name]["grad"] or stem == name)
     c = EdgeCase(name)
     assert c.checksum_errors(np.load(os.path.join(GOLDEN_DIR, stem + ".npz"))) == []
-    assert c.gold["pred64"].dtype == np.float64 and c.gold["pred64"].shape == (c.b, c.out, c.n, 1)
+    assert c.gold["pred64"].dtype == np.float64 and c.gold["pred64"].shape == (c.b, c.out, c.n, c.od)
 
 
 def test_every_edge_case_has_its_files():
@@ -146,6 +146,26 @@ def test_edge_fixtures_are_in_sync_with_the_oracle(name):
     pred = O.forward(torch.from_numpy(c.x), O.to_tensors(c.state), O.supports_as_tensors(c.mats), c.oracle_cfg(),
                      faithful=False)
     assert max_norm_err(pred.numpy(), c.gold["pred64"]) <= TOL
+
+
+@pytest.mark.parametrize("name", ["edge_oduni_n65_b3", "edge_od2_out24_n65_b3", "edge_l4_n48_b3", "edge_ext13_n65_b7",
+                                  "edge_c1_n65_b17_l3", "edge_emb8_n65_b3", "edge_ident_c3_n65_b5"])
+def test_configuration_edge_cases_are_rebuilt_as_the_generator_built_them(name):
+    """helpers.EdgeCase reads a case's configuration from edge_index.json: its inputs, its oracle configuration, its
+    static-support rule and its initial state give the stored float64 prediction back (fp32 oracle forward), and the
+    fixture passed the generator's admission rule"""
+    from helpers import EdgeCase
+    from multistgraph_amd.ops import HotPath
+    c = EdgeCase(name)
+    _, st = c.spec_and_static()
+    h0 = c.h0()
+    assert (h0 is not None) == ("grad." + HotPath.D_H0 in c.grad_gold.files)
+    pred = O.forward(torch.from_numpy(c.x), O.to_tensors(c.state), [] if st is None else list(st), c.oracle_cfg(),
+                     faithful=False, h0=None if h0 is None else torch.from_numpy(h0))
+    assert pred.shape == c.gold["pred64"].shape == (c.b, c.out, c.n, c.od)
+    assert max_norm_err(pred.numpy(), c.gold["pred64"]) <= TOL
+    assert float(c.gold["gap32_pred"]) <= 5e-6 and float(c.grad_gold["gap32_grad"]) <= 5e-6
+    assert int(c.grad_gold["sub"]) == c.meta["sub"]
 
 
 GRAD_CASES = sorted(f[5:-4] for f in os.listdir(GOLDEN_DIR) if f.startswith("grad_"))
