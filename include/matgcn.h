@@ -653,6 +653,59 @@ int matgcn_conformal_coverage(const float* scores, int64_t rows, int out_steps, 
                               const float* margin /* (groups) */, int64_t* counts /* (groups, 2): n, covered */,
                               int accumulate, void* stream);
 
+/* ---- totals over groups of nodes: regions (matgcn_regions.hip) -----------------------------------------------------------
+ * Forecasts are made per node (census tract) and planned with per county, district or corridor.  Quantiles and errors do
+ * not add, so the band and the scores of a region total are taken from totals formed sample by sample.  The two entry
+ * points form them - of any (rows, nodes, out_dim) tensor (the point forecast, the Monte-Carlo-dropout samples) and of the
+ * labels of a batch - on the re-transformed scale; every kernel above then applies to the result with nodes = n_groups and
+ * an identity descriptor.
+ *
+ * matgcn_groups is a CSR list over groups: groups may overlap, nest, be empty or leave nodes out.  `ptr` is read on the
+ * HOST at call time (ptr[0] = 0, non-decreasing, ptr[n_groups] = n_members, else MATGCN_ERR_BAD_ARG); the kernels read its
+ * device copy.  Node indices are validated where the map is built; an index outside 0 .. nodes-1 is clamped into the row,
+ * so no map makes a kernel read outside the tensor.
+ *
+ * Per member: value v of node n, channel c goes through the descriptor's first affine (scalar or per node; null =
+ * identity), then its per-node second affine, each an fp32 product and an fp32 sum, never fused, as in
+ * matgcn_mc_quantiles_scaled; then v := clamp_min where v < clamp_min (NaN: off).  truth_min and min_s are not used.
+ * Per (row r, group g, channel c): start from 0.0 in fp64; for k = ptr[g] .. ptr[g+1]-1 in ascending k add
+ * (double)weight[k] * (double)v(node[k]) (weight null = 1), one member at a time; round to fp32 once.  The product of
+ * two fp32 values is exact in fp64, so a contracted fma gives the bits of multiply then add.  An empty group stores +0.0;
+ * a NaN member makes the total NaN - the region-level mask: a region with a missing label has no label.
+ * One thread owns a chain from end to end: no atomics, nothing allocated, the caller's stream only, EVERY element of
+ * `out` is written, and the result does not depend on the order workgroups run in - the same bits every run, however a
+ * test set is batched.  matgcn_group_sums reads each row once into an LDS tile (several rows in up to 32 KB, one long row
+ * in up to 64 KB; a row of more than 16 383 floats is walked in global memory instead, same chain) and keeps a map of up
+ * to 16 KB beside it.
+ *
+ * matgcn_group_label_sums reads labels with the geometry of matgcn_masked_mae: label_start null = window labels
+ * (batch, y_steps, nodes, y_feat), channels y_start .. y_start + out_dim - 1 of steps 0 .. out_steps-1; otherwise `y` is
+ * the raw series (y_steps, nodes, y_feat) and label_start (batch) its first label rows, clamped and counted through
+ * matgcn_series_violations.
+ * Argument checks, before any launch: non-null pointers (node may be null with n_members = 0); rows (batch, out_steps),
+ * nodes, out_dim, n_groups >= 1, n_members >= 0; a lone mean or std; the label geometry; rows*n_groups*out_dim and
+ * rows*nodes*out_dim within int64 - MATGCN_ERR_BAD_ARG.  nodes*out_dim or 256*n_groups*out_dim of 2^31 or more, or more
+ * than 2^31 - 1 workgroups, is MATGCN_ERR_UNSUPPORTED.
+ * Measured at Baltimore 403 / B = 64 / out = 24 with the re-transform and clamp 0 (MI355X, tools/region_time.py, one
+ * process, routes alternating three times, median of 20 calls, HIP events), ten regions / the same
+ * plus one whole-city group: matgcn_group_sums 0.078 / 0.124 ms at S = 32 and 0.248 / 0.396 ms at S = 128; torch de-scale +
+ * clamp + matmul with the dense membership matrix 0.146 / 0.145 and 0.614 / 0.614 ms; torch index_add_ 1.62 / 3.11 and
+ * 5.79 / 11.9 ms; one plain read of the samples 0.019 and 0.057 ms.  Every gap to the matmul route is above twice the
+ * spread of the visits (at most 0.005 ms); the kernel is 4.1 to 7.0 times the plain read: not at memory speed. */
+typedef struct matgcn_groups {
+  const int32_t* ptr;     /* HOST, n_groups + 1 entries, ptr[0] = 0, non-decreasing, ptr[n_groups] = n_members */
+  const int32_t* ptr_dev; /* device copy of ptr */
+  const int32_t* node;    /* device, n_members node indices in 0 .. nodes-1, in the order they are to be added */
+  const float*   weight;  /* device, n_members, or NULL = 1 */
+  int32_t n_groups, n_members;
+} matgcn_groups;
+int matgcn_group_sums(const float* values, int64_t rows, int nodes, int out_dim, const matgcn_metric_scale* scale,
+                      const matgcn_groups* groups, float* out /* (rows, n_groups, out_dim) */, void* stream);
+int matgcn_group_label_sums(const float* y, const int32_t* label_start, int batch, int out_steps, int nodes, int out_dim,
+                            int y_steps, int y_feat, int y_start, const matgcn_metric_scale* scale,
+                            const matgcn_groups* groups, float* out /* (batch, out_steps, n_groups, out_dim) */,
+                            void* stream);
+
 /* ---- the optimizer step: global gradient norm, clip and Adam over a table of tensors -------------------------------------
  * What clip_grad_norm_(params, max_norm) followed by torch.optim.Adam.step() does (no amsgrad, no maximize), as three
  * launches over every tensor at once.  The tensors are described by a HOST array of matgcn_opt_tensor, read at call time;

@@ -93,6 +93,12 @@ class MetricScale(C.Structure):
                 ("std2", C.c_void_p), ("clamp_min", C.c_float), ("truth_min", C.c_float), ("min_s", C.c_float)]
 
 
+class Groups(C.Structure):
+    """matgcn_groups: a region map as a CSR list over groups (ptr on the host, the rest on the device)"""
+    _fields_ = [("ptr", C.POINTER(C.c_int32)), ("ptr_dev", C.c_void_p), ("node", C.c_void_p), ("weight", C.c_void_p),
+                ("n_groups", C.c_int32), ("n_members", C.c_int32)]
+
+
 class LossDesc(C.Structure):
     """matgcn_loss_desc: one training objective (kind, the scaler's affine, mask rule, delta)"""
     _fields_ = [("kind", C.c_int32), ("mean", C.c_float), ("std", C.c_float), ("null_val", C.c_float),
@@ -174,6 +180,9 @@ _SIGNATURES = {
                                        C.c_int, C.POINTER(MetricScale), C.c_float, C.POINTER(C.c_float), C.c_int, _P, _P]),
     "matgcn_conformal_quantile": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P]),
     "matgcn_conformal_coverage": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
+    "matgcn_group_sums": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.POINTER(MetricScale), C.POINTER(Groups), _P, _P]),
+    "matgcn_group_label_sums": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(MetricScale), C.POINTER(Groups), _P, _P]),
     "matgcn_grad_norm_bytes":(C.c_int, [C.POINTER(OptTensor), C.c_int, C.POINTER(C.c_size_t)]),
     "matgcn_grad_norm": (C.c_int, [C.POINTER(OptTensor), C.c_int, _P, C.c_size_t, _P, _P]),
     "matgcn_adam_step": (C.c_int, [C.POINTER(OptTensor), C.c_int, C.POINTER(Adam), _P, _P]),

@@ -19,6 +19,7 @@
 #include "matgcn_bwd_kernels.hip"
 #include "matgcn_mc_scores.hip"
 #include "matgcn_conformal.hip"
+#include "matgcn_regions.hip"
 #include "matgcn_optim.hip"
 #include "matgcn_loss.hip"
 
@@ -1739,6 +1740,94 @@ int matgcn_conformal_coverage(const float* scores, int64_t rows, int out_steps, 
     hipLaunchKernelGGL(k_conformal_coverage_rows, dim3((unsigned)out_steps), dim3(256), 0, s, scores, (int)rows, out_steps,
                        cols, margin, accumulate, (long long*)counts);
   return launch_ok();
+}
+
+// ---- totals over groups of nodes (matgcn_regions.hip) ----------------------------------------------------------------------
+namespace {
+// the map: non-null host and device offsets, G >= 1, members >= 0 (node may be null without members), ptr[0] = 0,
+// non-decreasing, ptr[G] = members
+int group_map(const matgcn_groups* groups, GroupMap* m) {
+  if (!groups) return MATGCN_ERR_NULL;
+  if (!groups->ptr || !groups->ptr_dev) return MATGCN_ERR_NULL;
+  if (groups->n_groups < 1 || groups->n_members < 0) return MATGCN_ERR_BAD_ARG;
+  if (groups->n_members > 0 && !groups->node) return MATGCN_ERR_NULL;
+  if (groups->ptr[0] != 0 || groups->ptr[groups->n_groups] != groups->n_members) return MATGCN_ERR_BAD_ARG;
+  for (int g = 0; g < groups->n_groups; ++g)
+    if (groups->ptr[g + 1] < groups->ptr[g]) return MATGCN_ERR_BAD_ARG;
+  m->ptr = groups->ptr_dev; m->node = groups->node; m->weight = groups->weight; m->G = groups->n_groups;
+  return MATGCN_OK;
+}
+// (rows, nodes, out_dim) in and (rows, G, out_dim) out: counts >= 1, both element counts inside int64, a row and the
+// chains of a tile inside a 32-bit index
+int group_shape(int64_t rows, int nodes, int out_dim, int n_groups) {
+  if (rows < 1 || nodes < 1 || out_dim < 1) return MATGCN_ERR_BAD_ARG;
+  const int64_t rowLen = (int64_t)nodes * out_dim, outLen = (int64_t)n_groups * out_dim;   // < 2^62
+  if (rows > INT64_MAX / rowLen || rows > INT64_MAX / outLen) return MATGCN_ERR_BAD_ARG;
+  if (rowLen > INT32_MAX || outLen > INT32_MAX / GROUP_MAX_ROWS) return MATGCN_ERR_UNSUPPORTED;
+  return MATGCN_OK;
+}
+int group_walk(GroupWalkArgs& a, int64_t rows, hipStream_t s) {
+  a.total = (long long)rows * a.map.G * a.od;
+  const long long blocks = (a.total + GROUP_THREADS - 1) / GROUP_THREADS;
+  if (blocks > INT32_MAX) return MATGCN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(k_group_walk, dim3((unsigned)blocks), dim3(GROUP_THREADS), 0, s, a);
+  return launch_ok();
+}
+}  // namespace
+
+int matgcn_group_sums(const float* values, int64_t rows, int nodes, int out_dim, const matgcn_metric_scale* scale,
+                      const matgcn_groups* groups, float* out, void* stream) {
+  if (!values || !out) return MATGCN_ERR_NULL;
+  McScale sc;
+  RETURN_IF(mc_scale(scale, &sc));
+  GroupMap map;
+  RETURN_IF(group_map(groups, &map));
+  RETURN_IF(group_shape(rows, nodes, out_dim, map.G));
+  const int rowLen = nodes * out_dim, stride = rowLen | 1;
+  hipStream_t s = (hipStream_t)stream;
+  if (stride > GROUP_TILE_FLOATS) {      // a row that no tile holds: walk it in global memory
+    GroupWalkArgs w;
+    memset(&w, 0, sizeof(w));
+    w.src = values; w.N = nodes; w.od = out_dim; w.sc = sc; w.map = map; w.out = out;
+    return group_walk(w, rows, s);
+  }
+  // rows per tile: what 32 KB hold (a longer row: that row alone), a multiple of 4 where it can be (a tile then starts
+  // 16-byte aligned whenever the tensor does), halved while that leaves fewer than 1024 tiles to spread over the CUs
+  int R = stride > GROUP_ROWS_FLOATS ? 1 : GROUP_ROWS_FLOATS / stride;
+  // the map goes into LDS behind the rows when it is small (its offsets, and its weights if any)
+  const int mapFloats = groups->n_members <= GROUP_MAP_FLOATS ? groups->n_members * (groups->weight ? 2 : 1) : INT32_MAX;
+  const bool staged = mapFloats <= GROUP_MAP_FLOATS && R * stride + mapFloats <= GROUP_TILE_FLOATS;
+  if (R > GROUP_MAX_ROWS) R = GROUP_MAX_ROWS;
+  if (R > 4) R &= ~3;
+  while (R > 4 && (rows + R - 1) / R < 1024) R = (R / 2 + 3) & ~3;
+  const int64_t tiles = (rows + R - 1) / R;
+  if (tiles > INT32_MAX) return MATGCN_ERR_UNSUPPORTED;
+  GroupTileArgs a;
+  a.values = values; a.rows = rows; a.N = nodes; a.od = out_dim; a.rowLen = rowLen; a.stride = stride; a.R = R;
+  a.mapAt = staged ? R * stride : -1; a.members = groups->n_members;
+  a.stepQuot = 4 * GROUP_THREADS / rowLen; a.stepRem = 4 * GROUP_THREADS % rowLen;
+  a.sc = sc; a.map = map; a.out = out;
+  const size_t ldsFloats = (size_t)R * stride + (staged ? mapFloats : 0);       // <= GROUP_TILE_FLOATS
+  hipLaunchKernelGGL(k_group_sums_tile, dim3((unsigned)tiles), dim3(GROUP_THREADS), ldsFloats * sizeof(float), s, a);
+  return launch_ok();
+}
+
+int matgcn_group_label_sums(const float* y, const int32_t* label_start, int batch, int out_steps, int nodes, int out_dim,
+                            int y_steps, int y_feat, int y_start, const matgcn_metric_scale* scale,
+                            const matgcn_groups* groups, float* out, void* stream) {
+  if (!y || !out) return MATGCN_ERR_NULL;
+  GroupWalkArgs w;
+  memset(&w, 0, sizeof(w));
+  RETURN_IF(mc_scale(scale, &w.sc));
+  RETURN_IF(group_map(groups, &w.map));
+  if (batch < 1 || out_steps < 1) return MATGCN_ERR_BAD_ARG;
+  RETURN_IF(group_shape((int64_t)batch * out_steps, nodes, out_dim, w.map.G));
+  if (y_steps < 1 || (!label_start && y_steps < out_steps) || y_feat < 1 || y_start < 0 || y_start + out_dim > y_feat)
+    return MATGCN_ERR_BAD_ARG;
+  w.src = y; w.labelStart = label_start; w.labels = 1;
+  w.outSteps = out_steps; w.ySteps = y_steps; w.yFeat = y_feat; w.yStart = y_start;
+  w.N = nodes; w.od = out_dim; w.out = out;
+  return group_walk(w, (int64_t)batch * out_steps, (hipStream_t)stream);
 }
 
 // ---- global gradient norm, clip and Adam over a table of tensors (matgcn_optim.hip) --------------------------------------

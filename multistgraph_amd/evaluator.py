@@ -15,6 +15,10 @@ batches of a test set on the device (matgcn_mc_scores).  The reference has no su
 conformity scores of a held-out split, kept, ranked and applied on the device (matgcn_mc_conformity,
 matgcn_conformal_quantile, matgcn_conformal_coverage).
 
+``RegionEvaluator`` is ``NodeEvaluator`` over the totals of groups of nodes (regions.RegionMap): predictions, samples and
+labels are summed per region first (matgcn_group_sums / matgcn_group_label_sums), then scored with the same kernels;
+``ConformalCalibrator(regions=...)`` calibrates the band of those totals.
+
 HIP path only: CPU tensors raise.
 """
 from __future__ import annotations
@@ -24,8 +28,8 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib
-from .ops import (conformal_coverage, conformal_quantile, mc_conformity, mc_scores, mc_scores_nodes, metric_sums,
-                  metric_sums_nodes, metric_table, metric_table_rows)
+from .ops import (conformal_coverage, conformal_quantile, group_label_sums, group_sums, mc_conformity, mc_scores,
+                  mc_scores_nodes, metric_sums, metric_sums_nodes, metric_table, metric_table_rows)
 
 ALLOWED_METRICS = list(_lib.METRICS)
 
@@ -253,6 +257,54 @@ class NodeEvaluator:
         return torch.cat([order[~nan[order]], order[nan[order]]])
 
 
+def _region_totals(regions, values, y, y_start, mean, std, group, member_clamp, label_start):
+    """(totals of ``values`` (..., out, N, od), totals of the labels (B, out, G, od)) on the re-transformed scale: members
+    de-scaled by mean / std and the group pair; predictions and samples clamped at ``member_clamp``, labels never"""
+    gm, gs = group if group is not None else (None, None)
+    totals = group_sums(values, regions, mean, std, gm, gs, member_clamp)
+    labels = group_label_sums(y, regions, int(values.shape[-3]), int(values.shape[-1]), y_start, mean, std, gm, gs,
+                              label_start=label_start)
+    return totals, labels
+
+
+class RegionEvaluator(NodeEvaluator):
+    """``NodeEvaluator`` with one row per region of ``regions`` (regions.RegionMap) in place of one per node: the error
+    and the scores of a region TOTAL, which are not the sums of its tracts' (errors of opposite sign cancel in a total,
+    and quantiles do not add).  Each batch is summed per region first - members de-scaled by the scaler and the
+    ``group_mean`` / ``group_std`` pair, predictions and samples below 0 set to 0 when the pair is given, then added in
+    the map's order (matgcn_group_sums, matgcn_group_label_sums) - and the totals go through matgcn_metric_sums_nodes /
+    matgcn_mc_scores_nodes with an identity scale.  Region-level conventions: a NaN label is the only mask (it makes its
+    regions' totals NaN), ``min_s`` is off, ``s_small`` filters on the region's true total, R2 / EVAR exchange prediction
+    and truth as in the re-transform table.  Tables and ``rank`` are those of ``NodeEvaluator`` with G rows; any split
+    of a test set into batches gives the same bits."""
+
+    def __init__(self, config, regions, probs=None, group_mean=None, group_std=None, s_small=None):
+        super().__init__(config, probs, group_mean, group_std, s_small)
+        self.regions = regions
+        self.member_clamp = self.clamp_min
+        self.clamp_min, self.min_s, self.null_val, self.swap_r2 = float("nan"), -1.0, float("nan"), True
+
+    def _level(self):
+        return dict(clamp_min=float("nan"), truth_min=self.truth_min, min_s=-1.0)
+
+    def collect_scaled(self, pred, y, y_start: int = 0, mean=None, std=None, label_start=None):
+        if (mean is None) != (std is None):
+            raise ValueError("mean and std come as a pair")
+        totals, labels = _region_totals(self.regions, pred, y, y_start, mean, std, self.group, self.member_clamp,
+                                        label_start)
+        self._metric_sums = metric_sums_nodes(totals, labels, 0, sums=self._metric_sums, **self._level())
+
+    def collect_samples(self, samples, y, y_start: int = 0, mean=None, std=None, label_start=None):
+        if self.probs is None:
+            raise RuntimeError("this evaluator was built without probs: no probabilistic scores")
+        if (mean is None) != (std is None):
+            raise ValueError("mean and std come as a pair")
+        totals, labels = _region_totals(self.regions, samples, y, y_start, mean, std, self.group, self.member_clamp,
+                                        label_start)
+        self._score_sums = mc_scores_nodes(totals, labels, self.probs, 0, null_val=float("nan"), sums=self._score_sums,
+                                           **self._level())
+
+
 def _f32(v) -> float:
     """the double of the float32 nearest to v: what the kernels see of a level"""
     return float(torch.tensor(float(v), dtype=torch.float32))
@@ -285,10 +337,14 @@ class ConformalCalibrator:
     Scale as ``NodeEvaluator``: with ``group_mean`` / ``group_std`` the re-transform, clamp at 0, NaN null value, no
     ``min_s``; without them the config's ``min_s`` and null value 0.  ``s_small`` leaves out labels at or below it.  The
     scaler's affine is the one of the first ``collect_samples`` call; bands passed to ``apply`` must be on that scale.
-    Only ``evaluate`` / ``coverage_table`` / ``state_dict`` read the device."""
+    Only ``evaluate`` / ``coverage_table`` / ``state_dict`` read the device.
+
+    ``regions`` (regions.RegionMap): the band of the region totals is calibrated instead - samples and labels are summed
+    per region first, as ``RegionEvaluator`` does (NaN the only mask, no ``min_s``, ``s_small`` on the region's true
+    total), "element" then means (horizon, region, channel), and ``apply`` takes bands (levels, ..., out, G, od)."""
 
     def __init__(self, config, probs=(0.05, 0.5, 0.95), grouping="horizon", group_mean=None, group_std=None, s_small=None,
-                 capacity: int = 256):
+                 capacity: int = 256, regions=None):
         if (group_mean is None) != (group_std is None):
             raise ValueError("group_mean and group_std come as a pair")
         self.probs = _check_probs(probs)
@@ -308,6 +364,7 @@ class ConformalCalibrator:
         self.clamp_min = float("nan") if self.group is None else 0.0
         self.min_s = float(config.get("min_s", 1e-4)) if self.group is None else -1.0
         self.null_val = 0.0 if self.group is None else float("nan")
+        self.regions = regions
         self.affine = None                                    # (mean, std) of the scaler, set by the first batch
         self.margin: Optional[torch.Tensor] = None            # (out,) or (out, N, od) float32
         self.count: Optional[torch.Tensor] = None             # the same shape, int32
@@ -331,14 +388,26 @@ class ConformalCalibrator:
         elif not on_device and not (_same_vector(self.affine[0], mean) and _same_vector(self.affine[1], std)):
             # (device tensors are taken on trust here: comparing them would read the device on every batch)
             raise ValueError("this calibrator collects on the scale mean, std = %s, got %s" % (self.affine, (mean, std)))
+        if self.regions is not None:
+            totals, labels = _region_totals(self.regions, samples, y, y_start, mean, std, self.group, self.clamp_min,
+                                            label_start)
+            return mc_conformity(totals, labels, self.probs, 0, clamp_min=float("nan"), truth_min=self.truth_min,
+                                 min_s=-1.0, null_val=float("nan"), out=out)
         gm, gs = self.group if self.group is not None else (None, None)
         return mc_conformity(samples, y, self.probs, y_start, mean, std, gm, gs, self.clamp_min, self.truth_min,
                              self.min_s, self.null_val, label_start, out=out)
 
+    def _score_shape(self, samples, lead: int):
+        """the shape of the scores of a batch of samples (S, B, out, N, od) from axis ``lead`` on"""
+        shape = [int(v) for v in samples.shape]
+        if self.regions is not None:
+            shape[3] = self.regions.num_groups
+        return tuple(shape[lead:])
+
     def collect_samples(self, samples, y, y_start: int = 0, mean=None, std=None, label_start=None):
         """One calibration batch: arguments as ``NodeEvaluator.collect_samples``.  Appends its B rows of scores to the
         store, which doubles its capacity when full."""
-        b, shape = int(samples.shape[1]), tuple(int(v) for v in samples.shape[2:])
+        b, shape = int(samples.shape[1]), self._score_shape(samples, 2)
         if self._store is not None and tuple(self._store.shape[1:]) != shape:
             raise ValueError("batch of shape %s after batches of shape %s" % (shape, tuple(self._store.shape[1:])))
         need, have = self._rows + b, 0 if self._store is None else int(self._store.shape[0])
@@ -383,9 +452,12 @@ class ConformalCalibrator:
             out[-1].clamp_(min=self.clamp_min)
         return out
 
-    def check_call(self, probs, affine, group_mean, group_std, clamp_min):
-        """ValueError unless a band of levels ``probs`` on the scale (affine, group pair, clamp) is one this calibrator's
-        margin applies to"""
+    def check_call(self, probs, affine, group_mean, group_std, clamp_min, regions=None):
+        """ValueError unless a band of levels ``probs`` on the scale (affine, group pair, clamp), of the totals of
+        ``regions`` (None: per node), is one this calibrator's margin applies to"""
+        if (self.regions is None) != (regions is None) or (regions is not None and self.regions != regions):
+            raise ValueError("the calibrator was fitted on %s, the call asks for %s"
+                             % ("nodes" if self.regions is None else self.regions, "nodes" if regions is None else regions))
         if _check_probs(probs) != self.probs:
             raise ValueError("the calibrator was built for the levels %s, the call asks for %s" % (self.probs, tuple(probs)))
         mine = self.affine if self.affine is not None else (None, None)
@@ -401,7 +473,7 @@ class ConformalCalibrator:
     def collect_test_samples(self, samples, y, y_start: int = 0, mean=None, std=None, label_start=None):
         """One test batch: counts per group how many of its valid scores the fitted margin covers."""
         margin = self._fitted().to(samples.device)
-        shape = tuple(int(v) for v in samples.shape[1:])
+        shape = self._score_shape(samples, 1)
         if self._batch_scores is None or tuple(self._batch_scores.shape) != shape:
             self._batch_scores = torch.empty(shape, dtype=torch.float32, device=samples.device)
         scores = self._scores(samples, y, y_start, mean, std, label_start, self._batch_scores)
@@ -439,6 +511,7 @@ class ConformalCalibrator:
         return {"margin": None if self.margin is None else self.margin.detach().cpu().clone(),
                 "count": None if self.count is None else self.count.detach().cpu().clone(),
                 "probs": tuple(self.probs), "grouping": self.grouping,
+                "regions": None if self.regions is None else self.regions.state_dict(),
                 "scale": {"mean": cpu(am), "std": cpu(asd), "group_mean": cpu(gm), "group_std": cpu(gs),
                           "clamp_min": self.clamp_min, "truth_min": self.truth_min, "min_s": self.min_s,
                           "null_val": self.null_val}}
@@ -454,6 +527,11 @@ class ConformalCalibrator:
         self.affine = None if sc["mean"] is None else (sc["mean"], sc["std"])
         self.clamp_min, self.truth_min = float(sc["clamp_min"]), float(sc["truth_min"])
         self.min_s, self.null_val = float(sc["min_s"]), float(sc["null_val"])
+        if state.get("regions") is None:
+            self.regions = None
+        else:
+            from .regions import RegionMap
+            self.regions = RegionMap.from_state_dict(state["regions"])
         self.margin = None if state["margin"] is None else state["margin"].clone()
         self.count = None if state["count"] is None else state["count"].clone()
         self.clear()

@@ -24,8 +24,8 @@ import torch.nn as nn
 
 from . import graph_prep
 from . import hidden_pad
-from .ops import (HotPath, PathSpec, diagonal_mask, masked_mae_device, masked_mae_loss, mc_quantiles, mc_quantiles_scaled,
-                  mc_scores, spec_from_config, train_loss_desc, train_loss_device)
+from .ops import (HotPath, PathSpec, diagonal_mask, group_sums, masked_mae_device, masked_mae_loss, mc_quantiles,
+                  mc_quantiles_scaled, mc_scores, spec_from_config, train_loss_desc, train_loss_device)
 from .ops import train_loss as train_loss_autograd
 
 try:  # inside a LibCity checkout: subclass the real plugin base so isinstance checks hold
@@ -451,7 +451,8 @@ class MultiATGCN(AbstractTrafficStateModel):
                                  keep_samples=keep_samples)
 
     def predict_interval(self, batch, samples: int = 32, probs=(0.05, 0.5, 0.95), seed: Optional[int] = None,
-                         group_mean=None, group_std=None, clamp_min: Optional[float] = None, calibrator=None):
+                         group_mean=None, group_std=None, clamp_min: Optional[float] = None, calibrator=None,
+                         regions=None):
         """Monte-Carlo-dropout forecast with its empirical band: (mean, std, quantiles) in the units of ``predict`` -
         mean and std what ``predict_mc`` gives for the same seed, quantiles (len(probs), B, out, N, od) the levels
         ``probs`` (up to 8, ascending, in [0, 1]) of the ``samples`` forecasts per output element, numpy's "linear" rule
@@ -463,7 +464,27 @@ class MultiATGCN(AbstractTrafficStateModel):
         ``calibrator`` (a fitted evaluator.ConformalCalibrator; None: the empirical band as it is): the outer two
         levels are widened by its margin (``calibrator.apply``).  Its levels and its scale must be those of this call
         - the scaler's affine (the identity for the band in the units of ``predict``), the group pair and the clamp -,
-        anything else is a ValueError."""
+        anything else is a ValueError.
+        ``regions`` (a regions.RegionMap): the forecast of the region TOTALS, (mean, std, quantiles) with G regions in
+        place of the N nodes.  Every sample is summed per region first - members go through the scaler's inverse (always:
+        a total is in visits; needs an affine scaler), then ``group_mean`` / ``group_std`` and ``clamp_min`` as above, and
+        are added in the map's order (matgcn_group_sums: one read of the samples, the same bits every run) -, quantiles
+        (len(probs), B, out, G, od) are matgcn_mc_quantiles of the summed samples (quantiles do not add), and mean and std
+        (population) are taken over the summed samples with torch: that tensor is S*B*out*G*od floats, a few MB.  A
+        ``calibrator`` must have been fitted on the same map (ConformalCalibrator(regions=...))."""
+        if regions is not None:
+            affine = self._affine_scaler()
+            if affine is None:
+                raise NotImplementedError("region totals need an affine scaler (StandardScaler / NoneScaler)")
+            if calibrator is not None:
+                if calibrator.margin is None:
+                    raise ValueError("the calibrator is not fitted: call calibrate_mc over a held-out split, then fit()")
+                calibrator.check_call(probs, affine, group_mean, group_std, clamp_min, regions)
+            kept = self.predict_mc(batch, samples=samples, seed=seed, keep_samples=True)[2]
+            totals = group_sums(kept, regions, affine[0], affine[1], group_mean, group_std,
+                                float("nan") if clamp_min is None else clamp_min)
+            band = mc_quantiles(totals, probs)
+            return totals.mean(0), totals.std(0, unbiased=False), band if calibrator is None else calibrator.apply(band)
         plain = group_mean is None and group_std is None and clamp_min is None
         affine = None if plain else self._affine_scaler()
         if not plain and affine is None:
@@ -479,6 +500,18 @@ class MultiATGCN(AbstractTrafficStateModel):
             band = mc_quantiles_scaled(kept, probs, affine[0], affine[1], group_mean, group_std,
                                        float("nan") if clamp_min is None else clamp_min)
         return mean, std, band if calibrator is None else calibrator.apply(band)
+
+    def predict_regions(self, batch, regions, group_mean=None, group_std=None, clamp_min: Optional[float] = None):
+        """The point forecast's region totals (B, out, G, od), in visits: ``predict``, then every member through the
+        scaler's inverse, ``group_mean`` / ``group_std`` (one value per node, a pair) and ``clamp_min``, added in the
+        order ``regions`` (a regions.RegionMap) lists them (matgcn_group_sums).  Needs an affine scaler."""
+        affine = self._affine_scaler()
+        if affine is None:
+            raise NotImplementedError("region totals need an affine scaler (StandardScaler / NoneScaler)")
+        with torch.no_grad():
+            pred = self.predict(batch)
+        return group_sums(pred.detach(), regions, affine[0], affine[1], group_mean, group_std,
+                          float("nan") if clamp_min is None else clamp_min)
 
     def score_mc(self, batch, samples: int = 32, probs=(0.05, 0.5, 0.95), seed: Optional[int] = None, sums=None):
         """The (out, 5 + len(probs)) float64 per-horizon sums [count, CRPS, covered, width, Winkler, pinball per level] of
@@ -655,6 +688,17 @@ class MultiATGCN(AbstractTrafficStateModel):
         """``collect_metrics`` per node: the same batch reduced into an evaluator.NodeEvaluator - the ten metrics per
         (horizon, node) on its scale (matgcn_metric_sums_nodes).  Returns the prediction (scaled)."""
         return self.collect_metrics(evaluator, batch)
+
+    def collect_region_metrics(self, evaluator, batch):
+        """``collect_metrics`` per region: the same batch reduced into an evaluator.RegionEvaluator - the ten metrics of the
+        region totals per (horizon, region).  Window and resident-series batches.  Returns the prediction (scaled)."""
+        return self.collect_metrics(evaluator, batch)
+
+    def score_mc_regions(self, batch, evaluator, samples: int = 32, seed: Optional[int] = None):
+        """``score_mc_nodes`` per region: one Monte-Carlo-dropout ensemble of the batch, summed per region sample by sample
+        and reduced into ``evaluator`` (evaluator.RegionEvaluator built with ``probs``).  Window and resident-series
+        batches.  Returns the samples (S, B, out, N, od), scaled."""
+        return self.score_mc_nodes(batch, evaluator, samples=samples, seed=seed)
 
     def gradient_exchange(self):
         """(bucket, leftovers) for the gradient exchange of data-parallel training after ``loss.backward()``:

@@ -656,6 +656,67 @@ def conformal_coverage(scores: torch.Tensor, rows: int, grouping, margin: torch.
     return counts
 
 
+def _region_groups(regions, n: int, device):
+    if regions.num_nodes != n:
+        raise _lib.MatgcnError("the region map covers %d nodes, the tensor has %d" % (regions.num_nodes, n))
+    return regions.groups_on(device)
+
+
+def _group_out(out, shape, device):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or out.device != device or not out.is_contiguous():
+        raise _lib.MatgcnError("out must be a contiguous CUDA float32 tensor of shape %s" % (tuple(shape),))
+    return out
+
+
+def group_sums(values: torch.Tensor, regions, mean=None, std=None, group_mean=None, group_std=None,
+               clamp_min: float = float("nan"), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Region totals of ``values`` (..., N, od) -> (..., G, od) (matgcn_group_sums): every member de-scaled by mean / std
+    (scalars or one pair per node), then by the per-node group_mean / group_std, set to ``clamp_min`` where below it, and
+    added in the order ``regions`` (a regions.RegionMap) lists it - one fp64 chain per total, rounded to float32 once.
+    Each row is read once; the same bits every run.  ``out``: the tensor to write (every element is written)."""
+    lib = _lib.load()
+    values = _check_tensor(values, "values")
+    if values.dim() < 2:
+        raise _lib.MatgcnError("values has shape %s, expected (..., N, od)" % (tuple(values.shape),))
+    n, od = int(values.shape[-2]), int(values.shape[-1])
+    groups = _region_groups(regions, n, values.device)
+    rows = values.numel() // (n * od) if n * od else 0
+    sc, keep = _metric_scale(n, values.device, mean, std, group_mean, group_std, clamp_min, float("nan"), -1.0)
+    out = _group_out(out, tuple(values.shape[:-2]) + (regions.num_groups, od), values.device)
+    stream = C.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)
+    _lib.check(lib.matgcn_group_sums(C.c_void_p(values.data_ptr()), rows, n, od, C.byref(sc), C.byref(groups),
+                                     C.c_void_p(out.data_ptr()), stream), "matgcn_group_sums")
+    del keep
+    return out
+
+
+def group_label_sums(y: torch.Tensor, regions, out_steps: int, out_dim: int, y_start: int = 0, mean=None, std=None,
+                     group_mean=None, group_std=None, clamp_min: float = float("nan"),
+                     label_start: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B, out_steps, G, out_dim) region totals of the labels of a batch (matgcn_group_label_sums): ``y`` windows
+    (B, y_steps, N, F), or with ``label_start`` (B) the resident series (T, N, F); channels y_start .. y_start+out_dim-1;
+    arithmetic and order as ``group_sums``.  A NaN label makes the totals of its regions NaN."""
+    lib = _lib.load()
+    if y.dim() not in (3, 4):
+        raise _lib.MatgcnError("y has shape %s, expected (B, y_steps, N, F) or the series (T, N, F)" % (tuple(y.shape),))
+    n = int(y.shape[-2])
+    b = int(y.shape[0]) if label_start is None else int(label_start.shape[0])
+    out_steps, out_dim = int(out_steps), int(out_dim)
+    out = _group_out(out, (b, out_steps, regions.num_groups, out_dim), y.device)
+    y, label_start, y_steps, y_feat = _label_geometry(torch.empty(b, out_steps, n, out_dim, device="meta"), y,
+                                                      label_start)
+    groups = _region_groups(regions, n, y.device)
+    sc, keep = _metric_scale(n, y.device, mean, std, group_mean, group_std, clamp_min, float("nan"), -1.0)
+    stream = C.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)
+    _lib.check(lib.matgcn_group_label_sums(C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(label_start)), b, out_steps, n,
+                                           out_dim, y_steps, y_feat, int(y_start), C.byref(sc), C.byref(groups),
+                                           C.c_void_p(out.data_ptr()), stream), "matgcn_group_label_sums")
+    del keep
+    return out
+
+
 def _opt_tensor(t, name: str) -> torch.Tensor:
     """an optimizer tensor as the C ABI wants it - the caller's own memory, so nothing is copied or converted here"""
     if not isinstance(t, torch.Tensor):
