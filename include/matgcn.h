@@ -54,6 +54,8 @@
  * Still ABI 12: new names only - conformal calibration of the Monte-Carlo-dropout band adds the functions
  * matgcn_mc_conformity, matgcn_conformal_quantile and matgcn_conformal_coverage; no existing symbol, signature, struct or
  * value changed, and no existing entry point launches anything else than it did.
+ * Still ABI 12: new names only - the region-level training loss adds the functions matgcn_region_loss_bytes,
+ * matgcn_region_loss and matgcn_region_loss_grad; no existing symbol, signature, struct or value changed.
  */
 #ifndef MATGCN_H
 #define MATGCN_H
@@ -704,6 +706,66 @@ int matgcn_group_sums(const float* values, int64_t rows, int nodes, int out_dim,
 int matgcn_group_label_sums(const float* y, const int32_t* label_start, int batch, int out_steps, int nodes, int out_dim,
                             int y_steps, int y_feat, int y_start, const matgcn_metric_scale* scale,
                             const matgcn_groups* groups, float* out /* (batch, out_steps, n_groups, out_dim) */,
+                            void* stream);
+
+/* ---- a training objective on region totals, value and gradient (matgcn_region_loss.hip) ------------------------------------
+ * Still ABI 12: new names only.  Training on  tract_weight * L(tracts) + region_weight * L(region totals):  the first term
+ * is matgcn_loss / matgcn_loss_grad, the second this pair, with any of the seven kinds.
+ * Inputs: pred (B, out, N, od), labels with the geometry of matgcn_loss, a matgcn_loss_desc, and the region map in two
+ * forms: by group (the matgcn_groups of matgcn_group_sums) and, for the gradient, by node (below).
+ * Totals.  P = matgcn_group_sums(pred), L = matgcn_group_label_sums(y), both with the descriptor's scalar (mean, std) as the
+ * first affine, no second affine and no clamp: the bits of those entry points, fp32, (B*out, G, od), kept in scratch.
+ * Value.  matgcn_loss on (P, L) with nodes = G, an identity affine (mean 0, std 1) and the descriptor's kind, null_val,
+ * min_s and delta: result[0] the objective over all horizons, result[1 + k] horizon k - bit for bit the composition of the
+ * three entry points.  Masking therefore acts on totals: a region whose label total is NaN (any NaN member) is left out
+ * under the NaN-null kinds; under null_val = 0 a region is zeroed and masked only when its TOTAL is below min_s; a masked
+ * tract simply adds its value to its regions.
+ * Gradient.  Per region element (r, g, c): q = fp32(slope * keep), slope = dt/dp of the table above at (P, L, d = P - L);
+ * q = 0 where the forward replaced a NaN term by 0; RMSE: q divided by 2 rmse, every q = 0 when rmse == 0 - the g of
+ * matgcn_loss_grad before its final scaling, rounded to fp32 ONCE.  The rounding is deliberate: (double)w * (double)q is
+ * then exact in fp64, so a contracted fma gives the bits of multiply then add (the idiom of matgcn_group_sums) and no
+ * compiler flag decides the result.  Per tract element (r, n, c): acc = 0.0 in fp64; for each membership of node n, in
+ * ascending member position k of the by-group map, acc += (double)weight[k] * (double)q[r, group[k], c] (weight null = 1);
+ * part = ((double)upstream[0] * (double)std) * acc / cnt, where cnt is the kept count the value call left in scratch
+ * (masked kinds) or B*out*G*od (the others), and cnt == 0 gives part = 0;  d_pred = fp32(part), or with a non-null base
+ * d_pred = fp32((double)base + part).  base has the shape of d_pred and may alias it.  A node in no region gets base's
+ * bits, or +0.0 without a base.  EVERY element of d_pred is written.
+ * One thread owns a chain from end to end: no atomics, nothing allocated, the caller's stream only, and the result does
+ * not depend on the order workgroups run in - the same bits every run.  The gradient reads pred and y only through the
+ * totals in scratch: it touches scratch, the by-node map, base, d_pred and upstream.  A workgroup computes the q of a tile
+ * of rows into LDS (at most 8192 floats) and keeps a by-node map of up to 16 KB beside them; with G * out_dim above 8192
+ * the coefficients are recomputed per membership from the totals in global memory instead: same chain, same bits.
+ * by_node is the transposed map in the same struct: n_groups = nodes, ptr (nodes + 1 entries, read on the HOST and checked
+ * like the by-group ptr; its last entry must equal by_group->n_members), node[e] a GROUP index (clamped into 0 .. G-1 in
+ * the kernel, as the forward clamps node indices), weight[e] that membership's weight (null with a null by-group weight);
+ * the entries of a node in ascending member position of the by-group map.  The library does not verify that the two maps
+ * agree: regions.RegionMap builds one from the other.
+ * scratch: caller-owned, 8-byte aligned device memory of matgcn_region_loss_bytes: the two total tensors, matgcn_loss's own
+ * scratch for (B, out, G, od), then the descriptor's (mean, std) as two floats where the total kernels read them.  The
+ * gradient call takes the scratch its value call left, like matgcn_loss_grad; every word read is written first by the same
+ * pair of calls.
+ * Argument checks, before any launch, as matgcn_loss and matgcn_group_sums: null pointers MATGCN_ERR_NULL; geometry
+ * (out_steps in 1 .. 64), kind, delta, either map's ptr, a misaligned scratch, a by_node whose n_groups is not `nodes` or
+ * whose member count differs - MATGCN_ERR_BAD_ARG; a short scratch MATGCN_ERR_SMALL_BUFFER; index spaces of 2^31 or more
+ * MATGCN_ERR_UNSUPPORTED.
+ * Measured at Baltimore 403 / B = 64 / out = 24, tract weight 1, region weight 0.5 (MI355X, tools/region_loss_time.py, one
+ * process, routes alternating three times, median of 30 steps, HIP events), ten regions / the same
+ * plus one whole-city group, forward + backward of the loss alone over masked_mae, huber, masked_mse: the four calls of
+ * both levels behind ops.tract_region_loss 0.285-0.289 / 0.286-0.290 ms; torch de-scale + dense-membership matmul + closure
+ * arithmetic + autograd on both levels 0.747-0.789 / 0.767-0.794 ms (spread at most 0.048 ms: every gap is above twice it);
+ * the tract-level pair alone 0.177-0.184 ms - all host-bound (the enqueue time is within 0.007 ms of the device time).
+ * matgcn_region_loss_grad alone 0.0158-0.0161 ms against 0.0095-0.0097 ms for one plain read of the totals plus one write
+ * of d_pred: 1.65x to 1.68x, not at memory speed.  The whole training step 21.80 / 21.86 ms with the region term against
+ * 21.63 / 21.60 ms without: about 1 % more, not level. */
+int matgcn_region_loss_bytes(int batch, int out_steps, int n_groups, int out_dim, size_t* bytes);
+int matgcn_region_loss(const float* pred, const float* y, const int32_t* label_start, int batch, int out_steps, int nodes,
+                       int out_dim, int y_steps, int y_feat, int y_start, const matgcn_loss_desc* desc,
+                       const matgcn_groups* by_group, void* scratch, size_t scratch_bytes,
+                       float* result /* 1 + out_steps */, void* stream);
+int matgcn_region_loss_grad(const float* pred, const float* y, const int32_t* label_start, int batch, int out_steps,
+                            int nodes, int out_dim, int y_steps, int y_feat, int y_start, const matgcn_loss_desc* desc,
+                            const matgcn_groups* by_group, const matgcn_groups* by_node, const void* scratch,
+                            size_t scratch_bytes, const float* upstream, const float* base /* or NULL */, float* d_pred,
                             void* stream);
 
 /* ---- the optimizer step: global gradient norm, clip and Adam over a table of tensors -------------------------------------

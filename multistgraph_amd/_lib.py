@@ -183,6 +183,12 @@ _SIGNATURES = {
     "matgcn_group_sums": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.POINTER(MetricScale), C.POINTER(Groups), _P, _P]),
     "matgcn_group_label_sums": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(MetricScale), C.POINTER(Groups), _P, _P]),
+    "matgcn_region_loss_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "matgcn_region_loss": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.POINTER(LossDesc), C.POINTER(Groups), _P, C.c_size_t, _P, _P]),
+    "matgcn_region_loss_grad": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(LossDesc), C.POINTER(Groups), C.POINTER(Groups), _P, C.c_size_t, _P,
+                                          _P, _P, _P]),
     "matgcn_grad_norm_bytes":(C.c_int, [C.POINTER(OptTensor), C.c_int, C.POINTER(C.c_size_t)]),
     "matgcn_grad_norm": (C.c_int, [C.POINTER(OptTensor), C.c_int, _P, C.c_size_t, _P, _P]),
     "matgcn_adam_step": (C.c_int, [C.POINTER(OptTensor), C.c_int, C.POINTER(Adam), _P, _P]),

@@ -22,6 +22,7 @@
 #include "matgcn_regions.hip"
 #include "matgcn_optim.hip"
 #include "matgcn_loss.hip"
+#include "matgcn_region_loss.hip"
 
 namespace {
 
@@ -1828,6 +1829,137 @@ int matgcn_group_label_sums(const float* y, const int32_t* label_start, int batc
   w.outSteps = out_steps; w.ySteps = y_steps; w.yFeat = y_feat; w.yStart = y_start;
   w.N = nodes; w.od = out_dim; w.out = out;
   return group_walk(w, (int64_t)batch * out_steps, (hipStream_t)stream);
+}
+
+// ---- a training objective on region totals, value and gradient (matgcn_region_loss.hip) ------------------------------------
+namespace {
+// the scratch of the pair: the totals of the predictions, the totals of the labels (rows * G * od floats each, together a
+// multiple of 8 bytes), matgcn_loss's own scratch for (B, out, G, od), then the descriptor's (mean, std) as two floats,
+// which the total kernels read through their scale descriptor
+struct RegionScratch {
+  float* P; float* L;
+  double* loss; size_t lossBytes;
+  float* affine;
+  size_t bytes;
+};
+int region_scratch(int batch, int out_steps, int n_groups, int out_dim, void* scratch, RegionScratch* r) {
+  size_t lossBytes = 0;
+  RETURN_IF(matgcn_loss_bytes(batch, out_steps, &lossBytes));
+  if (n_groups < 1 || out_dim < 1) return MATGCN_ERR_BAD_ARG;
+  if ((int64_t)n_groups * out_dim > INT32_MAX / GROUP_MAX_ROWS) return MATGCN_ERR_UNSUPPORTED;
+  const size_t totals = (size_t)batch * out_steps * n_groups * out_dim;        // < 2^31 * 2^23
+  char* at = (char*)scratch;
+  r->P = (float*)at; r->L = r->P + totals;
+  r->loss = (double*)(at + 2 * totals * sizeof(float)); r->lossBytes = lossBytes;
+  r->affine = (float*)(at + 2 * totals * sizeof(float) + lossBytes);
+  r->bytes = 2 * totals * sizeof(float) + lossBytes + 2 * sizeof(float);
+  return MATGCN_OK;
+}
+// every check of the pair that does not concern the by-node map; fills the layout, the by-group map and the descriptor of
+// the objective on the totals: nodes = G, identity affine, the caller's kind, null value, min_s and delta
+int region_check(int batch, int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start,
+                 const matgcn_loss_desc* desc, const matgcn_groups* by_group, const void* scratch, size_t scratch_bytes,
+                 RegionScratch* rs, GroupMap* map, matgcn_loss_desc* onTotals) {
+  LossArgs a;
+  RETURN_IF(loss_check(batch, out_steps, nodes, out_dim, y_steps, y_feat, y_start, desc, SIZE_MAX, &a));
+  RETURN_IF(group_map(by_group, map));
+  RETURN_IF(group_shape((int64_t)batch * out_steps, nodes, out_dim, map->G));
+  RETURN_IF(region_scratch(batch, out_steps, map->G, out_dim, const_cast<void*>(scratch), rs));
+  *onTotals = *desc;
+  onTotals->mean = 0.f; onTotals->std = 1.f;
+  RETURN_IF(loss_check(batch, out_steps, map->G, out_dim, out_steps, out_dim, 0, onTotals, SIZE_MAX, &a));
+  if (scratch_bytes < rs->bytes) return MATGCN_ERR_SMALL_BUFFER;
+  if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return MATGCN_ERR_BAD_ARG;
+  return MATGCN_OK;
+}
+}  // namespace
+
+int matgcn_region_loss_bytes(int batch, int out_steps, int n_groups, int out_dim, size_t* bytes) {
+  if (!bytes) return MATGCN_ERR_NULL;
+  RegionScratch rs;
+  RETURN_IF(region_scratch(batch, out_steps, n_groups, out_dim, nullptr, &rs));
+  *bytes = rs.bytes;
+  return MATGCN_OK;
+}
+
+int matgcn_region_loss(const float* pred, const float* y, const int32_t* label_start, int batch, int out_steps, int nodes,
+                       int out_dim, int y_steps, int y_feat, int y_start, const matgcn_loss_desc* desc,
+                       const matgcn_groups* by_group, void* scratch, size_t scratch_bytes, float* result, void* stream) {
+  if (!pred || !y || !desc || !by_group || !scratch || !result) return MATGCN_ERR_NULL;
+  RegionScratch rs;
+  GroupMap map;
+  matgcn_loss_desc onTotals;
+  RETURN_IF(region_check(batch, out_steps, nodes, out_dim, y_steps, y_feat, y_start, desc, by_group, scratch,
+                         scratch_bytes, &rs, &map, &onTotals));
+  hipLaunchKernelGGL(k_region_affine, dim3(1), dim3(64), 0, (hipStream_t)stream, rs.affine, desc->mean, desc->std);
+  CHECK_LAUNCH();
+  matgcn_metric_scale scale;
+  memset(&scale, 0, sizeof(scale));
+  scale.mean = rs.affine; scale.std = rs.affine + 1;
+  scale.clamp_min = scale.truth_min = __builtin_nanf(""); scale.min_s = -1.f;
+  RETURN_IF(matgcn_group_sums(pred, (int64_t)batch * out_steps, nodes, out_dim, &scale, by_group, rs.P, stream));
+  RETURN_IF(matgcn_group_label_sums(y, label_start, batch, out_steps, nodes, out_dim, y_steps, y_feat, y_start, &scale,
+                                    by_group, rs.L, stream));
+  return matgcn_loss(rs.P, rs.L, nullptr, batch, out_steps, map.G, out_dim, out_steps, out_dim, 0, &onTotals, rs.loss,
+                     rs.lossBytes, result, stream);
+}
+
+int matgcn_region_loss_grad(const float* pred, const float* y, const int32_t* label_start, int batch, int out_steps,
+                            int nodes, int out_dim, int y_steps, int y_feat, int y_start, const matgcn_loss_desc* desc,
+                            const matgcn_groups* by_group, const matgcn_groups* by_node, const void* scratch,
+                            size_t scratch_bytes, const float* upstream, const float* base, float* d_pred, void* stream) {
+  (void)label_start;      // the totals in scratch are all the gradient reads of pred and y
+  if (!pred || !y || !desc || !by_group || !by_node || !scratch || !upstream || !d_pred) return MATGCN_ERR_NULL;
+  RegionScratch rs;
+  GroupMap map, nodeMap;
+  matgcn_loss_desc onTotals;
+  RETURN_IF(region_check(batch, out_steps, nodes, out_dim, y_steps, y_feat, y_start, desc, by_group, scratch,
+                         scratch_bytes, &rs, &map, &onTotals));
+  RETURN_IF(group_map(by_node, &nodeMap));
+  if (nodeMap.G != nodes || by_node->n_members != by_group->n_members) return MATGCN_ERR_BAD_ARG;
+  RegionGradArgs a;
+  memset(&a, 0, sizeof(a));
+  a.id.pred = rs.P; a.id.y = rs.L;
+  a.id.outSteps = out_steps; a.id.N = map.G; a.id.od = out_dim; a.id.ySteps = out_steps; a.id.yFeat = out_dim;
+  a.id.mean = 0.f; a.id.std = 1.f; a.id.nullVal = desc->null_val; a.id.minS = desc->min_s; a.id.delta = desc->delta;
+  a.kept = rs.loss + 2 * (size_t)batch * out_steps;
+  a.upstream = upstream; a.base = base; a.dpred = d_pred;
+  a.rows = (long long)batch * out_steps;
+  a.N = nodes; a.od = out_dim; a.rowLen = nodes * out_dim;
+  a.G = map.G; a.GC = map.G * out_dim;
+  a.members = by_node->n_members;
+  a.std = desc->std;
+  a.nptr = nodeMap.ptr; a.ngroup = nodeMap.node; a.nweight = nodeMap.weight;
+  hipStream_t s = (hipStream_t)stream;
+  if (a.GC > REGION_Q_FLOATS) {       // no tile holds one row's coefficients: recompute them per membership
+    const long long total = a.rows * a.rowLen;
+    const long long blocks = (total + REGION_THREADS - 1) / REGION_THREADS;
+    if (blocks > INT32_MAX) return MATGCN_ERR_UNSUPPORTED;
+#define REGION_WALK(K, M) \
+    hipLaunchKernelGGL((k_region_grad_walk<K, M>), dim3((unsigned)blocks), dim3(REGION_THREADS), 0, s, a, total);
+    LOSS_KIND_SWITCH(desc->kind, REGION_WALK)
+#undef REGION_WALK
+    return launch_ok();
+  }
+  // rows per tile: what the coefficient budget and 16 elements per thread allow, halved while that leaves fewer than
+  // REGION_MIN_TILES tiles to spread over the CUs
+  int R = REGION_Q_FLOATS / a.GC;
+  const int byElems = REGION_TILE_ELEMS / a.rowLen;
+  if (R > byElems) R = byElems < 1 ? 1 : byElems;
+  if (R > REGION_MAX_ROWS) R = REGION_MAX_ROWS;
+  while (R > 1 && (a.rows + R - 1) / R < REGION_MIN_TILES) R = (R + 1) / 2;
+  a.R = R;
+  const int mapFloats = a.members <= REGION_MAP_FLOATS ? a.members * (a.nweight ? 2 : 1) : INT32_MAX;
+  a.staged = mapFloats <= REGION_MAP_FLOATS;
+  const long long tiles = (a.rows + R - 1) / R;
+  if (tiles > INT32_MAX) return MATGCN_ERR_UNSUPPORTED;
+  const size_t ldsFloats = (size_t)R * a.GC + (a.staged ? mapFloats : 0);      // <= REGION_Q_FLOATS + REGION_MAP_FLOATS
+#define REGION_TILE(K, M)                                                                                       \
+  hipLaunchKernelGGL((k_region_grad_tile<K, M>), dim3((unsigned)tiles), dim3(REGION_THREADS), ldsFloats * sizeof(float), \
+                     s, a);
+  LOSS_KIND_SWITCH(desc->kind, REGION_TILE)
+#undef REGION_TILE
+  return launch_ok();
 }
 
 // ---- global gradient norm, clip and Adam over a table of tensors (matgcn_optim.hip) --------------------------------------

@@ -26,7 +26,9 @@ from . import graph_prep
 from . import hidden_pad
 from .ops import (HotPath, PathSpec, diagonal_mask, group_sums, masked_mae_device, masked_mae_loss, mc_quantiles,
                   mc_quantiles_scaled, mc_scores, spec_from_config, train_loss_desc, train_loss_device)
+from .ops import tract_region_loss
 from .ops import train_loss as train_loss_autograd
+from .regions import RegionMap
 
 try:  # inside a LibCity checkout: subclass the real plugin base so isinstance checks hold
     from libcity.model.abstract_traffic_state_model import AbstractTrafficStateModel  # type: ignore
@@ -45,6 +47,35 @@ except Exception:  # standalone: same two-level base (abstract_model.py:4-7, abs
         def __init__(self, config, data_feature):
             self.data_feature = data_feature
             super().__init__(config, data_feature)
+
+
+def _train_regions(value, num_nodes: int) -> Optional[RegionMap]:
+    """config['hip_train_regions'] as a RegionMap over the model's nodes: a RegionMap, its state_dict(), or one region
+    label per node; None stays None"""
+    if value is None:
+        return None
+    if isinstance(value, RegionMap):
+        regions = value
+    elif isinstance(value, dict):
+        regions = RegionMap.from_state_dict(value)
+    else:
+        labels = list(value)
+        if len(labels) != num_nodes:
+            raise ValueError("hip_train_regions: %d labels for %d nodes" % (len(labels), num_nodes))
+        regions = RegionMap(num_nodes, labels=labels)
+    if regions.num_nodes != num_nodes:
+        raise ValueError("hip_train_regions covers %d nodes, the model has %d" % (regions.num_nodes, num_nodes))
+    return regions
+
+
+def _loss_weight(value, key: str) -> float:
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError("%s = %r: expected a number" % (key, value)) from None
+    if not (math.isfinite(v) and v >= 0.0):
+        raise ValueError("%s = %r: expected a finite weight >= 0" % (key, value))
+    return v
 
 
 def masked_mae(preds: torch.Tensor, labels: torch.Tensor, null_val=float("nan"), min_s: float = 1e-4):
@@ -219,6 +250,19 @@ class MultiATGCN(AbstractTrafficStateModel):
         self.hip_train_loss_delta = get("hip_train_loss_delta", None)
         if self.hip_train_loss != "none":
             train_loss_desc(self.hip_train_loss, 0.0, 1.0, self.hip_train_loss_delta)   # ValueError on a bad name or delta
+        # config['hip_train_regions']: a regions.RegionMap, its state_dict() or one region label per node;
+        # config['hip_region_loss_weight'] (default 0.0 = off) and config['hip_tract_loss_weight'] (default 1.0): with a
+        # region weight > 0 calculate_loss / calculate_loss_series return
+        #   tract_weight * L(tracts) + region_weight * L(region totals)
+        # with L = hip_train_loss ("none": masked_mae through matgcn_loss) on both levels, value and gradient on the device
+        # (ops.tract_region_loss: matgcn_region_loss / matgcn_region_loss_grad).  Without the keys, or with weight 0,
+        # calculate_loss and its gradients keep their bits.  Attributes like the ones above: checkpoints are unchanged.
+        self.hip_train_regions = _train_regions(get("hip_train_regions", None), self.num_nodes)
+        self.hip_region_loss_weight = _loss_weight(get("hip_region_loss_weight", 0.0), "hip_region_loss_weight")
+        self.hip_tract_loss_weight = _loss_weight(get("hip_tract_loss_weight", 1.0), "hip_tract_loss_weight")
+        if self.hip_region_loss_weight > 0.0 and self.hip_train_regions is None:
+            raise ValueError("hip_region_loss_weight = %r needs a region map: set hip_train_regions"
+                             % self.hip_region_loss_weight)
         self.batch_size = get("batch_size", 64)
         self.device = get("device", torch.device("cpu"))
         config["num_nodes"] = self.num_nodes  # the reference writes this back (:233)
@@ -647,6 +691,9 @@ class MultiATGCN(AbstractTrafficStateModel):
         src = self._series_source(series, label_start, rel_steps, trusted=_checked)
         pred = self._run(src, int(src[1].shape[0]), series.device)
         ls = src[1]
+        if self.hip_region_loss_weight > 0.0:
+            return self._objective(pred, series, self._region_objective(), self.hip_train_loss_delta, ls,
+                                   self.hip_train_regions, self.hip_region_loss_weight, self.hip_tract_loss_weight)
         if self.hip_train_loss != "none":
             return self._objective(pred, series, self.hip_train_loss, self.hip_train_loss_delta, ls)
         affine = self._affine_scaler()
@@ -753,6 +800,9 @@ class MultiATGCN(AbstractTrafficStateModel):
             return self.calculate_loss_series(src[0], src[1], src[2], _checked=True)
         y_true = batch["y"]
         y_predicted = self.predict(batch)
+        if self.hip_region_loss_weight > 0.0:
+            return self._objective(y_predicted, y_true, self._region_objective(), self.hip_train_loss_delta, None,
+                                   self.hip_train_regions, self.hip_region_loss_weight, self.hip_tract_loss_weight)
         if self.hip_train_loss != "none":
             return self._objective(y_predicted, y_true, self.hip_train_loss, self.hip_train_loss_delta)
         affine = self._affine_scaler()
@@ -764,31 +814,47 @@ class MultiATGCN(AbstractTrafficStateModel):
         y_predicted = self._scaler.inverse_transform(y_predicted)
         return masked_mae(y_predicted, y_true, 0)
 
-    def _objective(self, pred, y, name, delta, label_start=None):
+    def _region_objective(self) -> str:
+        """the objective of both levels when a region term is configured: hip_train_loss, "none" = masked_mae"""
+        return "masked_mae" if self.hip_train_loss == "none" else self.hip_train_loss
+
+    def _objective(self, pred, y, name, delta, label_start=None, regions=None, region_weight=0.0, tract_weight=1.0):
         """the executor's objective ``name`` of a prediction on the device: ``y`` the label windows, or with label_start
-        the resident series; with autograd when the prediction carries a graph"""
+        the resident series; with autograd when the prediction carries a graph.  With ``regions``:
+        tract_weight * L(tracts) + region_weight * L(region totals) (ops.tract_region_loss)."""
         affine = self._affine_scaler()
         if affine is None:
             raise NotImplementedError("train_loss needs an affine scaler (StandardScaler / NoneScaler)")
+        if regions is not None:
+            return tract_region_loss(pred, y, regions, self.start_dim, affine[0], affine[1], name, delta, label_start,
+                                     tract_weight, region_weight)
         fn = train_loss_autograd if pred.requires_grad else train_loss_device
         out = fn(pred, y, self.start_dim, affine[0], affine[1], name, delta, label_start)
         return out if pred.requires_grad else out[0]
 
-    def train_loss(self, batch, name, delta=None):
+    def train_loss(self, batch, name, delta=None, regions=None, region_weight=1.0, tract_weight=1.0):
         """One of the executor's eleven differentiable training objectives (TrafficStateExecutor._build_train_loss,
         traffic_state_executor.py:200-250; ops.TRAIN_LOSSES) of a window batch (``X``, ``y``) or a resident-series batch
         (``series``, ``label_start``): predict, de-scale, mask and reduce in a fixed order on the device (matgcn_loss); with
         gradients enabled the result backpropagates through matgcn_loss_grad into the HIP backward.  ``delta``: huber's
         knee / quantile's level (None: 1.0 / 0.25, the reference's defaults).  The label channels start at ``start_dim``,
-        as in calculate_loss."""
+        as in calculate_loss.  ``regions`` (a regions.RegionMap, its state_dict() or one label per node; None: what
+        this method always did): tract_weight * L(tracts) + region_weight * L(region totals) with the same objective on
+        both levels (matgcn_region_loss / matgcn_region_loss_grad); a weight of 0 skips its half."""
         train_loss_desc(name, 0.0, 1.0, delta)      # refuse a bad name or delta before any kernel runs
+        if regions is not None:
+            regions = _train_regions(regions, self.num_nodes)
+            region_weight = _loss_weight(region_weight, "region_weight")
+            tract_weight = _loss_weight(tract_weight, "tract_weight")
+            if region_weight == 0.0 and tract_weight == 0.0:
+                raise ValueError("train_loss: tract_weight and region_weight are both 0")
         if self._affine_scaler() is None:
             raise NotImplementedError("train_loss needs an affine scaler (StandardScaler / NoneScaler)")
         if _is_series_batch(batch):
             src = self._batch_source(batch)
             pred = self._run(src, int(src[1].shape[0]), src[0].device)
-            return self._objective(pred, src[0], name, delta, src[1])
-        return self._objective(self.predict(batch), batch["y"], name, delta)
+            return self._objective(pred, src[0], name, delta, src[1], regions, region_weight, tract_weight)
+        return self._objective(self.predict(batch), batch["y"], name, delta, None, regions, region_weight, tract_weight)
 
     def horizon_mae(self, batch):
         """(out,) device tensor MAE@1..MAE@out in the evaluator's "single" mode on de-scaled values

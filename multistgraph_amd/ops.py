@@ -717,6 +717,127 @@ def group_label_sums(y: torch.Tensor, regions, out_steps: int, out_dim: int, y_s
     return out
 
 
+# ---- a training objective on region totals (matgcn_region_loss / matgcn_region_loss_grad) ---------------------------------
+def _region_loss_call(pred, y, regions, y_start, desc, label_start=None):
+    """the value call: (pred, y, scratch, result (1 + out,), label_start) - the scratch holds the totals for the gradient"""
+    lib = _lib.load()
+    pred = _check_tensor(pred, "pred")
+    if pred.dim() != 4:
+        raise _lib.MatgcnError("pred has shape %s, expected (B, out, N, od)" % (tuple(pred.shape),))
+    b, out, n, od = pred.shape
+    y, label_start, y_steps, y_feat = _label_geometry(pred, y, label_start)
+    groups = _region_groups(regions, n, pred.device)
+    need = C.c_size_t()
+    _lib.check(lib.matgcn_region_loss_bytes(b, out, regions.num_groups, od, C.byref(need)), "matgcn_region_loss_bytes")
+    scratch = torch.empty((need.value + 7) // 8, dtype=torch.float64, device=pred.device)
+    result = torch.empty(1 + out, dtype=torch.float32, device=pred.device)
+    stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
+    _lib.check(lib.matgcn_region_loss(C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(label_start)),
+                                      b, out, n, od, y_steps, y_feat, int(y_start), C.byref(desc), C.byref(groups),
+                                      C.c_void_p(scratch.data_ptr()), scratch.numel() * 8, C.c_void_p(result.data_ptr()),
+                                      stream), "matgcn_region_loss")
+    return pred, y, scratch, result, label_start
+
+
+def _region_loss_grad_call(pred, y, regions, y_start, desc, label_start, scratch, upstream, base, d_pred):
+    """the gradient call into ``d_pred``; ``base`` None, ``d_pred`` itself or another tensor of its shape"""
+    b, out, n, od = pred.shape
+    y_steps, y_feat = (int(y.shape[1]), int(y.shape[3])) if label_start is None else (int(y.shape[0]), int(y.shape[2]))
+    by_group, by_node = regions.groups_on(pred.device), regions.node_groups_on(pred.device)
+    stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
+    _lib.check(_lib.load().matgcn_region_loss_grad(
+        C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(label_start)), b, out, n, od, y_steps,
+        y_feat, int(y_start), C.byref(desc), C.byref(by_group), C.byref(by_node), C.c_void_p(scratch.data_ptr()),
+        scratch.numel() * 8, C.c_void_p(upstream.data_ptr()), C.c_void_p(_ptr(base)), C.c_void_p(d_pred.data_ptr()),
+        stream), "matgcn_region_loss_grad")
+    return d_pred
+
+
+def region_loss_device(pred: torch.Tensor, y: torch.Tensor, regions, y_start: int, mean: float, std: float, name: str,
+                       delta=None, label_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(1 + out,) tensor [the executor's objective ``name`` of the REGION TOTALS over all horizons, the same per horizon]
+    (matgcn_region_loss): totals of the de-scaled prediction and label per region of ``regions`` (a regions.RegionMap),
+    then the objective on them - masks act on totals.  Bit for bit train_loss_device(group_sums(pred), group_label_sums(y))
+    with an identity affine.  Geometry as train_loss_device."""
+    return _region_loss_call(pred, y, regions, y_start, train_loss_desc(name, mean, std, delta), label_start)[3]
+
+
+def _weight_arg(v, name):
+    v = float(v)
+    if not (math.isfinite(v) and v >= 0.0):
+        raise ValueError("%s = %r: expected a finite weight >= 0" % (name, v))
+    return v
+
+
+class _TractRegionLoss(torch.autograd.Function):
+    """tract_weight * L(tracts) + region_weight * L(region totals), one gradient tensor: matgcn_loss_grad writes the tract
+    half, matgcn_region_loss_grad adds the region half onto it (base = d_pred) - no add kernel, no temporary.  A weight of
+    0 skips its half."""
+
+    @staticmethod
+    def forward(ctx, pred, y, regions, y_start, desc, label_start, tract_weight, region_weight):
+        p = pred.detach()
+        value, t_scratch, r_scratch = None, None, None
+        if tract_weight > 0.0:
+            p, y_c, t_scratch, result, ls = _loss_call(p, y, y_start, desc, label_start)
+            value = result[0] * tract_weight if tract_weight != 1.0 else result[0].clone()
+        if region_weight > 0.0:
+            p, y_c, r_scratch, result, ls = _region_loss_call(p, y, regions, y_start, desc, label_start)
+            part = result[0] * region_weight if region_weight != 1.0 else result[0].clone()
+            value = part if value is None else value + part
+        if value is None:
+            raise ValueError("tract_region_loss: both weights are 0")
+        ctx.save_for_backward(p, y_c, *[s for s in (t_scratch, r_scratch) if s is not None])
+        ctx.has = (t_scratch is not None, r_scratch is not None)
+        ctx.label_start, ctx.y_start, ctx.desc, ctx.regions = ls, int(y_start), desc, regions
+        ctx.weights = (tract_weight, region_weight)
+        return value
+
+    @staticmethod
+    def backward(ctx, upstream):
+        pred, y, *scr = ctx.saved_tensors
+        t_scratch = scr.pop(0) if ctx.has[0] else None
+        r_scratch = scr.pop(0) if ctx.has[1] else None
+        b, out, n, od = pred.shape
+        ls = ctx.label_start
+        y_steps, y_feat = (int(y.shape[1]), int(y.shape[3])) if ls is None else (int(y.shape[0]), int(y.shape[2]))
+        d_pred = torch.empty_like(pred)
+        up = upstream.detach().to(torch.float32).reshape(1).contiguous()
+        tw, rw = ctx.weights
+        if t_scratch is not None:
+            up_t = up * tw if tw != 1.0 else up
+            stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
+            _lib.check(_lib.load().matgcn_loss_grad(
+                C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(ls)), b, out, n, od, y_steps,
+                y_feat, ctx.y_start, C.byref(ctx.desc), C.c_void_p(t_scratch.data_ptr()), t_scratch.numel() * 8,
+                C.c_void_p(up_t.data_ptr()), C.c_void_p(d_pred.data_ptr()), stream), "matgcn_loss_grad")
+        if r_scratch is not None:
+            up_r = up * rw if rw != 1.0 else up
+            _region_loss_grad_call(pred, y, ctx.regions, ctx.y_start, ctx.desc, ls, r_scratch, up_r,
+                                   d_pred if t_scratch is not None else None, d_pred)
+        return d_pred, None, None, None, None, None, None, None
+
+
+def tract_region_loss(pred: torch.Tensor, y: torch.Tensor, regions, y_start: int, mean: float, std: float, name: str,
+                      delta=None, label_start: Optional[torch.Tensor] = None, tract_weight: float = 1.0,
+                      region_weight: float = 1.0) -> torch.Tensor:
+    """The autograd scalar  tract_weight * L(tracts) + region_weight * L(region totals)  of the executor's objective
+    ``name`` (float32 device arithmetic): matgcn_loss and matgcn_region_loss forward; backward matgcn_loss_grad with
+    upstream * tract_weight into the gradient, then matgcn_region_loss_grad with upstream * region_weight and that gradient
+    as its base.  Fixed summation orders throughout: the same bits every run.  A weight of 0 skips its half."""
+    tw, rw = _weight_arg(tract_weight, "tract_weight"), _weight_arg(region_weight, "region_weight")
+    if tw == 0.0 and rw == 0.0:
+        raise ValueError("tract_region_loss: both weights are 0")
+    return _TractRegionLoss.apply(pred, y, regions, y_start, train_loss_desc(name, mean, std, delta), label_start, tw, rw)
+
+
+def region_train_loss(pred: torch.Tensor, y: torch.Tensor, regions, y_start: int, mean: float, std: float, name: str,
+                      delta=None, label_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The scalar of the objective ``name`` on the region totals with autograd support: matgcn_region_loss forward,
+    matgcn_region_loss_grad backward (the region half of tract_region_loss alone)."""
+    return tract_region_loss(pred, y, regions, y_start, mean, std, name, delta, label_start, 0.0, 1.0)
+
+
 def _opt_tensor(t, name: str) -> torch.Tensor:
     """an optimizer tensor as the C ABI wants it - the caller's own memory, so nothing is copied or converted here"""
     if not isinstance(t, torch.Tensor):

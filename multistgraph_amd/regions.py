@@ -85,6 +85,8 @@ class RegionMap:
         self.names: Optional[List[str]] = names
         self._ptr_host = (C.c_int32 * len(self.ptr))(*self.ptr)
         self._device: Dict[torch.device, tuple] = {}
+        self._by_node = None                      # the transposed map, derived on first use
+        self._node_device: Dict[torch.device, tuple] = {}
 
     # ---- construction helpers -------------------------------------------------------------------------------------------
     @classmethod
@@ -175,4 +177,46 @@ class RegionMap:
         g.node = node.data_ptr() if self.num_members else None
         g.weight = None if weight is None or not self.num_members else weight.data_ptr()
         g.n_groups, g.n_members = self.num_groups, self.num_members
+        return g
+
+    def by_node(self):
+        """(ptr, group, weight): the transposed map as plain lists - a CSR list over nodes whose entries are the groups a
+        node belongs to, in ascending member position of the by-group map (a stable sort by node), with the weights
+        permuted alongside.  Derived, built once; state_dict() does not carry it."""
+        held = self._by_node
+        if held is None:
+            group_of = [g for g in range(self.num_groups) for _ in range(self.ptr[g + 1] - self.ptr[g])]
+            order = sorted(range(self.num_members), key=self.node.__getitem__)      # sorted() is stable
+            ptr = [0] * (self.num_nodes + 1)
+            for n in self.node:
+                ptr[n + 1] += 1
+            for n in range(self.num_nodes):
+                ptr[n + 1] += ptr[n]
+            group = [group_of[k] for k in order]
+            weight = None if self.weight is None else [self.weight[k] for k in order]
+            held = self._by_node = (ptr, group, weight, (C.c_int32 * len(ptr))(*ptr))
+        return held[0], held[1], held[2]
+
+    def node_groups_on(self, device) -> "_lib.Groups":
+        """the transposed map as a matgcn_groups descriptor for ``device`` (the by_node argument of
+        matgcn_region_loss_grad): n_groups = num_nodes, ``node`` holds group indices; uploaded on first use and kept"""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.MatgcnError("a region map is used on the GPU: the hot path is HIP-only (no CPU fallback)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        ptr_l, group_l, weight_l = self.by_node()
+        held = self._node_device.get(device)
+        if held is None:
+            ptr = torch.tensor(ptr_l, dtype=torch.int32).to(device)
+            group = torch.tensor(group_l, dtype=torch.int32).to(device)
+            weight = None if weight_l is None else torch.tensor(weight_l, dtype=torch.float32).to(device)
+            held = self._node_device[device] = (ptr, group, weight)
+        ptr, group, weight = held
+        g = _lib.Groups()
+        g.ptr = C.cast(self._by_node[3], C.POINTER(C.c_int32))
+        g.ptr_dev = ptr.data_ptr()
+        g.node = group.data_ptr() if self.num_members else None
+        g.weight = None if weight is None or not self.num_members else weight.data_ptr()
+        g.n_groups, g.n_members = self.num_nodes, self.num_members
         return g

@@ -1,8 +1,10 @@
 """Training steps of the bench workload (default Baltimore 403, B=64): forward_train + backward through the plugin
 surface (calculate_loss().backward()), timed with HIP events.
-usage: train_step.py [--deterministic] [--bf16x3] [--device-dropout] [--clip] [--fused-optimizer] [--loss NAME] [workload] [steps] [serial|wave] [batch] [fp32|bf16_mix|bf16]
+usage: train_step.py [--deterministic] [--bf16x3] [--device-dropout] [--clip] [--fused-optimizer] [--loss NAME] [--region-weight W] [workload] [steps] [serial|wave] [batch] [fp32|bf16_mix|bf16]
 (--loss NAME: the model's hip_train_loss - calculate_loss returns that objective of the executor instead of masked MAE,
 value and gradient from matgcn_loss / matgcn_loss_grad)
+(--region-weight W: the model's hip_region_loss_weight = W over ten random regions plus one whole-city group - calculate_loss
+returns L(tracts) + W * L(region totals), ops.tract_region_loss)
 (--deterministic: the model's hip_deterministic = True - the backward's sums in a fixed order, see matgcn_set_deterministic;
 the summary line then also gives the bytes the train buffer grew by)
 (--bf16x3: the model's hip_precision = "bf16x3_train" - the step's graph mixes, both directions, from three bf16 pieces,
@@ -40,6 +42,11 @@ if "--loss" in sys.argv:
     i = sys.argv.index("--loss")
     train_loss = sys.argv[i + 1]
     del sys.argv[i:i + 2]
+region_weight = 0.0
+if "--region-weight" in sys.argv:
+    i = sys.argv.index("--region-weight")
+    region_weight = float(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 name = sys.argv[1] if len(sys.argv) > 1 else "bm403"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 w = dict(bench.WORKLOADS[name])
@@ -57,6 +64,12 @@ if train_loss != "none":
     from multistgraph_amd.ops import train_loss_desc
     train_loss_desc(train_loss, 0.0, 1.0)      # a bad name stops here
     model.hip_train_loss = train_loss.lower()
+if region_weight > 0.0:
+    import numpy as np
+    from multistgraph_amd.regions import RegionMap
+    labels = np.random.default_rng(w["nodes"]).integers(0, 10, w["nodes"])
+    groups = [np.flatnonzero(labels == g).tolist() for g in range(10)] + [list(range(w["nodes"]))]
+    model.hip_train_regions, model.hip_region_loss_weight = RegionMap(w["nodes"], groups=groups), region_weight
 if len(sys.argv) > 5:
     model.hip_precision = sys.argv[5]
 if len(sys.argv) > 3 and sys.argv[3] == "serial":
@@ -96,11 +109,12 @@ print("train buffer %.2f GB  workspace %.2f GB  peak torch memory %.2f GB" % (
 if len(times) > 3:
     import statistics
     med = [statistics.median(t[k] for t in times[3:]) for k in range(5)]
-    print("median of %d steps (%s, B = %d, %s%s%s%s%s%s): step %.3f ms  forward %.3f ms  backward %.3f ms  optimizer %.3f ms  "
+    print("median of %d steps (%s, B = %d, %s%s%s%s%s%s%s): step %.3f ms  forward %.3f ms  backward %.3f ms  optimizer %.3f ms  "
           "host enqueue %.3f ms" % (
               len(times) - 3, name, w["batch"], model.hip_precision, ", deterministic" if deterministic else "",
               ", device dropout" if device_dropout else "", ", clip 5" if clip else "",
               ", ClipAdam" if fused_optimizer else "", ", loss %s" % model.hip_train_loss if train_loss != "none" else "",
+              ", region weight %g" % region_weight if region_weight > 0.0 else "",
               med[0], med[1], med[2], med[3], med[4]))
 if deterministic:
     import ctypes
