@@ -853,8 +853,11 @@ int matgcn_set_stream_pool(int own);
  * behind them itself - the wavefront forward per layer: each chain waits for exactly the weights it reads, so the weight
  * preparation runs beside head fusion, the layer-0 fold and the first graph mix of matgcn_forward{,_series}.  A caller
  * that enables it promises (a) to keep `prepared` and the parameter tensors alive and unmodified until a later call of
- * this library on the same stream has been enqueued, and (b) to call matgcn_prepare_join(stream) before it reads or
- * frees `prepared` itself.  Meant for hosts that own `prepared` for the lifetime of the model (the plugin class does).
+ * this library THAT TAKES `prepared` (or matgcn_prepare_join) has been enqueued on the same stream - only those order
+ * the stream behind the weight streams; the loss, metric, score, region and optimizer entry points do not -, and (b)
+ * to call matgcn_prepare_join(stream) before it reads or frees `prepared` itself.  Meant for hosts that own `prepared`
+ * for the lifetime of the model (the plugin class does).  (tests/test_stream_order.py holds both promises: the
+ * parameters are overwritten right behind a forward that follows a lazy prepare, `prepared` behind the join.)
  * Both return MATGCN_OK / the previous setting. */
 int matgcn_set_lazy_prepare(int enabled);
 int matgcn_prepare_join(void* stream);

@@ -325,9 +325,28 @@ def train_loss(pred: torch.Tensor, y: torch.Tensor, y_start: int, mean: float, s
     return _TrainLoss.apply(pred, y, y_start, train_loss_desc(name, mean, std, delta), label_start)
 
 
+_affine_uploads: Dict[tuple, torch.Tensor] = {}    # (device, the float32 bytes of a host-side affine) -> its device copy
+
+
 def _affine_arg(v, n, device, name):
-    """scalar or length-N vector -> (float32 device tensor, per_node flag)"""
-    t = torch.as_tensor(v, dtype=torch.float32).reshape(-1).to(device)
+    """scalar or length-N vector -> (float32 device tensor, per_node flag).  A device tensor is used where it lies.  Host
+    values (the scaler's numbers, a per-node numpy vector) are uploaded once per content and kept: a copy from pageable
+    host memory makes the host wait until the CALLER'S STREAM has drained, so an upload per batch would put a device
+    wait into every metric, score and region call of an evaluation pass (tests/test_stream_order.py).  The kept tensors
+    are never written."""
+    if isinstance(v, torch.Tensor) and v.is_cuda:
+        t = v.detach().to(dtype=torch.float32).reshape(-1).to(device)
+    else:
+        host = torch.as_tensor(v, dtype=torch.float32).detach().reshape(-1).contiguous()
+        device = torch.device(device)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        key = (device, host.numpy().tobytes())
+        t = _affine_uploads.get(key)
+        if t is None:
+            if len(_affine_uploads) >= 64:
+                _affine_uploads.clear()
+            t = _affine_uploads[key] = host.to(device)
     if t.numel() not in (1, n):
         raise _lib.MatgcnError("%s has %d entries, expected 1 or %d (one per node)" % (name, t.numel(), n))
     return t.contiguous(), int(t.numel() == n and n > 1)
