@@ -263,6 +263,13 @@ int matgcn_output_head(const matgcn_dims* dims, const matgcn_params* params, con
  * label_start != NULL (device, B int32): `y` is the raw series (y_steps, N, y_feat) instead and the label rows of
  * sample b are y[label_start[b] + o], o < out - the targets MTHDataset._generate_input_data materialises
  * (mth_dataset.py:110-160) are gathered here, on the device.
+ * The label contract - of every entry point that takes (y, label_start, batch, out_steps, nodes, out_dim, y_steps, y_feat,
+ * y_start): the four counts >= 1, 0 <= y_start and y_start + out_dim <= y_feat, and one of two rules for y_steps -
+ *   strict rule  y_steps >= out_steps, windows or series: matgcn_masked_mae{,_grad}, matgcn_loss{,_grad},
+ *                matgcn_metric_sums{,_nodes}, matgcn_region_loss{,_grad};
+ *   series rule  y_steps >= 1 and y_feat >= 1, and y_steps >= out_steps for windows only: matgcn_mc_scores{,_nodes},
+ *                matgcn_mc_conformity, matgcn_group_label_sums
+ * - else MATGCN_ERR_BAD_ARG, before any launch.
  * partials: caller-owned device scratch of 2*B*out + 1 floats (the last one keeps sum(mask) for the gradient);
  * result: device, 1+out floats.  Two launches, fixed summation order (no atomics): results are run-to-run identical. */
 int matgcn_masked_mae(const float* pred, const float* y, const int32_t* label_start, int batch, int out_steps, int nodes,
@@ -680,7 +687,7 @@ int matgcn_conformal_coverage(const float* scores, int64_t rows, int out_steps, 
  * in up to 64 KB; a row of more than 16 383 floats is walked in global memory instead, same chain) and keeps a map of up
  * to 16 KB beside it.
  *
- * matgcn_group_label_sums reads labels with the geometry of matgcn_masked_mae: label_start null = window labels
+ * matgcn_group_label_sums reads labels under the label contract of matgcn_masked_mae: label_start null = window labels
  * (batch, y_steps, nodes, y_feat), channels y_start .. y_start + out_dim - 1 of steps 0 .. out_steps-1; otherwise `y` is
  * the raw series (y_steps, nodes, y_feat) and label_start (batch) its first label rows, clamped and counted through
  * matgcn_series_violations.

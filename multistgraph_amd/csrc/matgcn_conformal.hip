@@ -40,14 +40,16 @@ __device__ __forceinline__ int conf_rank(int n, double coverage) {
   return k < 1.0 ? 1 : (int)k;
 }
 
+// k_mc_conformity keeps the argument order it had before LabelView (samples, labels, tile, geometry): with the view
+// embedded it measured slower than that by more than the run-to-run gap at S = 32
 struct McConformityArgs {
   const float* samples;   // (S, B, out, N, od)
-  const float* y;         // as McScoreArgs
+  const float* y;         // the fields of LabelView
   const int* labelStart;
   int S, P, logTE;
   int outSteps, N, od, ySteps, yFeat, yStart, tilesPerRow;
   long long E;
-  McScale sc;
+  NodeScale sc;
   float truthMin, minS, nullVal;
   float* scores;          // (B, out, N, od)
 };
@@ -66,9 +68,9 @@ __global__ __launch_bounds__(256) void k_mc_conformity(McConformityArgs a, McLev
   const int r = r0 + e, n = r / a.od, c = r - n * a.od;   // a node of the row where e < nValid
   mc_sort_tile_scaled(mcTile, a.samples, a.S, a.P, logTE, (size_t)a.E, e0, nValid, n, a.sc);
   if (tid >= TE || e >= nValid) return;                   // slot 0 holds every element of the tile
-  // label, filter and mask: the statements of k_mc_scores_nodes
-  const size_t yrow = a.labelStart ? series_row((long)a.labelStart[b] + o, a.ySteps) : (size_t)b * a.ySteps + o;
-  float l = mc_descale_node(a.sc, n, a.y[(yrow * a.N + n) * a.yFeat + a.yStart + c]);
+  // label, filter and mask: the statements of mc_node_label
+  const LabelView v = {a.y, a.labelStart, a.outSteps, a.N, a.od, a.ySteps, a.yFeat, a.yStart};
+  float l = descale_node(a.sc, n, label_at(v, label_row(v, b, o), n, c));
   bool keep = !(a.truthMin == a.truthMin) || l > a.truthMin;
   if (fabsf(l) < a.minS) l = 0.f;
   keep = keep && (a.nullVal != a.nullVal ? l == l : l != a.nullVal);

@@ -70,6 +70,24 @@ struct FuseArgs {
   int extSrc[16];
 };
 
+// The labels of a call that compares a (B, outSteps, N, od) tensor with them: element (b, o, n, c) is channel yStart + c of
+// node n in label row (b, o) (label_row, matgcn_kernels.hip).  Filled by label_view (matgcn_eval.hip), the one place that
+// checks this geometry.
+struct LabelView {
+  const float* y;          // windows (B, ySteps, N, yFeat), or the raw series (ySteps, N, yFeat) when labelStart != null
+  const int* labelStart;   // device (B) label starts, or null
+  int outSteps, N, od, ySteps, yFeat, yStart;
+};
+
+// The device-side form of matgcn_metric_scale without its label-only fields: first affine (scalar or one pair per node;
+// null = identity), second affine per node, clamp from below (NaN: off).  Filled by node_scale (matgcn_eval.hip).
+struct NodeScale {
+  const float* mean; const float* std;
+  const float* mean2; const float* std2;
+  int perNode;
+  float clampMin;
+};
+
 struct MixArgs {
   const float* St = nullptr;
   int ldS = 0;

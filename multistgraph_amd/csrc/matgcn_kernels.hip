@@ -662,6 +662,32 @@ __device__ __forceinline__ size_t series_row(long row, long steps) {
   }
   return (size_t)row;
 }
+// the label row of (b, o); in it the od label channels of node n, and channel c of them
+// (label_ptr and label_at each spell the offset: written through the other, instructions move in k_loss_grad or k_group_walk)
+__device__ __forceinline__ size_t label_row(const LabelView& v, size_t b, int o) {
+  return v.labelStart ? series_row((long)v.labelStart[b] + o, v.ySteps) : b * v.ySteps + o;
+}
+__device__ __forceinline__ const float* label_ptr(const LabelView& v, size_t row, int n) {
+  return v.y + (row * v.N + n) * v.yFeat + v.yStart;
+}
+__device__ __forceinline__ float label_at(const LabelView& v, size_t row, int n, int c) {
+  return v.y[(row * v.N + n) * v.yFeat + v.yStart + c];
+}
+
+// x * sd + mu as two fp32 roundings, the way the reference's tensors de-scale.  hipcc would fuse the pair into one fma
+// (the __fmul_rn / __fadd_rn of the HIP headers are plain operators and fuse as well): half an ulp of the product is a
+// visible share of a label that de-scales to nearly 0, and of its |d / l| (MAPE).
+__device__ __forceinline__ float scale_affine(float x, float sd, float mu) {
+#pragma clang fp contract(off)
+  const float t = x * sd;
+  return t + mu;
+}
+// the affines of node n, each two fp32 roundings
+__device__ __forceinline__ float descale_node(const NodeScale& sc, int n, float v) {
+  if (sc.std) v = scale_affine(v, sc.std[sc.perNode ? n : 0], sc.mean[sc.perNode ? n : 0]);
+  if (sc.std2) v = scale_affine(v, sc.std2[n], sc.mean2[n]);
+  return v;
+}
 
 __global__ __launch_bounds__(256) void k_fuse_heads(FuseArgs a) {
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -1901,6 +1927,8 @@ __global__ __launch_bounds__(64) void k_mae_final(const float* __restrict__ part
 // the reference's tensors.  stage 1: one workgroup per (b, horizon) -> partials[b][o][.]; stage 2 adds the batch up
 // in a fixed order (run-to-run identical) and, on request, onto the running sums of earlier batches.
 struct MetricArgs {
+  // the argument order from before LabelView and NodeScale, whose fields these are (both metric kernels measured slower
+  // with the two blocks embedded: DESIGN.md 5f)
   const float* pred;     // (B, out, N, od)
   const float* y;        // (B, ySteps, N, yFeat) windows, or the raw series (ySteps, N, yFeat) when labelStart != null
   const int* labelStart;
@@ -1913,25 +1941,22 @@ struct MetricArgs {
   int outSteps, N, od, ySteps, yFeat, yStart;
   double* partials;      // [B*out][MATGCN_METRIC_SUMS]
 };
-constexpr int METRIC_SUMS = 14;
-// x * sd + mu as two fp32 roundings, the way the reference's tensors de-scale.  hipcc would fuse the pair into one fma:
-// half an ulp of the product is a visible share of a label that de-scales to nearly 0, and of its |d / l| (MAPE).
-__device__ __forceinline__ float metric_affine(float x, float sd, float mu) {
-#pragma clang fp contract(off)
-  const float t = x * sd;
-  return t + mu;
+__device__ __forceinline__ LabelView metric_labels(const MetricArgs& a) {
+  return {a.y, a.labelStart, a.outSteps, a.N, a.od, a.ySteps, a.yFeat, a.yStart};
 }
+constexpr int METRIC_SUMS = 14;
 // sums: 0 elements, 1 non-NaN labels, 2 |d|, 3 d^2, 4 |d/l| (over 1), 5 labels != 0, 6-8 the same three over 5,
 //       9 l, 10 l^2, 11 p, 12 p^2, 13 l-p
 // The terms of one element - raw label l and prediction p of node n - added onto s[], one add per sum: both groupings
 // of the sums (per horizon, per horizon and node) are this function, so their per-element terms cannot differ.
 __device__ __forceinline__ void metric_add_element(const MetricArgs& a, bool clamp, bool pick, int n, float l, float p,
                                                    double* s) {
+  // descale_node's statements, kept here for the pair: two calls of it cost k_metric_partial four VGPRs (44 -> 48)
   if (a.std) {
     const float sd = a.std[a.perNode ? n : 0], mu = a.mean[a.perNode ? n : 0];
-    l = metric_affine(l, sd, mu); p = metric_affine(p, sd, mu);
+    l = scale_affine(l, sd, mu); p = scale_affine(p, sd, mu);
   }
-  if (a.std2) { l = metric_affine(l, a.std2[n], a.mean2[n]); p = metric_affine(p, a.std2[n], a.mean2[n]); }
+  if (a.std2) { l = scale_affine(l, a.std2[n], a.mean2[n]); p = scale_affine(p, a.std2[n], a.mean2[n]); }
   if (clamp && p < a.clampMin) p = a.clampMin;
   if (pick && !(l > a.truthMin)) return;
   if (a.minS >= 0.f && fabsf(l) < a.minS) l = 0.f;
@@ -1946,17 +1971,17 @@ __device__ __forceinline__ void metric_add_element(const MetricArgs& a, bool cla
 
 __global__ __launch_bounds__(256) void k_metric_partial(MetricArgs a) {
   __shared__ double red[4][METRIC_SUMS];
-  const int b = blockIdx.x / a.outSteps, o = blockIdx.x - b * a.outSteps;
-  const float* pp = a.pred + ((size_t)b * a.outSteps + o) * a.N * a.od;
-  const size_t yrow = a.labelStart ? series_row((long)a.labelStart[b] + o, a.ySteps) : (size_t)b * a.ySteps + o;
-  const float* yp = a.y + yrow * a.N * a.yFeat + a.yStart;
+  const LabelView v = metric_labels(a);
+  const int b = blockIdx.x / v.outSteps, o = blockIdx.x - b * v.outSteps;
+  const float* pp = a.pred + ((size_t)b * v.outSteps + o) * v.N * v.od;
+  const float* yp = label_ptr(v, label_row(v, b, o), 0);
   double s[METRIC_SUMS];
 #pragma unroll
   for (int k = 0; k < METRIC_SUMS; ++k) s[k] = 0.0;
   const bool clamp = a.clampMin == a.clampMin, pick = a.truthMin == a.truthMin;
-  for (int idx = threadIdx.x; idx < a.N * a.od; idx += 256) {
-    const int n = idx / a.od, c = idx - n * a.od;
-    metric_add_element(a, clamp, pick, n, yp[(size_t)n * a.yFeat + c], pp[idx], s);
+  for (int idx = threadIdx.x; idx < v.N * v.od; idx += 256) {
+    const int n = idx / v.od, c = idx - n * v.od;
+    metric_add_element(a, clamp, pick, n, yp[(size_t)n * v.yFeat + c], pp[idx], s);
   }
 #pragma unroll
   for (int k = 0; k < METRIC_SUMS; ++k) {
@@ -1985,18 +2010,18 @@ __global__ __launch_bounds__(64) void k_metric_accumulate(const double* __restri
 // the data alone fixes, so one call over B rows and accumulating calls over the same rows in pieces give the same bits.
 // No scratch, no second stage; lanes of a wave hold consecutive nodes of one horizon (coalesced for od = 1).
 __global__ __launch_bounds__(64) void k_metric_nodes(MetricArgs a, int B, int accumulate, double* __restrict__ sums) {
+  const LabelView v = metric_labels(a);
   const int idx = blockIdx.x * 64 + threadIdx.x;
-  if (idx >= a.outSteps * a.N) return;
-  const int o = idx / a.N, n = idx - o * a.N;
+  if (idx >= v.outSteps * v.N) return;
+  const int o = idx / v.N, n = idx - o * v.N;
   double s[METRIC_SUMS];
 #pragma unroll
   for (int k = 0; k < METRIC_SUMS; ++k) s[k] = accumulate ? sums[(size_t)idx * METRIC_SUMS + k] : 0.0;
   const bool clamp = a.clampMin == a.clampMin, pick = a.truthMin == a.truthMin;
   for (int b = 0; b < B; ++b) {
-    const size_t yrow = a.labelStart ? series_row((long)a.labelStart[b] + o, a.ySteps) : (size_t)b * a.ySteps + o;
-    const float* yp = a.y + (yrow * a.N + n) * a.yFeat + a.yStart;
-    const float* pp = a.pred + (((size_t)b * a.outSteps + o) * a.N + n) * a.od;
-    for (int c = 0; c < a.od; ++c) metric_add_element(a, clamp, pick, n, yp[c], pp[c], s);
+    const float* yp = label_ptr(v, label_row(v, b, o), n);
+    const float* pp = a.pred + (((size_t)b * v.outSteps + o) * v.N + n) * v.od;
+    for (int c = 0; c < v.od; ++c) metric_add_element(a, clamp, pick, n, yp[c], pp[c], s);
   }
 #pragma unroll
   for (int k = 0; k < METRIC_SUMS; ++k) sums[(size_t)idx * METRIC_SUMS + k] = s[k];

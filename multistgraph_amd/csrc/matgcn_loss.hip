@@ -6,7 +6,7 @@
 // Geometry is that of section 9 of matgcn_kernels.hip (k_mae_partial): pred (B, out, N, od); y (B, ySteps, N, yFeat) channels
 // yStart .., or with labelStart the raw series (ySteps, N, yFeat) gathered through series_row (clamped and counted).
 //
-// Arithmetic.  l = y*std + mean and p = pred*std + mean are two fp32 roundings each (metric_affine), and d = p - l one more:
+// Arithmetic.  l = y*std + mean and p = pred*std + mean are two fp32 roundings each (scale_affine), and d = p - l one more:
 // the values the reference's float32 tensors hold.  From there on everything is fp64 - the term of an element, the sums, the
 // quotient, the square root - and a result is rounded to float32 ONCE.  The partials of stage 1 are doubles.
 //   MASKED (MAE, MSE, RMSE, MAPE):  l := 0 where |l| < minS first; m = (l != nullVal) [nullVal NaN: !isnan(l)];
@@ -59,17 +59,15 @@ __device__ __forceinline__ double loss_slope(float pf, float lf, float df, doubl
 
 struct LossArgs {
   const float* pred;
-  const float* y;
-  const int* labelStart;
-  int outSteps, N, od, ySteps, yFeat, yStart;
+  LabelView lab;
   float mean, std, nullVal, minS, delta;
 };
 
 // p, l, d of one element and whether the mask keeps it
 template <int MASKED>
 __device__ __forceinline__ bool loss_element(const LossArgs& a, float yv, float pv, float& p, float& l, float& d) {
-  l = metric_affine(yv, a.std, a.mean);
-  p = metric_affine(pv, a.std, a.mean);
+  l = scale_affine(yv, a.std, a.mean);
+  p = scale_affine(pv, a.std, a.mean);
   bool keep = true;
   if (MASKED) {
     if (fabsf(l) < a.minS) l = 0.f;                       // loss.py:18/55/73/88 (in place in the reference)
@@ -83,17 +81,17 @@ __device__ __forceinline__ bool loss_element(const LossArgs& a, float yv, float 
 template <int KIND, int MASKED>
 __global__ __launch_bounds__(LOSS_THREADS) void k_loss_partial(LossArgs a, double* __restrict__ scratch) {
   __shared__ double red[LOSS_THREADS / 64][2];
-  const int b = blockIdx.x / a.outSteps, o = blockIdx.x - b * a.outSteps;
-  const int len = a.N * a.od;
-  const float* pp = a.pred + ((size_t)b * a.outSteps + o) * len;
-  const size_t yrow = a.labelStart ? series_row((long)a.labelStart[b] + o, a.ySteps) : (size_t)b * a.ySteps + o;
-  const float* yp = a.y + yrow * a.N * a.yFeat + a.yStart;
+  const LabelView& v = a.lab;
+  const int b = blockIdx.x / v.outSteps, o = blockIdx.x - b * v.outSteps;
+  const int len = v.N * v.od;
+  const float* pp = a.pred + ((size_t)b * v.outSteps + o) * len;
+  const float* yp = label_ptr(v, label_row(v, b, o), 0);
   const double delta = (double)a.delta;
   double st = 0.0, sc = 0.0;
   for (int idx = threadIdx.x; idx < len; idx += LOSS_THREADS) {
-    const int n = idx / a.od, c = idx - n * a.od;
+    const int n = idx / v.od, c = idx - n * v.od;
     float p, l, d;
-    const bool keep = loss_element<MASKED>(a, yp[(size_t)n * a.yFeat + c], pp[idx], p, l, d);
+    const bool keep = loss_element<MASKED>(a, yp[(size_t)n * v.yFeat + c], pp[idx], p, l, d);
     const double t = loss_term<KIND>(p, l, d, delta);
     if (MASKED) {
       if (keep) { sc += 1.0; st += (t == t) ? t : 0.0; }
@@ -146,13 +144,13 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss_grad(LossArgs a, const do
                                                             float* __restrict__ dpred) {
   const size_t idx = (size_t)blockIdx.x * LOSS_THREADS + threadIdx.x;
   if (idx >= total) return;
-  const int c = idx % a.od;
-  const int n = (idx / a.od) % a.N;
-  const int o = (idx / ((size_t)a.od * a.N)) % a.outSteps;
-  const size_t b = idx / ((size_t)a.od * a.N * a.outSteps);
-  const size_t yrow = a.labelStart ? series_row((long)a.labelStart[b] + o, a.ySteps) : b * a.ySteps + o;
+  const LabelView& v = a.lab;
+  const int c = idx % v.od;
+  const int n = (idx / v.od) % v.N;
+  const int o = (idx / ((size_t)v.od * v.N)) % v.outSteps;
+  const size_t b = idx / ((size_t)v.od * v.N * v.outSteps);
   float p, l, d;
-  const bool keep = loss_element<MASKED>(a, a.y[(yrow * a.N + n) * a.yFeat + a.yStart + c], a.pred[idx], p, l, d);
+  const bool keep = loss_element<MASKED>(a, label_at(v, label_row(v, b, o), n, c), a.pred[idx], p, l, d);
   const double delta = (double)a.delta;
   const double cnt = MASKED ? kept[0] : (double)total;
   double g = 0.0;

@@ -22,9 +22,9 @@
 // the order the workgroups run in: the scores are one partial per workgroup in caller-owned scratch and a second kernel
 // that adds them in ascending index (k_mc_accumulate, as k_metric_accumulate).
 //
-// Arithmetic whose bits the header promises is written through the helpers below with contraction switched off: hipcc
-// fuses a * b + c by default (the __fmul_rn / __fadd_rn of the HIP headers are plain operators and fuse as well), which
-// would make the bits depend on the compiler.
+// Arithmetic whose bits the header promises is written through scale_affine (matgcn_kernels.hip) and the helpers below,
+// with contraction switched off: hipcc fuses a * b + c by default (the __fmul_rn / __fadd_rn of the HIP headers are plain
+// operators and fuse as well), which would make the bits depend on the compiler.
 
 constexpr int MC_MAX_PROBS = 8;
 constexpr int MC_SCORE_SUMS = 5;                         // count, CRPS, covered, width, Winkler (+ one pinball sum per level)
@@ -32,12 +32,6 @@ constexpr int MC_MAX_SUMS = MC_SCORE_SUMS + MC_MAX_PROBS;
 constexpr int MC_TILE_FLOATS = 16384;
 constexpr int MC_REDUCE_BYTES = 256 * 2 * (int)sizeof(double);   // k_mc_scores: two fp64 partial sums per thread
 
-// x * sd + mu as two roundings (fp32)
-__device__ __forceinline__ float mc_affine(float x, float sd, float mu) {
-#pragma clang fp contract(off)
-  const float t = x * sd;
-  return t + mu;
-}
 // lo + g * (hi - lo) as three roundings (fp32): numpy's "linear" rule in float32 arithmetic
 __device__ __forceinline__ float mc_lerp(float lo, float hi, float g) {
 #pragma clang fp contract(off)
@@ -99,32 +93,18 @@ __device__ __forceinline__ void mc_sort_tile(float* __restrict__ x, const float*
     const int s = idx >> logTE, e = idx & (TE - 1);
     float v = __builtin_inff();
     if (e >= nValid) v = 0.f;
-    else if (s < S) v = mc_affine(samples[(size_t)s * E + e0 + e], std, mean);
+    else if (s < S) v = scale_affine(samples[(size_t)s * E + e0 + e], std, mean);
     x[(mc_row(s) << logTE) + e] = v;
   }
   mc_sort_network(x, P, logTE);
 }
 
-// The descriptor of the node-grouped entry points (matgcn_metric_scale without the label-only fields): first affine
-// (scalar or one pair per node; null = identity), second affine per node, clamp from below (NaN: off).
-struct McScale {
-  const float* mean; const float* std;
-  const float* mean2; const float* std2;
-  int perNode;
-  float clampMin;
-};
-// the affines of node n, each two fp32 roundings
-__device__ __forceinline__ float mc_descale_node(const McScale& sc, int n, float v) {
-  if (sc.std) v = mc_affine(v, sc.std[sc.perNode ? n : 0], sc.mean[sc.perNode ? n : 0]);
-  if (sc.std2) v = mc_affine(v, sc.std2[n], sc.mean2[n]);
-  return v;
-}
-
-// mc_sort_tile with the descriptor in place of the two scalars.  256 is a multiple of TE, so a thread loads one column
-// e = tid & (TE - 1) only: `node` is that column's node (read where e < nValid only) and its affines are fetched once.
+// mc_sort_tile with the descriptor of the node-grouped entry points (NodeScale) in place of the two scalars.  256 is a
+// multiple of TE, so a thread loads one column e = tid & (TE - 1) only: `node` is that column's node (read where
+// e < nValid only) and its affines are fetched once.
 __device__ __forceinline__ void mc_sort_tile_scaled(float* __restrict__ x, const float* __restrict__ samples, int S, int P,
                                                     int logTE, size_t E, size_t e0, int nValid, int node,
-                                                    const McScale& sc) {
+                                                    const NodeScale& sc) {
   const int TE = 1 << logTE, tid = threadIdx.x, e = tid & (TE - 1);
   const bool live = e < nValid, clamp = sc.clampMin == sc.clampMin;
   float sd = 1.f, mu = 0.f, sd2 = 1.f, mu2 = 0.f;
@@ -135,8 +115,8 @@ __device__ __forceinline__ void mc_sort_tile_scaled(float* __restrict__ x, const
     if (!live) v = 0.f;
     else if (s < S) {
       v = samples[(size_t)s * E + e0 + e];
-      if (sc.std) v = mc_affine(v, sd, mu);
-      if (sc.std2) v = mc_affine(v, sd2, mu2);
+      if (sc.std) v = scale_affine(v, sd, mu);
+      if (sc.std2) v = scale_affine(v, sd2, mu2);
       if (clamp && v < sc.clampMin) v = sc.clampMin;
     }
     x[(mc_row(s) << logTE) + e] = v;
@@ -166,7 +146,7 @@ __global__ __launch_bounds__(256) void k_mc_quantiles(const float* __restrict__ 
 
 // k_mc_quantiles with the descriptor: element g of the (.., N, od) tensor belongs to node (g / od) % N
 __global__ __launch_bounds__(256) void k_mc_quantiles_scaled(const float* __restrict__ samples, McLevels lv, int S, int P,
-                                                             int logTE, long long E, int rowLen, int od, McScale sc,
+                                                             int logTE, long long E, int rowLen, int od, NodeScale sc,
                                                              float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float mcTile[];
   const int TE = 1 << logTE;
@@ -181,9 +161,43 @@ __global__ __launch_bounds__(256) void k_mc_quantiles_scaled(const float* __rest
   }
 }
 
+// What the three score kernels share: the samples and labels of a call and its tiling, one workgroup per tile of TE
+// consecutive elements of one (b, horizon) row of N * od
+struct McTileView {
+  const float* samples;   // (S, B, out, N, od)
+  LabelView lab;
+  int S, P, logTE;
+  int tilesPerRow;
+  long long E;
+};
+// the tile of this workgroup: its row (b, o), its first position r0 in the row and first element e0, its valid columns
+struct McTileAt { int b, o, r0, nValid; size_t e0; };
+__device__ __forceinline__ McTileAt mc_tile_at(const McTileView& t) {
+  const int rowLen = t.lab.N * t.lab.od;
+  const int row = blockIdx.x / t.tilesPerRow, tile = blockIdx.x - row * t.tilesPerRow;
+  McTileAt at;
+  at.b = row / t.lab.outSteps; at.o = row - at.b * t.lab.outSteps;
+  at.r0 = tile << t.logTE;
+  at.nValid = min(1 << t.logTE, rowLen - at.r0);
+  at.e0 = (size_t)row * rowLen + at.r0;
+  return at;
+}
+
+// host: the view, field by field, into a block that keeps its own argument order (McScoreArgs, McConformityArgs)
+template <class Args>
+void mc_loose_fields(const McTileView& t, Args* a) {
+  a->samples = t.samples; a->y = t.lab.y; a->labelStart = t.lab.labelStart;
+  a->S = t.S; a->P = t.P; a->logTE = t.logTE; a->tilesPerRow = t.tilesPerRow; a->E = t.E;
+  a->outSteps = t.lab.outSteps; a->N = t.lab.N; a->od = t.lab.od;
+  a->ySteps = t.lab.ySteps; a->yFeat = t.lab.yFeat; a->yStart = t.lab.yStart;
+}
+
+// k_mc_scores keeps the argument order and every statement it had before LabelView and McTileView: with the view embedded
+// it measured slower than that by more than the run-to-run gap in one session of three, and its
+// instructions move with any rewording (sharing statements with k_mc_scores_nodes once cost it 18 scalar spills)
 struct McScoreArgs {
   const float* samples;   // (S, B, out, N, od)
-  const float* y;         // (B, ySteps, N, yFeat) windows, or the raw series (ySteps, N, yFeat) when labelStart != null
+  const float* y;         // the fields of LabelView
   const int* labelStart;
   int S, P, logTE;
   int outSteps, N, od, ySteps, yFeat, yStart, tilesPerRow;
@@ -209,9 +223,10 @@ __global__ __launch_bounds__(256) void k_mc_scores(McScoreArgs a, McLevels lv) {
   const bool inRow = e < nValid;
   float l = 0.f;
   if (inRow) {
+    // label_row and label_at written out: through them the compiler schedules this kernel differently (see above)
     const size_t yrow = a.labelStart ? series_row((long)a.labelStart[b] + o, a.ySteps) : (size_t)b * a.ySteps + o;
     const int r = r0 + e, n = r / a.od, c = r - n * a.od;
-    l = mc_affine(a.y[(yrow * a.N + n) * a.yFeat + a.yStart + c], a.std, a.mean);
+    l = scale_affine(a.y[(yrow * a.N + n) * a.yFeat + a.yStart + c], a.std, a.mean);
     if (fabsf(l) < a.minS) l = 0.f;
   }
   const bool nanMask = a.nullVal != a.nullVal;
@@ -286,49 +301,41 @@ __global__ __launch_bounds__(64) void k_mc_accumulate(const double* __restrict__
 // of every element (zeros for a masked one) to stage 2, which owns one (horizon, node, sum) per thread and adds its
 // terms one at a time in ascending (b, c) onto the stored value: a chain of adds whose order the data alone fixes.
 struct McNodeArgs {
-  const float* samples;   // (S, B, out, N, od)
-  const float* y;         // as McScoreArgs
-  const int* labelStart;
-  int S, P, logTE;
-  int outSteps, N, od, ySteps, yFeat, yStart, tilesPerRow;
-  long long E;
-  McScale sc;
+  McTileView t;
+  NodeScale sc;
   float truthMin, minS, nullVal;
-  double* terms;          // [E][5 + n]
 };
+// the label of element (n, c) of the tile's row on the re-transformed scale, filtered; false where a mask drops it
+__device__ __forceinline__ bool mc_node_label(const McNodeArgs& a, const McTileAt& at, int n, int c, float& l) {
+  l = descale_node(a.sc, n, label_at(a.t.lab, label_row(a.t.lab, at.b, at.o), n, c));
+  const bool keep = !(a.truthMin == a.truthMin) || l > a.truthMin;
+  if (fabsf(l) < a.minS) l = 0.f;
+  return keep && (a.nullVal != a.nullVal ? l == l : l != a.nullVal);
+}
 
-__global__ __launch_bounds__(256) void k_mc_scores_nodes(McNodeArgs a, McLevels lv) {
+// terms: [E][5 + n]
+__global__ __launch_bounds__(256) void k_mc_scores_nodes(McNodeArgs a, McLevels lv, double* __restrict__ terms) {
   extern __shared__ __attribute__((aligned(16))) float mcTile[];
-  const int logTE = a.logTE, TE = 1 << logTE, tid = threadIdx.x;
-  const int rowLen = a.N * a.od;
-  const int row = blockIdx.x / a.tilesPerRow, t = blockIdx.x - row * a.tilesPerRow;
-  const int b = row / a.outSteps, o = row - b * a.outSteps;
-  const int r0 = t << logTE;
-  const int nValid = min(TE, rowLen - r0);
-  const size_t e0 = (size_t)row * rowLen + r0;
+  const McTileView& t = a.t;
+  const int logTE = t.logTE, TE = 1 << logTE, tid = threadIdx.x, S = t.S;
+  const McTileAt at = mc_tile_at(t);
   const int e = tid & (TE - 1);
-  const int r = r0 + e, n = r / a.od, c = r - n * a.od;   // a node of the row where e < nValid
-  const bool inRow = e < nValid;
-  mc_sort_tile_scaled(mcTile, a.samples, a.S, a.P, logTE, (size_t)a.E, e0, nValid, n, a.sc);
+  const int r = at.r0 + e, n = r / t.lab.od, c = r - n * t.lab.od;   // a node of the row where e < nValid
+  const bool inRow = e < at.nValid;
+  mc_sort_tile_scaled(mcTile, t.samples, S, t.P, logTE, (size_t)t.E, at.e0, at.nValid, n, a.sc);
 
   float l = 0.f;
   bool keep = false;
-  if (inRow) {
-    const size_t yrow = a.labelStart ? series_row((long)a.labelStart[b] + o, a.ySteps) : (size_t)b * a.ySteps + o;
-    l = mc_descale_node(a.sc, n, a.y[(yrow * a.N + n) * a.yFeat + a.yStart + c]);
-    keep = !(a.truthMin == a.truthMin) || l > a.truthMin;
-    if (fabsf(l) < a.minS) l = 0.f;
-    keep = keep && (a.nullVal != a.nullVal ? l == l : l != a.nullVal);
-  }
+  if (inRow) keep = mc_node_label(a, at, n, c, l);
   // from here to the terms v[]: the statements of k_mc_scores, which stays as it was (sharing them through inline
   // functions cost that kernel 18 scalar-register spills); tests hold the two kernels' sums together
   const int slot = tid >> logTE, slots = 256 >> logTE;
   const double ld = (double)l;
   double sAbs = 0.0, sWgt = 0.0;
-  for (int i = slot; i < a.S; i += slots) {
+  for (int i = slot; i < S; i += slots) {
     const double xi = (double)mcTile[(mc_row(i) << logTE) + e];
     sAbs += fabs(xi - ld);
-    sWgt += mc_mul((double)(2 * i - a.S + 1), xi);      // exact: an integer below 2^11 times an fp32 value
+    sWgt += mc_mul((double)(2 * i - S + 1), xi);        // exact: an integer below 2^11 times an fp32 value
   }
   float qv[MC_MAX_PROBS];
 #pragma unroll
@@ -344,7 +351,7 @@ __global__ __launch_bounds__(256) void k_mc_scores_nodes(McNodeArgs a, McLevels 
   if (keep) {
     double A = 0.0, W = 0.0;
     for (int s = 0; s < slots; ++s) { A += red[2 * ((s << logTE) + e)]; W += red[2 * ((s << logTE) + e) + 1]; }
-    const double Sd = (double)a.S;
+    const double Sd = (double)S;
     float qFirst = 0.f, qLast = 0.f;
 #pragma unroll
     for (int k = 0; k < MC_MAX_PROBS; ++k) {
@@ -366,7 +373,7 @@ __global__ __launch_bounds__(256) void k_mc_scores_nodes(McNodeArgs a, McLevels 
     }
   }
   const int K = MC_SCORE_SUMS + lv.n;
-  double* out = a.terms + (e0 + e) * K;
+  double* out = terms + (at.e0 + e) * K;
 #pragma unroll
   for (int k = 0; k < MC_MAX_SUMS; ++k)
     if (k < K) out[k] = v[k];

@@ -40,7 +40,7 @@ __global__ void k_region_affine(float* __restrict__ dst, float mean, float std) 
 }
 
 struct RegionGradArgs {
-  LossArgs id;             // pred = P, y = L: the totals (rows, G, od); mean 0, std 1; the descriptor's nullVal, minS, delta
+  LossArgs id;             // pred = P, lab.y = L: the totals (rows, G, od); mean 0, std 1; the descriptor's nullVal, minS, delta
   const double* kept;      // what k_loss_final left: the kept count, the fp64 mse
   const float* upstream;
   const float* base;       // (rows, N, od) or null; may be dpred
@@ -98,7 +98,7 @@ __device__ __forceinline__ double region_chain(const RegionGradArgs& a, const in
       if (TILE) {
         v[u] = q[o[u]];
       } else {
-        v[u] = k + u < k1 ? region_coeff<KIND, MASKED>(a.id, a.id.pred[rowAt + o[u]], a.id.y[rowAt + o[u]], cnt, rmse) : 0.f;
+        v[u] = k + u < k1 ? region_coeff<KIND, MASKED>(a.id, a.id.pred[rowAt + o[u]], a.id.lab.y[rowAt + o[u]], cnt, rmse) : 0.f;
       }
     }
 #pragma unroll
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(REGION_THREADS) void k_region_grad_tile(RegionGradA
     const size_t at = (size_t)row0 * GC;
     const int nq = nRows * GC;                                       // <= REGION_Q_FLOATS
     for (int i = tid; i < nq; i += REGION_THREADS)
-      regionTile[i] = region_coeff<KIND, MASKED>(a.id, a.id.pred[at + i], a.id.y[at + i], cnt, rmse);
+      regionTile[i] = region_coeff<KIND, MASKED>(a.id, a.id.pred[at + i], a.id.lab.y[at + i], cnt, rmse);
   }
   // ---- the by-node map, where it fits behind them ---------------------------------------------------------------------------
   int* mapGroup = reinterpret_cast<int*>(regionTile + a.R * GC);

@@ -1,6 +1,6 @@
 // matgcn_regions.hip - totals over groups of nodes ("regions": counties, districts, corridors) of a (rows, N, od) tensor on
 // the re-transformed scale (matgcn_group_sums) and of the labels of a batch (matgcn_group_label_sums; include/matgcn.h).
-// Included by matgcn_capi.hip after matgcn_mc_scores.hip, whose descriptor (McScale, mc_descale_node) it uses unchanged.
+// Included by matgcn_capi.hip after matgcn_kernels.hip, whose descriptor (NodeScale, descale_node) it uses unchanged.
 //
 // A region map is a CSR list over groups.  One thread owns one (row, group, channel) chain from its first member to its
 // last: it starts from 0.0 in fp64, adds (double)weight[k] * (double)v(node[k]) for k = ptr[g] .. ptr[g + 1] - 1 in
@@ -38,8 +38,8 @@ struct GroupMap {
 };
 
 // the member arithmetic: both affines, then the clamp from below (NaN: off; a NaN value stays NaN)
-__device__ __forceinline__ float group_member(const McScale& sc, int n, float v) {
-  v = mc_descale_node(sc, n, v);
+__device__ __forceinline__ float group_member(const NodeScale& sc, int n, float v) {
+  v = descale_node(sc, n, v);
   if (sc.clampMin == sc.clampMin && v < sc.clampMin) v = sc.clampMin;
   return v;
 }
@@ -54,7 +54,7 @@ __device__ __forceinline__ int group_node(const GroupMap& m, int k, int N) {
 // independent of each other and of the sum; the adds are not reordered.  A slot behind the end re-reads member k1 - 1 and
 // is not added.
 template <bool STAGED>
-__device__ __forceinline__ float group_chain(const int* node, const float* weight, const McScale& sc, int N, int k0, int k1,
+__device__ __forceinline__ float group_chain(const int* node, const float* weight, const NodeScale& sc, int N, int k0, int k1,
                                              const float* x, size_t nodeStride) {
   double acc = 0.0;
   for (int k = k0; k < k1; k += GROUP_AHEAD) {
@@ -91,7 +91,7 @@ struct GroupTileArgs {
   int mapAt;             // >= 0: the map's element offsets (and weights) are staged in LDS from this float of the tile on
   int members;
   int stepQuot, stepRem; // 4 * GROUP_THREADS = stepQuot * rowLen + stepRem
-  McScale sc;
+  NodeScale sc;
   GroupMap map;
   float* out;            // (rows, G, od)
 };
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group_sums_tile(GroupTileArgs
     if (a.mapAt >= 0) {
       total = group_chain<true>(mapNode, mapWeight, a.sc, a.N, k0, k1, x, 0);
     } else {                                                         // the tile holds member values: nothing left to de-scale
-      McScale none;
+      NodeScale none;
       none.mean = none.std = none.mean2 = none.std2 = nullptr; none.perNode = 0; none.clampMin = __builtin_nanf("");
       total = group_chain<false>(a.map.node, a.map.weight, none, a.N, k0, k1, x, (size_t)od);
     }
@@ -169,13 +169,14 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group_sums_tile(GroupTileArgs
 }
 
 struct GroupWalkArgs {
+  // the argument order from before LabelView (k_group_walk measured slower with the view embedded: DESIGN.md 5f)
   const float* src;        // values (rows, N, od), or labels: windows (B, ySteps, N, yFeat) / the raw series (ySteps, N, yFeat)
   const int* labelStart;   // labels over the series, else null
   int labels;              // 1: src holds labels, row = b * outSteps + o
   int outSteps, ySteps, yFeat, yStart;
   int N, od;
   long long total;         // rows * G * od chains
-  McScale sc;
+  NodeScale sc;
   GroupMap map;
   float* out;              // (rows, G, od)
 };
@@ -190,10 +191,9 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group_walk(GroupWalkArgs a) {
   const float* x;
   int nodeStride;
   if (a.labels) {
+    const LabelView v = {a.src, a.labelStart, a.outSteps, a.N, a.od, a.ySteps, a.yFeat, a.yStart};
     const long long b = row / a.outSteps;
-    const int o = (int)(row - b * a.outSteps);
-    const size_t yrow = a.labelStart ? series_row((long)a.labelStart[b] + o, a.ySteps) : (size_t)b * a.ySteps + o;
-    x = a.src + yrow * a.N * a.yFeat + a.yStart + c;
+    x = label_ptr(v, label_row(v, b, (int)(row - b * a.outSteps)), 0) + c;
     nodeStride = a.yFeat;
   } else {
     x = a.src + (size_t)row * a.N * a.od + c;
