@@ -211,6 +211,7 @@ PROF_KINDS = {1: "k_mix", 2: "k_gate", 4: "k_update", 8: "k_res_gru", 16: "k_px"
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 _lib = None
+_entries: dict = {}     # name -> the loaded function, as call() has looked it up
 
 
 def load() -> C.CDLL:
@@ -241,3 +242,17 @@ def check(status: int, what: str) -> None:
     if status != 0:
         msg = load().matgcn_error_string(status).decode()
         raise MatgcnError("%s failed: %s (status %d)" % (what, msg, status))
+
+
+def call(name: str, *args) -> None:
+    """Entry point ``name`` of the loaded library on ``args``, its status checked under the same name.  ``argtypes`` are set
+    for every symbol, so plain ints (device pointers included), floats, None (NULL) and byref(...) go in as they are.  A
+    name include/matgcn.h does not declare raises before anything is called."""
+    fn = _entries.get(name)
+    if fn is None:
+        if name not in _SIGNATURES:
+            raise MatgcnError("%s is not an entry point of libmatgcn.so" % name)
+        fn = _entries[name] = getattr(load(), name)
+    status = fn(*args)
+    if status != 0:
+        check(status, name)

@@ -11,7 +11,7 @@ import contextlib
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -133,8 +133,17 @@ def spec_from_config(config, data_feature, num_nodes: int, adj_rank: int, n_stat
         gcn_off=bool(config.get("gcn_off", False)), fnn_off=bool(config.get("fnn_off", False)))
 
 
+# ---- the shared pieces of every wrapper below ----------------------------------------------------------------------------
+# _lib.call(name, *args) looks the entry point up, calls it and checks its status: the signature table converts plain ints
+# (device pointers), floats and None (NULL).  _stream: the caller's stream.  _label_view: the label contract, once.
+# _out_arg: the one check of a tensor the caller hands in to be written.  _scratch: the one get / clear-when-full / put of the scratch caches.
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
+
+
+def _stream(device) -> int:
+    """torch's current HIP stream on ``device`` at call time, as the handle the C ABI takes"""
+    return torch.cuda.current_stream(device).cuda_stream
 
 
 def _check_tensor(t: torch.Tensor, name: str, shape=None) -> torch.Tensor:
@@ -147,44 +156,108 @@ def _check_tensor(t: torch.Tensor, name: str, shape=None) -> torch.Tensor:
     return t.contiguous()
 
 
+def _out_arg(t: Optional[torch.Tensor], shape, dtype, device, name: str):
+    """(the tensor an entry point writes, whether the caller gave it): a fresh one, or the caller's own - running sums or
+    counts to add to, a slice of a store to fill - after the one check there is: same device, exact dtype, exact shape,
+    contiguous.  The library writes it as dense memory, so nothing here may be converted or copied."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device), False
+    if tuple(t.shape) != shape or t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise _lib.MatgcnError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, device))
+    return t, True
+
+
+_mc_scratch: Dict[tuple, torch.Tensor] = {}     # (device, entry point, batch, out, nodes, od, S, levels) -> stage-1 partials
+_norm_scratch: Dict[tuple, torch.Tensor] = {}   # (device, bytes) -> the per-chunk partials of matgcn_grad_norm
+_SCRATCH_ENTRIES = 16                           # per cache
+
+
+def _scratch(cache: Dict[tuple, torch.Tensor], key: tuple, nbytes: int, device) -> torch.Tensor:
+    """fp64 scratch of ``nbytes`` (one element at least) that the calls of one ``key`` on one device share - a call writes
+    it before it reads it, in stream order -, kept in ``cache``, which is cleared when it is full."""
+    key = (device,) + key
+    t = cache.get(key)
+    if t is None:
+        if len(cache) >= _SCRATCH_ENTRIES:
+            cache.clear()
+        t = cache[key] = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=device)
+    return t
+
+
 def debug_gemm(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, desc, alpha=1.0, beta=0.0) -> None:
     """matgcn_debug_gemm on raw buffers (tests): desc = the 22 integers of include/matgcn.h."""
-    lib = _lib.load()
     arr = (C.c_int64 * 22)(*[int(v) for v in desc])
-    stream = C.c_void_p(torch.cuda.current_stream(c.device).cuda_stream)
-    _lib.check(lib.matgcn_debug_gemm(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(c.data_ptr()), arr,
-                                     C.c_float(alpha), C.c_float(beta), stream), "matgcn_debug_gemm")
+    _lib.call("matgcn_debug_gemm", a.data_ptr(), b.data_ptr(), c.data_ptr(), arr, float(alpha), float(beta),
+              _stream(c.device))
 
 
-def _label_geometry(pred, y, label_start):
-    """(y, label_start, y_steps, y_feat) checked: y is (B, y_steps, N, F) windows, or - with label_start (B) int32 -
-    the raw series (T, N, F) whose rows label_start[b] .. +out are sample b's targets"""
-    b, out, n, od = pred.shape
+class _LabelView(NamedTuple):
+    """The label contract (include/matgcn.h) of one call, checked: the contiguous tensors and the geometry every
+    label-reading entry point takes.  Built by _label_view; autograd functions keep it for their backward."""
+    pred: Optional[torch.Tensor]    # (B, out, N, od), the samples (S, B, out, N, od), or None (built from a shape)
+    y: torch.Tensor                 # (B, y_steps, N, F) windows, or the raw series (T, N, F)
+    label_start: Optional[torch.Tensor]     # (B,) int32 with the series: rows label_start[b] .. + out are b's targets
+    b: int
+    out: int
+    n: int
+    od: int
+    y_steps: int
+    y_feat: int
+
+    def save(self, ctx, *more) -> "_LabelView":
+        """pred, y and ``more`` go through ctx.save_for_backward (released with the graph, as they always were); returns
+        what an autograd function keeps on ctx beside them: the geometry and label_start"""
+        ctx.save_for_backward(self.pred, self.y, *more)
+        return self._replace(pred=None, y=None)
+
+    def saved(self, ctx) -> list:
+        """[the whole view again, *more] in backward"""
+        pred, y, *more = ctx.saved_tensors
+        return [self._replace(pred=pred, y=y)] + more
+
+    def args(self, y_start) -> tuple:
+        """the leading C arguments: [pred | samples, S], y, label_start, b, out, n, od, y_steps, y_feat, y_start"""
+        p = self.pred
+        lead = () if p is None else (p.data_ptr(),) if p.dim() == 4 else (p.data_ptr(), int(p.shape[0]))
+        return lead + (self.y.data_ptr(), _ptr(self.label_start), self.b, self.out, self.n, self.od, self.y_steps,
+                       self.y_feat, int(y_start))
+
+
+def _label_view(pred, y, label_start, samples: bool = False) -> _LabelView:
+    """``pred``: the prediction (B, out, N, od) - ``samples``: the ensemble (S, B, out, N, od) - or the bare shape
+    (B, out, N, od) of an entry point that reads labels only.  ``y`` is (B, y_steps, N, F) windows, or - with label_start
+    (B) int32 - the raw series (T, N, F).  Every refusal is a MatgcnError."""
+    if isinstance(pred, torch.Tensor):
+        pred = _check_tensor(pred, "samples" if samples else "pred")
+        if pred.dim() != (5 if samples else 4):
+            raise _lib.MatgcnError("%s has shape %s, expected %s" % (
+                ("samples", tuple(pred.shape), "(S, B, out, N, od)") if samples else
+                ("pred", tuple(pred.shape), "(B, out, N, od)")))
+        shape = pred.shape[1:] if samples else pred.shape
+    else:
+        shape, pred = pred, None
+    b, out, n, od = shape
     y = _check_tensor(y, "y")
     if label_start is None:
         if y.dim() != 4 or y.shape[0] != b or y.shape[2] != n:
-            raise _lib.MatgcnError("y has shape %s, incompatible with pred %s" % (tuple(y.shape), tuple(pred.shape)))
-        return y, None, int(y.shape[1]), int(y.shape[3])
+            raise _lib.MatgcnError("y has shape %s, incompatible with pred %s" % (tuple(y.shape), (b, out, n, od)))
+        return _LabelView(pred, y, None, b, out, n, od, int(y.shape[1]), int(y.shape[3]))
     if y.dim() != 3 or y.shape[1] != n:
         raise _lib.MatgcnError("series has shape %s, expected (T, %d, F)" % (tuple(y.shape), n))
-    if not label_start.is_cuda or label_start.dtype != torch.int32 or tuple(label_start.shape) != (b,):
+    if not isinstance(label_start, torch.Tensor) or not label_start.is_cuda or label_start.dtype != torch.int32 or \
+            tuple(label_start.shape) != (b,):
         raise _lib.MatgcnError("label_start must be a CUDA int32 tensor of shape (%d,)" % b)
-    return y, label_start.contiguous(), int(y.shape[0]), int(y.shape[2])
+    return _LabelView(pred, y, label_start.contiguous(), b, out, n, od, int(y.shape[0]), int(y.shape[2]))
 
 
-def _mae_call(pred, y, y_start, mean, std, null_val, min_s, label_start=None):
-    lib = _lib.load()
-    pred = _check_tensor(pred, "pred")
-    b, out, n, od = pred.shape
-    y, label_start, y_steps, y_feat = _label_geometry(pred, y, label_start)
-    partials = torch.empty(2 * b * out + 1, dtype=torch.float32, device=pred.device)
-    result = torch.empty(1 + out, dtype=torch.float32, device=pred.device)
-    stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-    _lib.check(lib.matgcn_masked_mae(C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(label_start)),
-                                     b, out, n, od, y_steps, y_feat, int(y_start), float(mean), float(std),
-                                     float(null_val), float(min_s), C.c_void_p(partials.data_ptr()),
-                                     C.c_void_p(result.data_ptr()), stream), "matgcn_masked_mae")
-    return pred, y, partials, result, label_start
+def _mae_call(v: _LabelView, y_start, mean, std, null_val, min_s):
+    """the value call: (partials - kept for the gradient -, result (1 + out,))"""
+    dev = v.pred.device
+    partials = torch.empty(2 * v.b * v.out + 1, dtype=torch.float32, device=dev)
+    result = torch.empty(1 + v.out, dtype=torch.float32, device=dev)
+    _lib.call("matgcn_masked_mae", *v.args(y_start), float(mean), float(std), float(null_val), float(min_s),
+              partials.data_ptr(), result.data_ptr(), _stream(dev))
+    return partials, result
 
 
 def masked_mae_device(pred: torch.Tensor, y: torch.Tensor, y_start: int, mean: float, std: float,
@@ -193,7 +266,12 @@ def masked_mae_device(pred: torch.Tensor, y: torch.Tensor, y_start: int, mean: f
     """(1 + out,) tensor [masked-MAE over all horizons, MAE@1 .. MAE@out] computed on the device by
     matgcn_masked_mae (de-scale + mask + reduce; reference loss.py:17-29, traffic_state_evaluator.py:87-104).
     With label_start, y is the raw series and the targets are gathered on the device."""
-    return _mae_call(pred, y, y_start, mean, std, null_val, min_s, label_start)[3]
+    return _mae_call(_label_view(pred, y, label_start), y_start, mean, std, null_val, min_s)[1]
+
+
+def _upstream(upstream: torch.Tensor) -> torch.Tensor:
+    """the upstream gradient of a scalar loss as the (1,) float32 device tensor the gradient kernels read"""
+    return upstream.detach().to(torch.float32).reshape(1).contiguous()
 
 
 class _MaskedMAE(torch.autograd.Function):
@@ -201,26 +279,21 @@ class _MaskedMAE(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, y, y_start, mean, std, null_val, min_s, label_start):
-        pred_c, y_c, partials, result, ls = _mae_call(pred.detach(), y, y_start, mean, std, null_val, min_s, label_start)
-        ctx.save_for_backward(pred_c, y_c, partials)
-        ctx.label_start = ls
+        v = _label_view(pred.detach(), y, label_start)
         ctx.args = (int(y_start), float(mean), float(std), float(null_val), float(min_s))
+        partials, result = _mae_call(v, *ctx.args)
+        ctx.view = v.save(ctx, partials)
         return result[0].clone()
 
     @staticmethod
     def backward(ctx, upstream):
-        pred, y, partials = ctx.saved_tensors
-        y_start, mean, std, null_val, min_s = ctx.args
-        b, out, n, od = pred.shape
-        ls = ctx.label_start
-        y_steps, y_feat = (int(y.shape[1]), int(y.shape[3])) if ls is None else (int(y.shape[0]), int(y.shape[2]))
+        v, partials = ctx.view.saved(ctx)
+        pred = v.pred
         d_pred = torch.empty_like(pred)
-        up = upstream.detach().to(torch.float32).reshape(1).contiguous()
-        stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-        _lib.check(_lib.load().matgcn_masked_mae_grad(
-            C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(ls)), b, out, n, od, y_steps, y_feat,
-            y_start, mean, std, null_val, min_s, C.c_void_p(partials.data_ptr()), C.c_void_p(up.data_ptr()),
-            C.c_void_p(d_pred.data_ptr()), stream), "matgcn_masked_mae_grad")
+        up = _upstream(upstream)
+        y_start, *scale = ctx.args
+        _lib.call("matgcn_masked_mae_grad", *v.args(y_start), *scale, partials.data_ptr(), up.data_ptr(),
+                  d_pred.data_ptr(), _stream(pred.device))
         return d_pred, None, None, None, None, None, None, None
 
 
@@ -265,23 +338,16 @@ def train_loss_desc(name: str, mean: float, std: float, delta=None) -> "_lib.Los
     return _lib.LossDesc(kind, float(mean), float(std), null_val, TRAIN_LOSS_MIN_S if masked else 0.0, delta)
 
 
-def _loss_call(pred, y, y_start, desc, label_start=None):
-    lib = _lib.load()
-    pred = _check_tensor(pred, "pred")
-    if pred.dim() != 4:
-        raise _lib.MatgcnError("pred has shape %s, expected (B, out, N, od)" % (tuple(pred.shape),))
-    b, out, n, od = pred.shape
-    y, label_start, y_steps, y_feat = _label_geometry(pred, y, label_start)
+def _loss_call(v: _LabelView, y_start, desc):
+    """the value call: (scratch - kept for the gradient, so per call -, result (1 + out,))"""
+    dev = v.pred.device
     need = C.c_size_t()
-    _lib.check(lib.matgcn_loss_bytes(b, out, C.byref(need)), "matgcn_loss_bytes")
-    scratch = torch.empty(need.value // 8, dtype=torch.float64, device=pred.device)
-    result = torch.empty(1 + out, dtype=torch.float32, device=pred.device)
-    stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-    _lib.check(lib.matgcn_loss(C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(label_start)),
-                               b, out, n, od, y_steps, y_feat, int(y_start), C.byref(desc),
-                               C.c_void_p(scratch.data_ptr()), need.value, C.c_void_p(result.data_ptr()), stream),
-               "matgcn_loss")
-    return pred, y, scratch, result, label_start
+    _lib.call("matgcn_loss_bytes", v.b, v.out, C.byref(need))
+    scratch = torch.empty(need.value // 8, dtype=torch.float64, device=dev)
+    result = torch.empty(1 + v.out, dtype=torch.float32, device=dev)
+    _lib.call("matgcn_loss", *v.args(y_start), C.byref(desc), scratch.data_ptr(), need.value, result.data_ptr(),
+              _stream(dev))
+    return scratch, result
 
 
 def train_loss_device(pred: torch.Tensor, y: torch.Tensor, y_start: int, mean: float, std: float, name: str,
@@ -289,40 +355,15 @@ def train_loss_device(pred: torch.Tensor, y: torch.Tensor, y_start: int, mean: f
     """(1 + out,) tensor [the executor's objective ``name`` over all horizons, the same per horizon] computed on the
     device by matgcn_loss (de-scale + mask + fixed-order reduction).  Geometry as masked_mae_device: ``y`` windows, or
     with label_start the raw series whose targets are gathered on the device."""
-    return _loss_call(pred, y, y_start, train_loss_desc(name, mean, std, delta), label_start)[3]
-
-
-class _TrainLoss(torch.autograd.Function):
-    """one of the executor's objectives on the device with its gradient (matgcn_loss / matgcn_loss_grad)."""
-
-    @staticmethod
-    def forward(ctx, pred, y, y_start, desc, label_start):
-        pred_c, y_c, scratch, result, ls = _loss_call(pred.detach(), y, y_start, desc, label_start)
-        ctx.save_for_backward(pred_c, y_c, scratch)
-        ctx.label_start, ctx.y_start, ctx.desc = ls, int(y_start), desc
-        return result[0].clone()
-
-    @staticmethod
-    def backward(ctx, upstream):
-        pred, y, scratch = ctx.saved_tensors
-        b, out, n, od = pred.shape
-        ls = ctx.label_start
-        y_steps, y_feat = (int(y.shape[1]), int(y.shape[3])) if ls is None else (int(y.shape[0]), int(y.shape[2]))
-        d_pred = torch.empty_like(pred)
-        up = upstream.detach().to(torch.float32).reshape(1).contiguous()
-        stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-        _lib.check(_lib.load().matgcn_loss_grad(
-            C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(ls)), b, out, n, od, y_steps, y_feat,
-            ctx.y_start, C.byref(ctx.desc), C.c_void_p(scratch.data_ptr()), scratch.numel() * 8,
-            C.c_void_p(up.data_ptr()), C.c_void_p(d_pred.data_ptr()), stream), "matgcn_loss_grad")
-        return d_pred, None, None, None, None
+    return _loss_call(_label_view(pred, y, label_start), y_start, train_loss_desc(name, mean, std, delta))[1]
 
 
 def train_loss(pred: torch.Tensor, y: torch.Tensor, y_start: int, mean: float, std: float, name: str, delta=None,
                label_start: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The scalar of the executor's objective ``name`` with autograd support: matgcn_loss forward, matgcn_loss_grad
-    backward.  With label_start, y is the raw series and the targets are gathered on the device."""
-    return _TrainLoss.apply(pred, y, y_start, train_loss_desc(name, mean, std, delta), label_start)
+    backward (the tract half of tract_region_loss alone).  With label_start, y is the raw series and the targets are
+    gathered on the device."""
+    return _TractRegionLoss.apply(pred, y, None, y_start, train_loss_desc(name, mean, std, delta), label_start, 1.0, 0.0)
 
 
 _affine_uploads: Dict[tuple, torch.Tensor] = {}    # (device, the float32 bytes of a host-side affine) -> its device copy
@@ -353,7 +394,7 @@ def _affine_arg(v, n, device, name):
 
 
 def _metric_scale(n, device, mean, std, group_mean, group_std, clamp_min, truth_min, min_s):
-    """(matgcn_metric_scale, the device tensors its pointers refer to - keep them alive across the call)"""
+    """(matgcn_metric_scale, the device tensors its pointers refer to - hold them until the call is enqueued)"""
     sc = _lib.MetricScale()
     keep = []
     if (mean is None) != (std is None) or (group_mean is None) != (group_std is None):
@@ -382,23 +423,13 @@ def metric_sums(pred: torch.Tensor, y: torch.Tensor, y_start: int = 0, mean=None
     (matgcn_metric_sums, include/matgcn.h): de-scale (mean / std: the scaler, scalar or per node; group_mean /
     group_std: the per-node group-std re-transform), clamp, select, zero tiny labels and reduce on the device.
     ``sums``: running sums of earlier batches to add to (several batches = one collect over their concatenation)."""
-    lib = _lib.load()
-    pred = _check_tensor(pred, "pred")
-    b, out, n, od = pred.shape
-    y, label_start, y_steps, y_feat = _label_geometry(pred, y, label_start)
-    sc, keep = _metric_scale(n, pred.device, mean, std, group_mean, group_std, clamp_min, truth_min, min_s)
-    partials = torch.empty(b * out * _lib.METRIC_SUMS, dtype=torch.float64, device=pred.device)
-    accumulate = sums is not None
-    if sums is None:
-        sums = torch.empty(out, _lib.METRIC_SUMS, dtype=torch.float64, device=pred.device)
-    elif tuple(sums.shape) != (out, _lib.METRIC_SUMS) or sums.dtype != torch.float64 or not sums.is_cuda:
-        raise _lib.MatgcnError("sums must be a CUDA float64 tensor of shape (%d, %d)" % (out, _lib.METRIC_SUMS))
-    stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-    _lib.check(lib.matgcn_metric_sums(C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(label_start)),
-                                      b, out, n, od, y_steps, y_feat, int(y_start), C.byref(sc),
-                                      C.c_void_p(partials.data_ptr()), C.c_void_p(sums.data_ptr()), int(accumulate),
-                                      stream), "matgcn_metric_sums")
-    del keep
+    v = _label_view(pred, y, label_start)
+    dev = v.pred.device
+    sc, _keep = _metric_scale(v.n, dev, mean, std, group_mean, group_std, clamp_min, truth_min, min_s)
+    partials = torch.empty(v.b * v.out * _lib.METRIC_SUMS, dtype=torch.float64, device=dev)
+    sums, given = _out_arg(sums, (v.out, _lib.METRIC_SUMS), torch.float64, dev, "sums")
+    _lib.call("matgcn_metric_sums", *v.args(y_start), C.byref(sc), partials.data_ptr(), sums.data_ptr(), int(given),
+              _stream(dev))
     return sums
 
 
@@ -407,19 +438,8 @@ def metric_table(sums: torch.Tensor, swap_r2: bool = False) -> torch.Tensor:
     "average" mode; metric order _lib.METRICS (matgcn_metric_table)."""
     out = int(sums.shape[0])
     table = torch.empty(2, out, len(_lib.METRICS), dtype=torch.float64, device=sums.device)
-    stream = C.c_void_p(torch.cuda.current_stream(sums.device).cuda_stream)
-    _lib.check(_lib.load().matgcn_metric_table(C.c_void_p(sums.data_ptr()), out, int(bool(swap_r2)),
-                                               C.c_void_p(table.data_ptr()), stream), "matgcn_metric_table")
+    _lib.call("matgcn_metric_table", sums.data_ptr(), out, int(bool(swap_r2)), table.data_ptr(), _stream(sums.device))
     return table
-
-
-def _sums_arg(sums, shape, device):
-    """(sums to write, accumulate flag): a fresh tensor, or the caller's running sums after a check"""
-    if sums is None:
-        return torch.empty(shape, dtype=torch.float64, device=device), 0
-    if tuple(sums.shape) != tuple(shape) or sums.dtype != torch.float64 or not sums.is_cuda or not sums.is_contiguous():
-        raise _lib.MatgcnError("sums must be a contiguous CUDA float64 tensor of shape %s" % (tuple(shape),))
-    return sums, 1
 
 
 def metric_sums_nodes(pred: torch.Tensor, y: torch.Tensor, y_start: int = 0, mean=None, std=None, group_mean=None,
@@ -429,23 +449,15 @@ def metric_sums_nodes(pred: torch.Tensor, y: torch.Tensor, y_start: int = 0, mea
     """(out, N, 14) float64 device tensor: the sums of ``metric_sums`` per horizon AND node (matgcn_metric_sums_nodes),
     every entry added up over batch and channel in a fixed order - feeding a test set batch by batch through ``sums``
     gives the bits of one call over all of it."""
-    lib = _lib.load()
-    pred = _check_tensor(pred, "pred")
-    if pred.dim() != 4:
-        raise _lib.MatgcnError("pred has shape %s, expected (B, out, N, od)" % (tuple(pred.shape),))
-    b, out, n, od = (int(v) for v in pred.shape)
-    y, label_start, y_steps, y_feat = _label_geometry(pred, y, label_start)
-    sc, keep = _metric_scale(n, pred.device, mean, std, group_mean, group_std, clamp_min, truth_min, min_s)
+    v = _label_view(pred, y, label_start)
+    dev = v.pred.device
+    sc, _keep = _metric_scale(v.n, dev, mean, std, group_mean, group_std, clamp_min, truth_min, min_s)
     need = C.c_size_t(0)
-    _lib.check(lib.matgcn_metric_sums_nodes_bytes(b, out, n, od, C.byref(need)), "matgcn_metric_sums_nodes_bytes")
-    scratch = torch.empty(need.value // 8, dtype=torch.float64, device=pred.device) if need.value else None
-    sums, accumulate = _sums_arg(sums, (out, n, _lib.METRIC_SUMS), pred.device)
-    stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-    _lib.check(lib.matgcn_metric_sums_nodes(C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()),
-                                            C.c_void_p(_ptr(label_start)), b, out, n, od, y_steps, y_feat, int(y_start),
-                                            C.byref(sc), C.c_void_p(_ptr(scratch)), C.c_size_t(need.value),
-                                            C.c_void_p(sums.data_ptr()), accumulate, stream), "matgcn_metric_sums_nodes")
-    del keep
+    _lib.call("matgcn_metric_sums_nodes_bytes", v.b, v.out, v.n, v.od, C.byref(need))
+    scratch = torch.empty(need.value // 8, dtype=torch.float64, device=dev) if need.value else None
+    sums, given = _out_arg(sums, (v.out, v.n, _lib.METRIC_SUMS), torch.float64, dev, "sums")
+    _lib.call("matgcn_metric_sums_nodes", *v.args(y_start), C.byref(sc), _ptr(scratch), need.value, sums.data_ptr(),
+              int(given), _stream(dev))
     return sums
 
 
@@ -461,9 +473,8 @@ def metric_table_rows(sums: torch.Tensor, fold: int = 1, swap_r2: bool = False) 
         raise _lib.MatgcnError("fold = %d does not divide the %d rows of sums" % (fold, total))
     rows = total // fold
     table = torch.empty(rows, len(_lib.METRICS), dtype=torch.float64, device=sums.device)
-    stream = C.c_void_p(torch.cuda.current_stream(sums.device).cuda_stream)
-    _lib.check(_lib.load().matgcn_metric_table_rows(C.c_void_p(sums.data_ptr()), rows, fold, int(bool(swap_r2)),
-                                                    C.c_void_p(table.data_ptr()), stream), "matgcn_metric_table_rows")
+    _lib.call("matgcn_metric_table_rows", sums.data_ptr(), rows, fold, int(bool(swap_r2)), table.data_ptr(),
+              _stream(sums.device))
     return table
 
 
@@ -485,18 +496,13 @@ def mc_quantiles(samples: torch.Tensor, probs: Sequence[float], mean: float = 0.
     ``samples`` (S, ...) as HotPath.forward_mc(keep_samples=True) returns them, de-scaled as x*std + mean on load;
     ``probs`` up to 8 ascending levels in [0, 1].  Returns (len(probs), *samples.shape[1:]) - numpy's "linear" rule in
     float32, no sorted copy of the samples anywhere."""
-    lib = _lib.load()
     samples = _mc_samples(samples)
     levels, nq = _mc_probs(probs)
     s, elems = int(samples.shape[0]), samples[0].numel()
     out = torch.empty((nq,) + tuple(samples.shape[1:]), dtype=torch.float32, device=samples.device)
-    stream = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
-    _lib.check(lib.matgcn_mc_quantiles(C.c_void_p(samples.data_ptr()), s, elems, levels, nq, float(mean), float(std),
-                                       C.c_void_p(out.data_ptr()), stream), "matgcn_mc_quantiles")
+    _lib.call("matgcn_mc_quantiles", samples.data_ptr(), s, elems, levels, nq, float(mean), float(std), out.data_ptr(),
+              _stream(samples.device))
     return out
-
-
-_mc_scratch: Dict[tuple, torch.Tensor] = {}   # (device, batch, out, nodes, od, S, levels) -> the stage-1 partials
 
 
 def mc_scores(samples: torch.Tensor, y: torch.Tensor, probs: Sequence[float], y_start: int = 0, mean: float = 0.0,
@@ -506,33 +512,15 @@ def mc_scores(samples: torch.Tensor, y: torch.Tensor, probs: Sequence[float], y_
     level] of the ensemble ``samples`` (S, B, out, N, od) against the labels (matgcn_mc_scores, include/matgcn.h): labels,
     mask and geometry as masked_mae_device (``y`` windows, or with ``label_start`` the resident series), the interval is
     [first level, last level].  ``sums``: running sums of earlier batches to add to."""
-    lib = _lib.load()
-    samples = _mc_samples(samples)
-    if samples.dim() != 5:
-        raise _lib.MatgcnError("samples has shape %s, expected (S, B, out, N, od)" % (tuple(samples.shape),))
-    s, b, out, n, od = (int(v) for v in samples.shape)
-    y, label_start, y_steps, y_feat = _label_geometry(samples[0], y, label_start)
+    v = _label_view(samples, y, label_start, samples=True)
+    dev, s = v.pred.device, int(v.pred.shape[0])
     levels, nq = _mc_probs(probs)
     need = C.c_size_t(0)
-    _lib.check(lib.matgcn_mc_scores_bytes(b, out, n, od, s, nq, C.byref(need)), "matgcn_mc_scores_bytes")
-    key = (samples.device, b, out, n, od, s, nq)
-    scratch = _mc_scratch.get(key)
-    if scratch is None:
-        if len(_mc_scratch) >= 16:
-            _mc_scratch.clear()
-        scratch = _mc_scratch[key] = torch.empty(max(1, need.value // 8), dtype=torch.float64, device=samples.device)
-    cols = _lib.MC_SCORE_SUMS + nq
-    accumulate = sums is not None
-    if sums is None:
-        sums = torch.empty(out, cols, dtype=torch.float64, device=samples.device)
-    elif tuple(sums.shape) != (out, cols) or sums.dtype != torch.float64 or not sums.is_cuda or not sums.is_contiguous():
-        raise _lib.MatgcnError("sums must be a contiguous CUDA float64 tensor of shape (%d, %d)" % (out, cols))
-    stream = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
-    _lib.check(lib.matgcn_mc_scores(C.c_void_p(samples.data_ptr()), s, C.c_void_p(y.data_ptr()),
-                                    C.c_void_p(_ptr(label_start)), b, out, n, od, y_steps, y_feat, int(y_start),
-                                    float(mean), float(std), float(null_val), float(min_s), levels, nq,
-                                    C.c_void_p(scratch.data_ptr()), C.c_size_t(scratch.numel() * 8),
-                                    C.c_void_p(sums.data_ptr()), int(accumulate), stream), "matgcn_mc_scores")
+    _lib.call("matgcn_mc_scores_bytes", v.b, v.out, v.n, v.od, s, nq, C.byref(need))
+    scratch = _scratch(_mc_scratch, ("mc_scores", v.b, v.out, v.n, v.od, s, nq), need.value, dev)
+    sums, given = _out_arg(sums, (v.out, _lib.MC_SCORE_SUMS + nq), torch.float64, dev, "sums")
+    _lib.call("matgcn_mc_scores", *v.args(y_start), float(mean), float(std), float(null_val), float(min_s), levels, nq,
+              scratch.data_ptr(), scratch.numel() * 8, sums.data_ptr(), int(given), _stream(dev))
     return sums
 
 
@@ -541,18 +529,15 @@ def mc_quantiles_scaled(samples: torch.Tensor, probs: Sequence[float], mean=None
     """``mc_quantiles`` on the re-transformed scale (matgcn_mc_quantiles_scaled): ``samples`` (S, ..., N, od), every
     sample de-scaled by mean / std (scalars or one pair per node), then by the per-node group_mean / group_std, and set
     to ``clamp_min`` where below it, before the sort.  Returns (len(probs), *samples.shape[1:])."""
-    lib = _lib.load()
     samples = _mc_samples(samples)
     if samples.dim() < 3:
         raise _lib.MatgcnError("samples has shape %s, expected (S, ..., N, od)" % (tuple(samples.shape),))
     levels, nq = _mc_probs(probs)
     s, elems, n, od = int(samples.shape[0]), samples[0].numel(), int(samples.shape[-2]), int(samples.shape[-1])
-    sc, keep = _metric_scale(n, samples.device, mean, std, group_mean, group_std, clamp_min, float("nan"), -1.0)
+    sc, _keep = _metric_scale(n, samples.device, mean, std, group_mean, group_std, clamp_min, float("nan"), -1.0)
     out = torch.empty((nq,) + tuple(samples.shape[1:]), dtype=torch.float32, device=samples.device)
-    stream = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
-    _lib.check(lib.matgcn_mc_quantiles_scaled(C.c_void_p(samples.data_ptr()), s, elems, n, od, levels, nq, C.byref(sc),
-                                              C.c_void_p(out.data_ptr()), stream), "matgcn_mc_quantiles_scaled")
-    del keep
+    _lib.call("matgcn_mc_quantiles_scaled", samples.data_ptr(), s, elems, n, od, levels, nq, C.byref(sc), out.data_ptr(),
+              _stream(samples.device))
     return out
 
 
@@ -564,30 +549,16 @@ def mc_scores_nodes(samples: torch.Tensor, y: torch.Tensor, probs: Sequence[floa
     ``metric_sums_nodes`` (matgcn_mc_scores_nodes) - samples and labels de-scaled by mean / std and the per-node
     group_mean / group_std, samples clamped from below before the sort, labels <= ``truth_min`` left out.  Fixed order
     of summation: feeding batches through ``sums`` gives the bits of one call over all of them."""
-    lib = _lib.load()
-    samples = _mc_samples(samples)
-    if samples.dim() != 5:
-        raise _lib.MatgcnError("samples has shape %s, expected (S, B, out, N, od)" % (tuple(samples.shape),))
-    s, b, out, n, od = (int(v) for v in samples.shape)
-    y, label_start, y_steps, y_feat = _label_geometry(samples[0], y, label_start)
+    v = _label_view(samples, y, label_start, samples=True)
+    dev, s = v.pred.device, int(v.pred.shape[0])
     levels, nq = _mc_probs(probs)
-    sc, keep = _metric_scale(n, samples.device, mean, std, group_mean, group_std, clamp_min, truth_min, min_s)
+    sc, _keep = _metric_scale(v.n, dev, mean, std, group_mean, group_std, clamp_min, truth_min, min_s)
     need = C.c_size_t(0)
-    _lib.check(lib.matgcn_mc_scores_nodes_bytes(b, out, n, od, s, nq, C.byref(need)), "matgcn_mc_scores_nodes_bytes")
-    key = ("nodes", samples.device, b, out, n, od, s, nq)
-    scratch = _mc_scratch.get(key)
-    if scratch is None:
-        if len(_mc_scratch) >= 16:
-            _mc_scratch.clear()
-        scratch = _mc_scratch[key] = torch.empty(max(1, need.value // 8), dtype=torch.float64, device=samples.device)
-    sums, accumulate = _sums_arg(sums, (out, n, _lib.MC_SCORE_SUMS + nq), samples.device)
-    stream = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
-    _lib.check(lib.matgcn_mc_scores_nodes(C.c_void_p(samples.data_ptr()), s, C.c_void_p(y.data_ptr()),
-                                          C.c_void_p(_ptr(label_start)), b, out, n, od, y_steps, y_feat, int(y_start),
-                                          C.byref(sc), float(null_val), levels, nq, C.c_void_p(scratch.data_ptr()),
-                                          C.c_size_t(scratch.numel() * 8), C.c_void_p(sums.data_ptr()), accumulate,
-                                          stream), "matgcn_mc_scores_nodes")
-    del keep
+    _lib.call("matgcn_mc_scores_nodes_bytes", v.b, v.out, v.n, v.od, s, nq, C.byref(need))
+    scratch = _scratch(_mc_scratch, ("mc_scores_nodes", v.b, v.out, v.n, v.od, s, nq), need.value, dev)
+    sums, given = _out_arg(sums, (v.out, v.n, _lib.MC_SCORE_SUMS + nq), torch.float64, dev, "sums")
+    _lib.call("matgcn_mc_scores_nodes", *v.args(y_start), C.byref(sc), float(null_val), levels, nq, scratch.data_ptr(),
+              scratch.numel() * 8, sums.data_ptr(), int(given), _stream(dev))
     return sums
 
 
@@ -599,25 +570,13 @@ def mc_conformity(samples: torch.Tensor, y: torch.Tensor, probs: Sequence[float]
     (S, B, out, N, od) against the labels, on the scale and with the label filters of ``mc_scores_nodes``
     (matgcn_mc_conformity); NaN where the label is masked or filtered out.  ``probs``: at least two levels, the outer two
     are the band.  ``out``: the tensor to write - a slice of a caller's store of scores."""
-    lib = _lib.load()
-    samples = _mc_samples(samples)
-    if samples.dim() != 5:
-        raise _lib.MatgcnError("samples has shape %s, expected (S, B, out, N, od)" % (tuple(samples.shape),))
-    s, b, steps, n, od = (int(v) for v in samples.shape)
-    y, label_start, y_steps, y_feat = _label_geometry(samples[0], y, label_start)
+    v = _label_view(samples, y, label_start, samples=True)
+    dev = v.pred.device
     levels, nq = _mc_probs(probs)
-    sc, keep = _metric_scale(n, samples.device, mean, std, group_mean, group_std, clamp_min, truth_min, min_s)
-    if out is None:
-        out = torch.empty(b, steps, n, od, dtype=torch.float32, device=samples.device)
-    elif (tuple(out.shape) != (b, steps, n, od) or out.dtype != torch.float32 or out.device != samples.device
-          or not out.is_contiguous()):
-        raise _lib.MatgcnError("out must be a contiguous CUDA float32 tensor of shape %s" % ((b, steps, n, od),))
-    stream = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
-    _lib.check(lib.matgcn_mc_conformity(C.c_void_p(samples.data_ptr()), s, C.c_void_p(y.data_ptr()),
-                                        C.c_void_p(_ptr(label_start)), b, steps, n, od, y_steps, y_feat, int(y_start),
-                                        C.byref(sc), float(null_val), levels, nq, C.c_void_p(out.data_ptr()), stream),
-               "matgcn_mc_conformity")
-    del keep
+    sc, _keep = _metric_scale(v.n, dev, mean, std, group_mean, group_std, clamp_min, truth_min, min_s)
+    out, _ = _out_arg(out, (v.b, v.out, v.n, v.od), torch.float32, dev, "out")
+    _lib.call("matgcn_mc_conformity", *v.args(y_start), C.byref(sc), float(null_val), levels, nq, out.data_ptr(),
+              _stream(dev))
     return out
 
 
@@ -647,10 +606,8 @@ def conformal_quantile(scores: torch.Tensor, rows: int, grouping, coverage: floa
     scores, rows, steps, cols, code, shape = _conformal_store(scores, rows, grouping)
     margin = torch.empty(shape, dtype=torch.float32, device=scores.device)
     count = torch.empty(shape, dtype=torch.int32, device=scores.device)
-    stream = C.c_void_p(torch.cuda.current_stream(scores.device).cuda_stream)
-    _lib.check(_lib.load().matgcn_conformal_quantile(C.c_void_p(scores.data_ptr()), rows, steps, cols, code,
-                                                     float(coverage), C.c_void_p(margin.data_ptr()),
-                                                     C.c_void_p(count.data_ptr()), stream), "matgcn_conformal_quantile")
+    _lib.call("matgcn_conformal_quantile", scores.data_ptr(), rows, steps, cols, code, float(coverage),
+              margin.data_ptr(), count.data_ptr(), _stream(scores.device))
     return margin, count
 
 
@@ -662,16 +619,9 @@ def conformal_coverage(scores: torch.Tensor, rows: int, grouping, margin: torch.
     margin = _check_tensor(margin, "margin")
     if tuple(margin.shape) != shape:
         raise _lib.MatgcnError("margin has shape %s, expected %s" % (tuple(margin.shape), shape))
-    accumulate = counts is not None
-    if counts is None:
-        counts = torch.empty(shape + (2,), dtype=torch.int64, device=scores.device)
-    elif (tuple(counts.shape) != shape + (2,) or counts.dtype != torch.int64 or not counts.is_cuda
-          or not counts.is_contiguous()):
-        raise _lib.MatgcnError("counts must be a contiguous CUDA int64 tensor of shape %s" % (shape + (2,),))
-    stream = C.c_void_p(torch.cuda.current_stream(scores.device).cuda_stream)
-    _lib.check(_lib.load().matgcn_conformal_coverage(C.c_void_p(scores.data_ptr()), rows, steps, cols, code,
-                                                     C.c_void_p(margin.data_ptr()), C.c_void_p(counts.data_ptr()),
-                                                     int(accumulate), stream), "matgcn_conformal_coverage")
+    counts, given = _out_arg(counts, shape + (2,), torch.int64, scores.device, "counts")
+    _lib.call("matgcn_conformal_coverage", scores.data_ptr(), rows, steps, cols, code, margin.data_ptr(),
+              counts.data_ptr(), int(given), _stream(scores.device))
     return counts
 
 
@@ -681,33 +631,22 @@ def _region_groups(regions, n: int, device):
     return regions.groups_on(device)
 
 
-def _group_out(out, shape, device):
-    if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=device)
-    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or out.device != device or not out.is_contiguous():
-        raise _lib.MatgcnError("out must be a contiguous CUDA float32 tensor of shape %s" % (tuple(shape),))
-    return out
-
-
 def group_sums(values: torch.Tensor, regions, mean=None, std=None, group_mean=None, group_std=None,
                clamp_min: float = float("nan"), out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Region totals of ``values`` (..., N, od) -> (..., G, od) (matgcn_group_sums): every member de-scaled by mean / std
     (scalars or one pair per node), then by the per-node group_mean / group_std, set to ``clamp_min`` where below it, and
     added in the order ``regions`` (a regions.RegionMap) lists it - one fp64 chain per total, rounded to float32 once.
     Each row is read once; the same bits every run.  ``out``: the tensor to write (every element is written)."""
-    lib = _lib.load()
     values = _check_tensor(values, "values")
     if values.dim() < 2:
         raise _lib.MatgcnError("values has shape %s, expected (..., N, od)" % (tuple(values.shape),))
     n, od = int(values.shape[-2]), int(values.shape[-1])
     groups = _region_groups(regions, n, values.device)
     rows = values.numel() // (n * od) if n * od else 0
-    sc, keep = _metric_scale(n, values.device, mean, std, group_mean, group_std, clamp_min, float("nan"), -1.0)
-    out = _group_out(out, tuple(values.shape[:-2]) + (regions.num_groups, od), values.device)
-    stream = C.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)
-    _lib.check(lib.matgcn_group_sums(C.c_void_p(values.data_ptr()), rows, n, od, C.byref(sc), C.byref(groups),
-                                     C.c_void_p(out.data_ptr()), stream), "matgcn_group_sums")
-    del keep
+    sc, _keep = _metric_scale(n, values.device, mean, std, group_mean, group_std, clamp_min, float("nan"), -1.0)
+    out, _ = _out_arg(out, tuple(values.shape[:-2]) + (regions.num_groups, od), torch.float32, values.device, "out")
+    _lib.call("matgcn_group_sums", values.data_ptr(), rows, n, od, C.byref(sc), C.byref(groups), out.data_ptr(),
+              _stream(values.device))
     return out
 
 
@@ -717,58 +656,38 @@ def group_label_sums(y: torch.Tensor, regions, out_steps: int, out_dim: int, y_s
     """(B, out_steps, G, out_dim) region totals of the labels of a batch (matgcn_group_label_sums): ``y`` windows
     (B, y_steps, N, F), or with ``label_start`` (B) the resident series (T, N, F); channels y_start .. y_start+out_dim-1;
     arithmetic and order as ``group_sums``.  A NaN label makes the totals of its regions NaN."""
-    lib = _lib.load()
     if y.dim() not in (3, 4):
         raise _lib.MatgcnError("y has shape %s, expected (B, y_steps, N, F) or the series (T, N, F)" % (tuple(y.shape),))
-    n = int(y.shape[-2])
     b = int(y.shape[0]) if label_start is None else int(label_start.shape[0])
-    out_steps, out_dim = int(out_steps), int(out_dim)
-    out = _group_out(out, (b, out_steps, regions.num_groups, out_dim), y.device)
-    y, label_start, y_steps, y_feat = _label_geometry(torch.empty(b, out_steps, n, out_dim, device="meta"), y,
-                                                      label_start)
-    groups = _region_groups(regions, n, y.device)
-    sc, keep = _metric_scale(n, y.device, mean, std, group_mean, group_std, clamp_min, float("nan"), -1.0)
-    stream = C.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)
-    _lib.check(lib.matgcn_group_label_sums(C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(label_start)), b, out_steps, n,
-                                           out_dim, y_steps, y_feat, int(y_start), C.byref(sc), C.byref(groups),
-                                           C.c_void_p(out.data_ptr()), stream), "matgcn_group_label_sums")
-    del keep
+    v = _label_view((b, int(out_steps), int(y.shape[-2]), int(out_dim)), y, label_start)
+    dev = v.y.device
+    out, _ = _out_arg(out, (v.b, v.out, regions.num_groups, v.od), torch.float32, dev, "out")
+    groups = _region_groups(regions, v.n, dev)
+    sc, _keep = _metric_scale(v.n, dev, mean, std, group_mean, group_std, clamp_min, float("nan"), -1.0)
+    _lib.call("matgcn_group_label_sums", *v.args(y_start), C.byref(sc), C.byref(groups), out.data_ptr(), _stream(dev))
     return out
 
 
 # ---- a training objective on region totals (matgcn_region_loss / matgcn_region_loss_grad) ---------------------------------
-def _region_loss_call(pred, y, regions, y_start, desc, label_start=None):
-    """the value call: (pred, y, scratch, result (1 + out,), label_start) - the scratch holds the totals for the gradient"""
-    lib = _lib.load()
-    pred = _check_tensor(pred, "pred")
-    if pred.dim() != 4:
-        raise _lib.MatgcnError("pred has shape %s, expected (B, out, N, od)" % (tuple(pred.shape),))
-    b, out, n, od = pred.shape
-    y, label_start, y_steps, y_feat = _label_geometry(pred, y, label_start)
-    groups = _region_groups(regions, n, pred.device)
+def _region_loss_call(v: _LabelView, regions, y_start, desc):
+    """the value call: (scratch - it holds the totals for the gradient, so per call -, result (1 + out,))"""
+    dev = v.pred.device
+    groups = _region_groups(regions, v.n, dev)
     need = C.c_size_t()
-    _lib.check(lib.matgcn_region_loss_bytes(b, out, regions.num_groups, od, C.byref(need)), "matgcn_region_loss_bytes")
-    scratch = torch.empty((need.value + 7) // 8, dtype=torch.float64, device=pred.device)
-    result = torch.empty(1 + out, dtype=torch.float32, device=pred.device)
-    stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-    _lib.check(lib.matgcn_region_loss(C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(label_start)),
-                                      b, out, n, od, y_steps, y_feat, int(y_start), C.byref(desc), C.byref(groups),
-                                      C.c_void_p(scratch.data_ptr()), scratch.numel() * 8, C.c_void_p(result.data_ptr()),
-                                      stream), "matgcn_region_loss")
-    return pred, y, scratch, result, label_start
+    _lib.call("matgcn_region_loss_bytes", v.b, v.out, regions.num_groups, v.od, C.byref(need))
+    scratch = torch.empty((need.value + 7) // 8, dtype=torch.float64, device=dev)
+    result = torch.empty(1 + v.out, dtype=torch.float32, device=dev)
+    _lib.call("matgcn_region_loss", *v.args(y_start), C.byref(desc), C.byref(groups), scratch.data_ptr(),
+              scratch.numel() * 8, result.data_ptr(), _stream(dev))
+    return scratch, result
 
 
-def _region_loss_grad_call(pred, y, regions, y_start, desc, label_start, scratch, upstream, base, d_pred):
+def _region_loss_grad_call(v: _LabelView, regions, y_start, desc, scratch, upstream, base, d_pred):
     """the gradient call into ``d_pred``; ``base`` None, ``d_pred`` itself or another tensor of its shape"""
-    b, out, n, od = pred.shape
-    y_steps, y_feat = (int(y.shape[1]), int(y.shape[3])) if label_start is None else (int(y.shape[0]), int(y.shape[2]))
-    by_group, by_node = regions.groups_on(pred.device), regions.node_groups_on(pred.device)
-    stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-    _lib.check(_lib.load().matgcn_region_loss_grad(
-        C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(label_start)), b, out, n, od, y_steps,
-        y_feat, int(y_start), C.byref(desc), C.byref(by_group), C.byref(by_node), C.c_void_p(scratch.data_ptr()),
-        scratch.numel() * 8, C.c_void_p(upstream.data_ptr()), C.c_void_p(_ptr(base)), C.c_void_p(d_pred.data_ptr()),
-        stream), "matgcn_region_loss_grad")
+    dev = v.pred.device
+    by_group, by_node = regions.groups_on(dev), regions.node_groups_on(dev)
+    _lib.call("matgcn_region_loss_grad", *v.args(y_start), C.byref(desc), C.byref(by_group), C.byref(by_node),
+              scratch.data_ptr(), scratch.numel() * 8, upstream.data_ptr(), _ptr(base), d_pred.data_ptr(), _stream(dev))
     return d_pred
 
 
@@ -778,7 +697,8 @@ def region_loss_device(pred: torch.Tensor, y: torch.Tensor, regions, y_start: in
     (matgcn_region_loss): totals of the de-scaled prediction and label per region of ``regions`` (a regions.RegionMap),
     then the objective on them - masks act on totals.  Bit for bit train_loss_device(group_sums(pred), group_label_sums(y))
     with an identity affine.  Geometry as train_loss_device."""
-    return _region_loss_call(pred, y, regions, y_start, train_loss_desc(name, mean, std, delta), label_start)[3]
+    return _region_loss_call(_label_view(pred, y, label_start), regions, y_start,
+                             train_loss_desc(name, mean, std, delta))[1]
 
 
 def _weight_arg(v, name):
@@ -791,49 +711,42 @@ def _weight_arg(v, name):
 class _TractRegionLoss(torch.autograd.Function):
     """tract_weight * L(tracts) + region_weight * L(region totals), one gradient tensor: matgcn_loss_grad writes the tract
     half, matgcn_region_loss_grad adds the region half onto it (base = d_pred) - no add kernel, no temporary.  A weight of
-    0 skips its half."""
+    0 skips its half (``regions`` may then be None); a weight of 1 costs no multiplication.  train_loss is the (1, 0)
+    case, region_train_loss the (0, 1) case."""
 
     @staticmethod
     def forward(ctx, pred, y, regions, y_start, desc, label_start, tract_weight, region_weight):
-        p = pred.detach()
-        value, t_scratch, r_scratch = None, None, None
-        if tract_weight > 0.0:
-            p, y_c, t_scratch, result, ls = _loss_call(p, y, y_start, desc, label_start)
-            value = result[0] * tract_weight if tract_weight != 1.0 else result[0].clone()
-        if region_weight > 0.0:
-            p, y_c, r_scratch, result, ls = _region_loss_call(p, y, regions, y_start, desc, label_start)
-            part = result[0] * region_weight if region_weight != 1.0 else result[0].clone()
-            value = part if value is None else value + part
-        if value is None:
+        if not (tract_weight > 0.0 or region_weight > 0.0):
             raise ValueError("tract_region_loss: both weights are 0")
-        ctx.save_for_backward(p, y_c, *[s for s in (t_scratch, r_scratch) if s is not None])
-        ctx.has = (t_scratch is not None, r_scratch is not None)
-        ctx.label_start, ctx.y_start, ctx.desc, ctx.regions = ls, int(y_start), desc, regions
+        v = _label_view(pred.detach(), y, label_start)
+        value, scratches = None, []
+        for weight, call in ((tract_weight, lambda: _loss_call(v, y_start, desc)),
+                             (region_weight, lambda: _region_loss_call(v, regions, y_start, desc))):
+            if weight > 0.0:
+                scratch, result = call()
+                scratches.append(scratch)
+                part = result[0] * weight if weight != 1.0 else result[0].clone()
+                value = part if value is None else value + part
+        ctx.view = v.save(ctx, *scratches)
+        ctx.y_start, ctx.desc, ctx.regions = int(y_start), desc, regions
         ctx.weights = (tract_weight, region_weight)
         return value
 
     @staticmethod
     def backward(ctx, upstream):
-        pred, y, *scr = ctx.saved_tensors
-        t_scratch = scr.pop(0) if ctx.has[0] else None
-        r_scratch = scr.pop(0) if ctx.has[1] else None
-        b, out, n, od = pred.shape
-        ls = ctx.label_start
-        y_steps, y_feat = (int(y.shape[1]), int(y.shape[3])) if ls is None else (int(y.shape[0]), int(y.shape[2]))
+        v, *scratches = ctx.view.saved(ctx)
+        pred, (tw, rw) = v.pred, ctx.weights
         d_pred = torch.empty_like(pred)
-        up = upstream.detach().to(torch.float32).reshape(1).contiguous()
-        tw, rw = ctx.weights
-        if t_scratch is not None:
+        up = _upstream(upstream)
+        if tw > 0.0:
+            t_scratch = scratches.pop(0)
             up_t = up * tw if tw != 1.0 else up
-            stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-            _lib.check(_lib.load().matgcn_loss_grad(
-                C.c_void_p(pred.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(_ptr(ls)), b, out, n, od, y_steps,
-                y_feat, ctx.y_start, C.byref(ctx.desc), C.c_void_p(t_scratch.data_ptr()), t_scratch.numel() * 8,
-                C.c_void_p(up_t.data_ptr()), C.c_void_p(d_pred.data_ptr()), stream), "matgcn_loss_grad")
-        if r_scratch is not None:
+            _lib.call("matgcn_loss_grad", *v.args(ctx.y_start), C.byref(ctx.desc), t_scratch.data_ptr(),
+                      t_scratch.numel() * 8, up_t.data_ptr(), d_pred.data_ptr(), _stream(pred.device))
+        if rw > 0.0:
             up_r = up * rw if rw != 1.0 else up
-            _region_loss_grad_call(pred, y, ctx.regions, ctx.y_start, ctx.desc, ls, r_scratch, up_r,
-                                   d_pred if t_scratch is not None else None, d_pred)
+            _region_loss_grad_call(v, ctx.regions, ctx.y_start, ctx.desc, scratches.pop(0), up_r,
+                                   d_pred if tw > 0.0 else None, d_pred)
         return d_pred, None, None, None, None, None, None, None
 
 
@@ -871,7 +784,6 @@ def _opt_tensor(t, name: str) -> torch.Tensor:
 
 
 _opt_tables: Dict[tuple, tuple] = {}    # the pointers of a tensor set -> its matgcn_opt_tensor array (a loop re-uses one)
-_norm_scratch: Dict[tuple, torch.Tensor] = {}   # (device, bytes) -> the per-chunk partials of matgcn_grad_norm
 
 
 def _opt_table(grads, params=None, exp_avgs=None, exp_avg_sqs=None):
@@ -914,19 +826,12 @@ def _opt_table(grads, params=None, exp_avgs=None, exp_avg_sqs=None):
 def grad_norm(tensors: Sequence[torch.Tensor]) -> torch.Tensor:
     """The 2-norm over all elements of ``tensors`` as a 0-dim float32 device tensor (matgcn_grad_norm): what
     clip_grad_norm_ returns, summed in fp64 in a fixed order - two launches, no host synchronisation."""
-    lib = _lib.load()
     arr, n, dev = _opt_table(list(tensors))
     need = C.c_size_t(0)
-    _lib.check(lib.matgcn_grad_norm_bytes(arr, n, C.byref(need)), "matgcn_grad_norm_bytes")
-    scratch = _norm_scratch.get((dev, need.value))
-    if scratch is None:
-        if len(_norm_scratch) >= 16:
-            _norm_scratch.clear()
-        scratch = _norm_scratch[(dev, need.value)] = torch.empty(max(1, need.value // 8), dtype=torch.float64, device=dev)
+    _lib.call("matgcn_grad_norm_bytes", arr, n, C.byref(need))
+    scratch = _scratch(_norm_scratch, (need.value,), need.value, dev)     # the per-chunk partials
     out = torch.empty((), dtype=torch.float32, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(lib.matgcn_grad_norm(arr, n, C.c_void_p(scratch.data_ptr()), C.c_size_t(need.value),
-                                    C.c_void_p(out.data_ptr()), stream), "matgcn_grad_norm")
+    _lib.call("matgcn_grad_norm", arr, n, scratch.data_ptr(), need.value, out.data_ptr(), _stream(dev))
     return out
 
 
@@ -936,7 +841,6 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, *, lr, betas, eps, weight_de
     1-based count after this update, common to all tensors.  With ``max_norm`` the gradients are scaled, as they are read,
     by min(1, max_norm / (total_norm + 1e-6)) - ``total_norm`` is grad_norm() over every gradient of the model, not only
     over the ones of this call; the ``grads`` themselves are never written."""
-    lib = _lib.load()
     arr, n, dev = _opt_table(list(grads), list(params), list(exp_avgs), list(exp_avg_sqs))
     clip = max_norm is not None and float(max_norm) > 0
     if max_norm is not None and not clip and not float(max_norm) <= 0:
@@ -949,9 +853,38 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, *, lr, betas, eps, weight_de
             raise ValueError("total_norm must be one float on %s" % (dev,))
     hp = _lib.Adam(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
                    float(max_norm) if clip else 0.0, int(step))
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(lib.matgcn_adam_step(arr, n, C.byref(hp), C.c_void_p(total_norm.data_ptr() if clip else None), stream),
-               "matgcn_adam_step")
+    _lib.call("matgcn_adam_step", arr, n, C.byref(hp), total_norm.data_ptr() if clip else None, _stream(dev))
+
+
+def _walk_params(s: PathSpec, p: "_lib.Params", ptr_of) -> None:
+    """Every tensor field of a matgcn_params / matgcn_grads ``p`` of configuration ``s``: field = ptr_of(name in the
+    reference's state dict, shape); None leaves the field NULL.  static_supports is no state-dict tensor and not set here."""
+    n, d, h, kt = s.nodes, s.embed_dim, s.hidden, s.k_total
+    p.node_emb = ptr_of("node_emb", (n, d))
+    if s.adpadj == "unidirection":      # the only adaptive adjacency that reads the two factors
+        p.node_vec1, p.node_vec2 = ptr_of("node_vec1", (n, s.adj_rank)), ptr_of("node_vec2", (s.adj_rank, n))
+    else:
+        p.node_vec1 = p.node_vec2 = None
+    p.weights_gru = ptr_of("encoder.weights_gru", (s.layers, s.in_steps))
+    p.weight_tsg = ptr_of("weight_tsg", (s.n_ts,))
+    for i in range(len(s.head_begin)):
+        p.weight_ts[i] = ptr_of("weight_ts.%d" % i, (1, 24, n, s.out_dim))
+    for l in range(s.layers):
+        cin = (s.feat_in if l == 0 else h) + h
+        if not s.gcn_off:
+            for nm, o, dst in (("gate", 2 * h, p.gate), ("update", h, p.update)):
+                pre = "encoder.agru_cells.%d.%s." % (l, nm)
+                dst[l].weights_g = ptr_of(pre + "weights_g", (kt, 1, 1))
+                dst[l].weights_pool = ptr_of(pre + "weights_pool", (d, kt, cin, o))
+                dst[l].bias_pool = ptr_of(pre + "bias_pool", (d, o))
+        # gcn_off: encoder.agru_cells hold the dense GRU cells; they travel in the res_* fields
+        cells = "encoder.agru_cells" if s.gcn_off else "encoder.res_cells"
+        for nm, o, dst in (("gate", 2 * h, p.res_gate), ("update", h, p.res_update)):
+            pre = "%s.%d.%s." % (cells, l, nm)
+            dst[l].weight = ptr_of(pre + "weight", (o, cin))
+            dst[l].bias = ptr_of(pre + "bias", (o,))
+    p.end_conv_weight = ptr_of("end_conv.weight", (s.out_window * s.out_dim, 1 if s.fnn_off else s.in_steps, 1, h))
+    p.end_conv_bias = ptr_of("end_conv.bias", (s.out_window * s.out_dim,))
 
 
 class HotPath:
@@ -963,11 +896,8 @@ class HotPath:
         if self.device.type != "cuda":
             raise _lib.MatgcnError("HotPath needs a GPU device, got %s" % self.device)
         self.dims = spec.dims(batch)
-        nbytes = C.c_size_t()
-        _lib.check(self.lib.matgcn_prepared_bytes(C.byref(self.dims), C.byref(nbytes)), "matgcn_prepared_bytes")
-        self.prepared = torch.empty(nbytes.value // 4, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.matgcn_workspace_bytes(C.byref(self.dims), C.byref(nbytes)), "matgcn_workspace_bytes")
-        self.workspace = torch.empty(nbytes.value // 4, dtype=torch.float32, device=self.device)
+        self.prepared = self._buffer(self._bytes("matgcn_prepared_bytes"))
+        self.workspace = self._buffer(self._bytes("matgcn_workspace_bytes"))
         self.params = _lib.Params()
         self._static = None
         self._keep: List[torch.Tensor] = []
@@ -992,13 +922,43 @@ class HotPath:
         self.train_bf16x3: Optional[bool] = None
 
     # ---- plumbing ------------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _stream(self) -> int:
+        return _stream(self.device)
+
+    def _bytes(self, name: str) -> int:
+        """what matgcn_prepared_bytes / matgcn_workspace_bytes / matgcn_train_bytes report under the current settings"""
+        nbytes = C.c_size_t()
+        _lib.call(name, C.byref(self.dims), C.byref(nbytes))
+        return nbytes.value
+
+    def _buffer(self, nbytes: int) -> torch.Tensor:
+        return torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+
+    def _out(self) -> torch.Tensor:
+        """a fresh forecast (B, out_window, N, out_dim)"""
+        s = self.spec
+        return torch.empty(self.batch, s.out_window, s.nodes, s.out_dim, dtype=torch.float32, device=self.device)
 
     def _ws(self):
         # every call that uses the workspace invalidates what an earlier forward_train left there for its backward
         self.train_generation += 1
-        return C.c_void_p(self.workspace.data_ptr()), C.c_size_t(self.workspace.numel() * 4)
+        return self.workspace.data_ptr(), self.workspace.numel() * 4
+
+    def _status(self, name: str, tail, ws, wsb, train: bool = False, prepared: bool = True) -> int:
+        """The status of entry point ``name`` on (dims, params, prepared - where it takes one -, *tail, the workspace
+        ``ws`` of ``wsb`` bytes, the train buffer and its bytes - train -, the current stream)."""
+        head = (self.prepared.data_ptr(),) if prepared else ()
+        tr = (self._train.data_ptr(), self._train.numel() * 4) if train else ()
+        return getattr(self.lib, name)(C.byref(self.dims), C.byref(self.params), *head, *tail, ws, wsb, *tr,
+                                       _stream(self.device))
+
+    def _call(self, name: str, *tail, regrow: bool = False, train: bool = False, prepared: bool = True) -> None:
+        """``_status`` checked; regrow: through _with_workspace, which re-sizes a buffer that the current library mode
+        has outgrown and repeats the call (the forwards; the single-step entry points take the workspace as it is)."""
+        if regrow:
+            self._with_workspace(lambda ws, wsb: self._status(name, tail, ws, wsb, train, prepared), name, train=train)
+        else:
+            _lib.check(self._status(name, tail, *self._ws(), train, prepared), name)
 
     def _with_workspace(self, call, what: str, train: bool = False) -> None:
         """Run ``call(ws_ptr, ws_bytes)``; a workspace that is too small for the CURRENT library mode - precision mode 2
@@ -1009,15 +969,13 @@ class HotPath:
         ws, wsb = self._ws()
         status = call(ws, wsb)
         if status == -4:      # MATGCN_ERR_SMALL_BUFFER
-            nbytes = C.c_size_t()
             grown = False
-            _lib.check(self.lib.matgcn_workspace_bytes(C.byref(self.dims), C.byref(nbytes)), "matgcn_workspace_bytes")
-            if nbytes.value > self.workspace.numel() * 4:
-                self.workspace = torch.empty(nbytes.value // 4, dtype=torch.float32, device=self.device)
+            nbytes = self._bytes("matgcn_workspace_bytes")
+            if nbytes > self.workspace.numel() * 4:
+                self.workspace = self._buffer(nbytes)
                 grown = True
             if train and self._train is not None:
-                _lib.check(self.lib.matgcn_train_bytes(C.byref(self.dims), C.byref(nbytes)), "matgcn_train_bytes")
-                if nbytes.value > self._train.numel() * 4:
+                if self._bytes("matgcn_train_bytes") > self._train.numel() * 4:
                     self._train = None
                     self._train_buffer()
                     grown = True
@@ -1062,57 +1020,25 @@ class HotPath:
         s, p = self.spec, self.params
         keep: List[torch.Tensor] = []
 
-        def dev(name, shape=None):
+        def dev(name, shape):
             t = _check_tensor(state[name], name, shape)
             keep.append(t)
             return t.data_ptr()
 
-        n, d, h = s.nodes, s.embed_dim, s.hidden
-        p.node_emb = dev("node_emb", (n, d))
-        if s.adpadj == "unidirection":
-            p.node_vec1 = dev("node_vec1", (n, s.adj_rank))
-            p.node_vec2 = dev("node_vec2", (s.adj_rank, n))
-        else:
-            p.node_vec1 = p.node_vec2 = None
+        _walk_params(s, p, dev)
         if s.n_static > 0:
-            st = _check_tensor(static_supports, "static_supports", (s.n_static, n, n))
+            st = _check_tensor(static_supports, "static_supports", (s.n_static, s.nodes, s.nodes))
             keep.append(st)
             self._static = st
             p.static_supports = st.data_ptr()
         else:
             p.static_supports = None
-        p.weight_tsg = dev("weight_tsg", (s.n_ts,))
-        for i in range(len(s.head_begin)):
-            p.weight_ts[i] = dev("weight_ts.%d" % i, (1, 24, n, s.out_dim))
-        p.weights_gru = dev("encoder.weights_gru", (s.layers, s.in_steps))
-        kt = s.k_total
-        for l in range(s.layers):
-            cin = (s.feat_in if l == 0 else h) + h
-            if not s.gcn_off:
-                for nm, o, dst in (("gate", 2 * h, p.gate), ("update", h, p.update)):
-                    pre = "encoder.agru_cells.%d.%s." % (l, nm)
-                    dst[l].weights_g = dev(pre + "weights_g", (kt, 1, 1))
-                    dst[l].weights_pool = dev(pre + "weights_pool", (d, kt, cin, o))
-                    dst[l].bias_pool = dev(pre + "bias_pool", (d, o))
-            # gcn_off: encoder.agru_cells hold the dense GRU cells; they travel in the res_* fields
-            cells = "encoder.agru_cells" if s.gcn_off else "encoder.res_cells"
-            for nm, o, dst in (("gate", 2 * h, p.res_gate), ("update", h, p.res_update)):
-                pre = "%s.%d.%s." % (cells, l, nm)
-                dst[l].weight = dev(pre + "weight", (o, cin))
-                dst[l].bias = dev(pre + "bias", (o,))
-        p.end_conv_weight = dev("end_conv.weight",
-                                (s.out_window * s.out_dim, 1 if s.fnn_off else s.in_steps, 1, h))
-        p.end_conv_bias = dev("end_conv.bias", (s.out_window * s.out_dim,))
         self._keep = keep
         self._prepared_ok = False
 
     # ---- entry points --------------------------------------------------------------------------
     def prepare(self):
-        ws, wsb = self._ws()
-        _lib.check(self.lib.matgcn_prepare(C.byref(self.dims), C.byref(self.params),
-                                           C.c_void_p(self.prepared.data_ptr()),
-                                           C.c_size_t(self.prepared.numel() * 4), ws, wsb, self._stream()),
-                   "matgcn_prepare")
+        self._call("matgcn_prepare", self.prepared.numel() * 4)
         self._prepared_ok = True
 
     def _need_prepared(self):
@@ -1122,7 +1048,7 @@ class HotPath:
     def prepare_join(self):
         """the current stream waits for whatever a lazy matgcn_prepare still writes (include/matgcn.h): needed only by
         code that reads ``self.prepared`` itself instead of through the library"""
-        _lib.check(self.lib.matgcn_prepare_join(self._stream()), "matgcn_prepare_join")
+        _lib.call("matgcn_prepare_join", self._stream())
 
     def __del__(self):
         # `prepared` goes back to torch's allocator when this object dies: nothing of the library may still write it.
@@ -1134,7 +1060,7 @@ class HotPath:
             if self._prepared_ok and torch.cuda.is_available():
                 with torch.cuda.device(self.device):
                     cur = torch.cuda.current_stream(self.device)
-                    self.lib.matgcn_prepare_join(C.c_void_p(cur.cuda_stream))
+                    self.lib.matgcn_prepare_join(cur.cuda_stream)
                     self.prepared.record_stream(cur)
         except Exception as exc:   # interpreter shutdown: torch may already be gone - say so instead of hiding it
             try:
@@ -1144,9 +1070,10 @@ class HotPath:
                 pass
 
     def _source(self, x):
-        """The batch of a training step: a windows tensor X (B, x_steps, N, F), or a (series, label_start, rel_steps)
-        triple - the raw series (T, N, F) resident on the device, B int32 label starts, the x_steps row offsets.
-        Returns (X pointer or None, matgcn_series or None, objects to keep alive)."""
+        """The batch of a call: a windows tensor X (B, x_steps, N, F), or a (series, label_start, rel_steps) triple - the
+        raw series (T, N, F) resident on the device, B int32 label starts, the x_steps row offsets.
+        Returns (X pointer or None, reference to a matgcn_series or None, objects to keep alive: X, or the contiguous
+        series, label_start, the C array of rel_steps and the matgcn_series)."""
         s = self.spec
         if isinstance(x, torch.Tensor):
             x = _check_tensor(x, "X", (self.batch, s.x_steps, s.nodes, s.x_feat))
@@ -1163,7 +1090,7 @@ class HotPath:
         label_start = label_start.contiguous()
         rel_c = (C.c_int32 * len(rel))(*rel)
         src = _lib.Series(series.data_ptr(), int(series.shape[0]), label_start.data_ptr(), rel_c)
-        return None, src, (series, label_start, rel_c)
+        return None, C.byref(src), (series, label_start, rel_c, src)
 
     def _h0(self, h0):
         """initial encoder state (L, B, N, H) or None = zeros (MultiATGCN.py:405-409)"""
@@ -1177,11 +1104,9 @@ class HotPath:
         x = _check_tensor(x, "X", (self.batch, s.x_steps, s.nodes, s.x_feat))
         h0 = self._h0(h0)
         self._need_prepared()
-        out = torch.empty(self.batch, s.out_window, s.nodes, s.out_dim, dtype=torch.float32, device=self.device)
+        out = self._out()
         with self._mode(self.lib.matgcn_set_mix_precision):
-            self._with_workspace(lambda ws, wsb: self.lib.matgcn_forward(
-                C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()), C.c_void_p(x.data_ptr()),
-                C.c_void_p(_ptr(h0)), C.c_void_p(out.data_ptr()), ws, wsb, self._stream()), "matgcn_forward")
+            self._call("matgcn_forward", x.data_ptr(), _ptr(h0), out.data_ptr(), regrow=True)
         return out
 
     # ---- training step ---------------------------------------------------
@@ -1190,17 +1115,17 @@ class HotPath:
         counts the deterministic backward's partial slabs and mode 2's bf16 copies only while they are set): a buffer
         sized before a setting was switched on is replaced.  Called in front of forward_train, never between it and
         its backward - a new buffer has none of the saved activations."""
-        nbytes = C.c_size_t()
-        _lib.check(self.lib.matgcn_train_bytes(C.byref(self.dims), C.byref(nbytes)), "matgcn_train_bytes")
-        if self._train is None or nbytes.value > self._train.numel() * 4:
-            self._train = torch.empty(nbytes.value // 4, dtype=torch.float32, device=self.device)
+        nbytes = self._bytes("matgcn_train_bytes")
+        if self._train is None or nbytes > self._train.numel() * 4:
+            self._train = self._buffer(nbytes)
         return self._train
 
-    def _mask(self, drop_mask):
-        if drop_mask is None:
-            return None
+    def _mask_shape(self):
         s = self.spec
-        return _check_tensor(drop_mask, "drop_mask", (self.batch, 1 if s.fnn_off else s.in_steps, s.nodes, s.hidden))
+        return (self.batch, 1 if s.fnn_off else s.in_steps, s.nodes, s.hidden)
+
+    def _mask(self, drop_mask):
+        return None if drop_mask is None else _check_tensor(drop_mask, "drop_mask", self._mask_shape())
 
     @staticmethod
     def _dropout(dropout, drop_mask=None) -> Optional[_lib.Dropout]:
@@ -1215,13 +1140,15 @@ class HotPath:
     def dropout_mask(self, seed: int, offset: int, p: float) -> torch.Tensor:
         """The (B, headT, N, 64) mask the descriptor (seed, offset, p) stands for, written out by matgcn_dropout_mask
         (tests, and callers that want to look at it: the training and MC entry points never materialise it)."""
-        s = self.spec
-        mask = torch.empty(self.batch, 1 if s.fnn_off else s.in_steps, s.nodes, s.hidden, dtype=torch.float32,
-                           device=self.device)
+        mask = torch.empty(self._mask_shape(), dtype=torch.float32, device=self.device)
         d = self._dropout((seed, offset, p))
-        _lib.check(self.lib.matgcn_dropout_mask(C.byref(self.dims), C.byref(d), C.c_void_p(mask.data_ptr()),
-                                                self._stream()), "matgcn_dropout_mask")
+        _lib.call("matgcn_dropout_mask", C.byref(self.dims), C.byref(d), mask.data_ptr(), self._stream())
         return mask
+
+    @staticmethod
+    def _drop_variant(name: str, seeded, drop_mask):
+        """the two training entry points differ in one argument: the mask tensor, or the descriptor that stands for it"""
+        return (name, _ptr(drop_mask)) if seeded is None else (name + "_seeded", C.byref(seeded))
 
     def forward_train(self, x, drop_mask: Optional[torch.Tensor] = None,
                       h0: Optional[torch.Tensor] = None, dropout=None) -> torch.Tensor:
@@ -1231,23 +1158,16 @@ class HotPath:
         dropout: (seed, offset, p) instead - the same dropout drawn on the device by matgcn_forward_train_seeded, no mask
         tensor (the matching backward must get the same triple);
         h0: initial encoder state (L, B, N, H) or None."""
-        s = self.spec
         xp, src, _keep = self._source(x)
         drop_mask = self._mask(drop_mask)
         seeded = self._dropout(dropout, drop_mask)
         h0 = self._h0(h0)
         self._need_prepared()
-        out = torch.empty(self.batch, s.out_window, s.nodes, s.out_dim, dtype=torch.float32, device=self.device)
+        out = self._out()
         with self._mode(self.lib.matgcn_set_train_precision), self._x3(), self._det():
             self._train_buffer()
-            fn, what, drop = ((self.lib.matgcn_forward_train, "matgcn_forward_train", C.c_void_p(_ptr(drop_mask)))
-                              if seeded is None else
-                              (self.lib.matgcn_forward_train_seeded, "matgcn_forward_train_seeded", C.byref(seeded)))
-            self._with_workspace(lambda ws, wsb: fn(
-                C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
-                C.byref(src) if src is not None else None, C.c_void_p(_ptr(h0)), drop,
-                C.c_void_p(out.data_ptr()), ws, wsb, C.c_void_p(self._train.data_ptr()),
-                C.c_size_t(self._train.numel() * 4), self._stream()), what, train=True)
+            name, drop = self._drop_variant("matgcn_forward_train", seeded, drop_mask)
+            self._call(name, xp, src, _ptr(h0), drop, out.data_ptr(), regrow=True, train=True)
         return out
 
     def forward_mc(self, x, h0: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0, p: float = 0.1,
@@ -1256,23 +1176,17 @@ class HotPath:
         s draws with (seed, offset + s, p).  x: the windows tensor X or a (series, label_start, rel_steps) triple.
         Returns (mean, std) of shape (B, out, N, od) - the population standard deviation over the samples - and, with
         keep_samples, the (samples, B, out, N, od) forecasts as a third entry."""
-        s = self.spec
         xp, src, _keep = self._source(x)
         h0 = self._h0(h0)
         d = self._dropout((seed, offset, p))
         self._need_prepared()
-        shape = (self.batch, s.out_window, s.nodes, s.out_dim)
-        mean = torch.empty(shape, dtype=torch.float32, device=self.device)
-        std = torch.empty(shape, dtype=torch.float32, device=self.device)
+        mean, std = self._out(), self._out()
         kept = None
         if keep_samples and 1 <= int(samples) <= _lib.MAX_MC_SAMPLES:
-            kept = torch.empty((int(samples),) + shape, dtype=torch.float32, device=self.device)
+            kept = torch.empty((int(samples),) + tuple(mean.shape), dtype=torch.float32, device=self.device)
         with self._mode(self.lib.matgcn_set_mix_precision):
-            self._with_workspace(lambda ws, wsb: self.lib.matgcn_forward_mc(
-                C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
-                C.byref(src) if src is not None else None, C.c_void_p(_ptr(h0)), C.byref(d), int(samples),
-                C.c_void_p(mean.data_ptr()), C.c_void_p(std.data_ptr()), C.c_void_p(_ptr(kept)), ws, wsb,
-                self._stream()), "matgcn_forward_mc")
+            self._call("matgcn_forward_mc", xp, src, _ptr(h0), C.byref(d), int(samples), mean.data_ptr(), std.data_ptr(),
+                       _ptr(kept), regrow=True)
         return (mean, std, kept) if keep_samples else (mean, std)
 
     D_H0 = "__d_h0__"   # key of the initial-state gradient in backward()'s result
@@ -1311,35 +1225,20 @@ class HotPath:
         grads: Dict[str, torch.Tensor] = {}
         g = _lib.Params()
         views = self._grad_views(state)
+        # fields left NULL: under gcn_off what only the graph cells read, otherwise a node_emb that is a frozen Parameter
+        if s.gcn_off:
+            skip = ("node_emb", "node_vec1", "node_vec2", "encoder.weights_gru")
+        else:
+            emb = state["node_emb"]
+            skip = () if emb.requires_grad or not isinstance(emb, torch.nn.Parameter) else ("node_emb",)
 
-        def new(name):
+        def new(name, shape):
+            if name in skip:
+                return None
             grads[name] = views[name]
             return views[name].data_ptr()
 
-        if not s.gcn_off:
-            if state["node_emb"].requires_grad or not isinstance(state["node_emb"], torch.nn.Parameter):
-                g.node_emb = new("node_emb")
-            if s.adpadj == "unidirection":
-                g.node_vec1, g.node_vec2 = new("node_vec1"), new("node_vec2")
-            g.weights_gru = new("encoder.weights_gru")
-        g.weight_tsg = new("weight_tsg")
-        for i in range(len(s.head_begin)):
-            g.weight_ts[i] = new("weight_ts.%d" % i)
-        for l in range(s.layers):
-            if not s.gcn_off:
-                for nm, dst in (("gate", g.gate), ("update", g.update)):
-                    pre = "encoder.agru_cells.%d.%s." % (l, nm)
-                    dst[l].weights_g = new(pre + "weights_g")
-                    dst[l].weights_pool = new(pre + "weights_pool")
-                    dst[l].bias_pool = new(pre + "bias_pool")
-            # gcn_off: encoder.agru_cells hold the dense GRU cells; they travel in the res_* fields (see bind)
-            cells = "encoder.agru_cells" if s.gcn_off else "encoder.res_cells"
-            for nm, dst in (("gate", g.res_gate), ("update", g.res_update)):
-                pre = "%s.%d.%s." % (cells, l, nm)
-                dst[l].weight = new(pre + "weight")
-                dst[l].bias = new(pre + "bias")
-        g.end_conv_weight = new("end_conv.weight")
-        g.end_conv_bias = new("end_conv.bias")
+        _walk_params(s, g, new)
         if not s.scale_by_g and not s.gcn_off:   # the stack is not scaled: weights_g does not reach the output
             for l in range(s.layers):
                 for nm in ("gate", "update"):
@@ -1349,20 +1248,15 @@ class HotPath:
                 continue
             if name not in grads and (t.requires_grad or not isinstance(t, torch.nn.Parameter)):   # adaptive adjacency)
                 grads[name] = views[name].zero_()
-        tr = self._train
-        if tr is None:
+        if self._train is None:
             raise _lib.MatgcnError("backward() without a forward_train() before it")
-        ws, wsb = self._ws()   # (the workspace and the train buffer as forward_train left them: no re-sizing here - a
-        # deterministic backward behind a forward_train that ran without the setting reports MATGCN_ERR_SMALL_BUFFER)
-        # the two entry points differ in one argument: the mask tensor, or the descriptor that stands for it
-        fn, what, drop = ((self.lib.matgcn_backward, "matgcn_backward", C.c_void_p(_ptr(drop_mask))) if seeded is None else
-                          (self.lib.matgcn_backward_seeded, "matgcn_backward_seeded", C.byref(seeded)))
+        # the workspace and the train buffer as forward_train left them: no re-sizing here - a deterministic backward
+        # behind a forward_train that ran without the setting reports MATGCN_ERR_SMALL_BUFFER
+        name, drop = self._drop_variant("matgcn_backward", seeded, drop_mask)
         with self._x3(), self._det():
-            status = fn(C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()), C.c_void_p(xp),
-                        C.byref(src) if src is not None else None, C.c_void_p(_ptr(h0)), drop,
-                        C.c_void_p(d_out.data_ptr()), C.byref(g), C.c_void_p(_ptr(d_h0)), ws, wsb,
-                        C.c_void_p(tr.data_ptr()), C.c_size_t(tr.numel() * 4), self._stream())
-        _lib.check(status, what)
+            status = self._status(name, (xp, src, _ptr(h0), drop, d_out.data_ptr(), C.byref(g), _ptr(d_h0)), *self._ws(),
+                                  train=True)
+        _lib.check(status, name)
         if d_h0 is not None:
             grads[self.D_H0] = d_h0
         return grads
@@ -1371,95 +1265,72 @@ class HotPath:
                        h0: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Forward fed from the device-resident series (T, N, F): sample b's window rows are gathered by the
         head-fusion prologue from series[label_start[b] + rel_steps[s]] (multistgraph_amd/windows.py)."""
-        s = self.spec
-        if series.dim() != 3 or tuple(series.shape[1:]) != (s.nodes, s.x_feat):
-            raise _lib.MatgcnError("series has shape %s, expected (T, %d, %d)" % (tuple(series.shape), s.nodes, s.x_feat))
-        series = _check_tensor(series, "series")
-        if not label_start.is_cuda or label_start.dtype != torch.int32 or tuple(label_start.shape) != (self.batch,):
-            raise _lib.MatgcnError("label_start must be a CUDA int32 tensor of shape (%d,)" % self.batch)
-        rel = [int(v) for v in rel_steps]
-        if len(rel) != s.x_steps:
-            raise _lib.MatgcnError("rel_steps has %d entries, x_steps is %d" % (len(rel), s.x_steps))
+        _, _, (series, label_start, rel_c, _src) = self._source((series, label_start, rel_steps))
         h0 = self._h0(h0)
         self._need_prepared()
-        out = torch.empty(self.batch, s.out_window, s.nodes, s.out_dim, dtype=torch.float32, device=self.device)
-        rel_c = (C.c_int32 * len(rel))(*rel)
+        out = self._out()
         with self._mode(self.lib.matgcn_set_mix_precision):
-            self._with_workspace(lambda ws, wsb: self.lib.matgcn_forward_series(
-                C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()),
-                C.c_void_p(series.data_ptr()), C.c_int64(series.shape[0]), C.c_void_p(label_start.contiguous().data_ptr()),
-                rel_c, C.c_void_p(_ptr(h0)), C.c_void_p(out.data_ptr()), ws, wsb, self._stream()), "matgcn_forward_series")
+            self._call("matgcn_forward_series", series.data_ptr(), int(series.shape[0]), label_start.data_ptr(), rel_c,
+                       _ptr(h0), out.data_ptr(), regrow=True)
         return out
 
     def fuse_heads(self, x: torch.Tensor) -> torch.Tensor:
         s = self.spec
         x = _check_tensor(x, "X", (self.batch, s.x_steps, s.nodes, s.x_feat))
         out = torch.empty(self.batch, s.in_steps, s.nodes, s.feat_in, dtype=torch.float32, device=self.device)
-        ws, wsb = self._ws()
-        _lib.check(self.lib.matgcn_fuse_heads(C.byref(self.dims), C.byref(self.params), C.c_void_p(x.data_ptr()),
-                                              C.c_void_p(out.data_ptr()), ws, wsb, self._stream()),
-                   "matgcn_fuse_heads")
+        self._call("matgcn_fuse_heads", x.data_ptr(), out.data_ptr(), prepared=False)
         return out
 
-    def _single(self, fn, name, layer, x, h, out_cols):
+    def _single(self, name, layer, x, h, out_cols):
         s = self.spec
         cl = s.feat_in if layer == 0 else s.hidden
         x = _check_tensor(x, "x", (self.batch, s.nodes, cl))
         h = _check_tensor(h, "h", (self.batch, s.nodes, s.hidden))
         self._need_prepared()
         out = torch.empty(self.batch, s.nodes, out_cols, dtype=torch.float32, device=self.device)
-        ws, wsb = self._ws()
-        _lib.check(fn(C.byref(self.dims), C.byref(self.params), C.c_void_p(self.prepared.data_ptr()), layer,
-                      C.c_void_p(x.data_ptr()), C.c_void_p(h.data_ptr()), C.c_void_p(out.data_ptr()), ws, wsb,
-                      self._stream()), name)
+        self._call(name, layer, x.data_ptr(), h.data_ptr(), out.data_ptr())
         return out
 
     def agcn_gate(self, layer, x, h):
-        return self._single(self.lib.matgcn_agcn_gate_fwd, "matgcn_agcn_gate_fwd", layer, x, h, 2 * self.spec.hidden)
+        return self._single("matgcn_agcn_gate_fwd", layer, x, h, 2 * self.spec.hidden)
 
     def atgru_cell(self, layer, x, h):
-        return self._single(self.lib.matgcn_atgru_cell_fwd, "matgcn_atgru_cell_fwd", layer, x, h, self.spec.hidden)
+        return self._single("matgcn_atgru_cell_fwd", layer, x, h, self.spec.hidden)
 
     def res_cell(self, layer, x, h):
-        return self._single(self.lib.matgcn_res_cell_fwd, "matgcn_res_cell_fwd", layer, x, h, self.spec.hidden)
+        return self._single("matgcn_res_cell_fwd", layer, x, h, self.spec.hidden)
 
     def encoder(self, x0: torch.Tensor, h0: Optional[torch.Tensor] = None):
         s = self.spec
         x0 = _check_tensor(x0, "x0", (self.batch, s.in_steps, s.nodes, s.feat_in))
-        if h0 is not None:
-            h0 = _check_tensor(h0, "h0", (s.layers, self.batch, s.nodes, s.hidden))
+        h0 = self._h0(h0)
         self._need_prepared()
         seq = torch.empty(self.batch, s.in_steps, s.nodes, s.hidden, dtype=torch.float32, device=self.device)
         fin = torch.empty(s.layers, self.batch, s.nodes, s.hidden, dtype=torch.float32, device=self.device)
-        ws, wsb = self._ws()
-        _lib.check(self.lib.matgcn_encoder_fwd(C.byref(self.dims), C.byref(self.params),
-                                               C.c_void_p(self.prepared.data_ptr()), C.c_void_p(x0.data_ptr()),
-                                               C.c_void_p(_ptr(h0)), C.c_void_p(seq.data_ptr()),
-                                               C.c_void_p(fin.data_ptr()), ws, wsb, self._stream()),
-                   "matgcn_encoder_fwd")
+        self._call("matgcn_encoder_fwd", x0.data_ptr(), _ptr(h0), seq.data_ptr(), fin.data_ptr())
         return seq, fin
 
     def output_head(self, seq: torch.Tensor) -> torch.Tensor:
         s = self.spec
         seq = _check_tensor(seq, "seq", (self.batch, s.in_steps, s.nodes, s.hidden))
         self._need_prepared()
-        out = torch.empty(self.batch, s.out_window, s.nodes, s.out_dim, dtype=torch.float32, device=self.device)
-        ws, wsb = self._ws()
-        _lib.check(self.lib.matgcn_output_head(C.byref(self.dims), C.byref(self.params),
-                                               C.c_void_p(self.prepared.data_ptr()), C.c_void_p(seq.data_ptr()),
-                                               C.c_void_p(out.data_ptr()), ws, wsb, self._stream()),
-                   "matgcn_output_head")
+        out = self._out()
+        self._call("matgcn_output_head", seq.data_ptr(), out.data_ptr())
         return out
+
+    def _layout(self, name: str, *which):
+        """the four integers of matgcn_supports_layout / matgcn_weights_layout, behind a joined prepare"""
+        self._need_prepared()
+        self.prepare_join()
+        lay = (C.c_int64 * 4)()
+        _lib.call(name, C.byref(self.dims), *which, C.byref(lay))
+        return (int(v) for v in lay)
 
     def supports(self) -> torch.Tensor:
         """(Ks, N, N): the DENSE non-identity slots of the support stack as matgcn_prepare built them, in stack order
         (tests).  Diagonal supports never reach the stack - they are folded into the identity slot of the node-adaptive
         weights (read those back with node_weights) -, and cheb_order = 1 holds the SUM of its dense supports."""
-        self._need_prepared()
-        self.prepare_join()
-        lay = (C.c_int64 * 4)()
-        _lib.check(self.lib.matgcn_supports_layout(C.byref(self.dims), C.byref(lay)), "matgcn_supports_layout")
-        off, ld, npad, ks = (int(v) for v in lay)
+        off, ld, npad, ks = self._layout("matgcn_supports_layout")
         n = self.spec.nodes
         if ks == 0:
             return torch.empty(0, n, n, dtype=torch.float32, device=self.device)
@@ -1470,12 +1341,7 @@ class HotPath:
         """(N, 1 + Ks, 64, O): the recurrent (hidden-channel) rows of the node-adaptive weights of
         agru_cells[layer].gate (part 0, O = 128) / .update (part 1, O = 64), decoded from the MFMA-fragment-ordered
         stream matgcn_prepare wrote into `prepared` (tests: softmax(weights_g) and the diagonal-support fold included)."""
-        self._need_prepared()
-        self.prepare_join()
-        lay = (C.c_int64 * 4)()
-        _lib.check(self.lib.matgcn_weights_layout(C.byref(self.dims), layer, part, C.byref(lay)),
-                   "matgcn_weights_layout")
-        off, stride, groups, ot = (int(v) for v in lay)
+        off, stride, groups, ot = self._layout("matgcn_weights_layout", layer, part)
         n, o_dim = self.spec.nodes, ot * 16
         idx = torch.arange(n, device=self.device)[:, None] * stride + off + \
             torch.arange(groups * ot * 256, device=self.device)[None, :]

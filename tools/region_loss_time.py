@@ -89,12 +89,13 @@ def tract_route(objective, key):
 
 def grad_kernel_route(objective, key):
     desc = ops.train_loss_desc(objective, MEAN, STD)
-    p, yc, scratch, _, _ = ops._region_loss_call(pred, y, MAPS[key], 0, desc)
+    view = ops._label_view(pred, y, None)
+    scratch, _ = ops._region_loss_call(view, MAPS[key], 0, desc)
     up = torch.ones(1, device=dev)
-    d_pred = torch.empty_like(p)
+    d_pred = torch.empty_like(view.pred)
 
     def step():
-        ops._region_loss_grad_call(p, yc, MAPS[key], 0, desc, None, scratch, up, None, d_pred)
+        ops._region_loss_grad_call(view, MAPS[key], 0, desc, scratch, up, None, d_pred)
         return None, d_pred
     return step
 
