@@ -56,6 +56,10 @@
  * value changed, and no existing entry point launches anything else than it did.
  * Still ABI 12: new names only - the region-level training loss adds the functions matgcn_region_loss_bytes,
  * matgcn_region_loss and matgcn_region_loss_grad; no existing symbol, signature, struct or value changed.
+ * Still ABI 12: new names only - training on the CRPS of the Monte-Carlo-dropout ensemble adds the functions
+ * matgcn_train_mc_bytes, matgcn_forward_train_mc, matgcn_backward_mc, matgcn_crps_loss_bytes, matgcn_crps_loss and
+ * matgcn_crps_loss_grad; no existing symbol, signature, struct or value changed, both *_bytes() of the training step give
+ * their numbers, and no existing entry point launches anything else than it did.
  */
 #ifndef MATGCN_H
 #define MATGCN_H
@@ -1006,6 +1010,77 @@ int matgcn_set_train_bf16x3(int enabled);
  * section 5c): 20 887 040 bytes of slabs; backward 14.3 ms against 13.8 (+3.6 %), training step 22.0 ms against 21.7
  * (+1.7 %); the default path as fast as before the switch existed.  No single site dominates the added time. */
 int matgcn_set_deterministic(int enabled);
+
+/* ---- ensemble training: CRPS over dropout samples, backward through the head -----------------------------------------------
+ * Dropout sits only in front of end_conv, so the encoder - its saved activations and its backward chain - does not depend
+ * on the mask: a step that trains on S samples runs the encoder ONCE in both directions and only the head S times.
+ *
+ * matgcn_forward_train_mc: matgcn_forward_train with drop_mask = NULL - its kernels, its precision mode, the same bits in
+ * `train` and the workspace - with the head replaced by k_head_mc over `samples` masks of the top layer's sequence, sample s
+ * drawn at dropout->offset + s.  samples_out (samples, B, out, N, od) is required; mean / std (B, out, N, od) may be NULL.
+ * samples_out[s] is bit-equal to what matgcn_forward_mc writes for the same descriptor (fp32 modes) and to
+ * matgcn_output_head on seq * mask_s.  Limits as matgcn_forward_mc: in_steps > 24 without fnn_off or out_channels > 64 is
+ * MATGCN_ERR_UNSUPPORTED, samples outside 1 .. MATGCN_MAX_MC_SAMPLES is MATGCN_ERR_BAD_ARG; p = 0 is a valid descriptor.
+ * `train` must hold matgcn_train_mc_bytes(dims, samples) bytes (less: MATGCN_ERR_SMALL_BUFFER): matgcn_train_bytes of any
+ * setting, plus a tail for this pair - two (B, out, N, od) tensors, the partial slabs of the head's weight gradient (at most
+ * 256 x out_channels x headT x 64 floats) and samples x out_channels doubles.  matgcn_train_bytes and
+ * matgcn_workspace_bytes are unchanged.
+ *
+ * matgcn_backward_mc: matgcn_backward behind matgcn_forward_train_mc.  d_samples (samples, B, out, N, od) is the gradient
+ * w.r.t. samples_out; by linearity every gradient equals the sum over s of what matgcn_backward returns with
+ * drop_mask = mask(seed, offset + s) and d_out = d_samples[s] on the same saved activations.  Only the head stage differs
+ * (bwd_head_mc beside bwd_head; fp32 in every training precision mode); the chains, the weight-gradient streams, the error
+ * exits and the mode that follows the forward are matgcn_backward's.  No mask and no (S, B, T, N, 64) tensor exists:
+ *   k_head_mc_dseq   one workgroup per (b, 32-node tile); the 24 x 32 x 64 tile of the sequence gradient stays in 192
+ *                    accumulator registers per lane over all samples, d_s . W on the fp32 MFMA, the multiplier drawn at the
+ *                    element's position and applied as the product lands; every element is stored once;
+ *   k_head_mc_wgrad  32 channels x 12 steps per workgroup, accumulators in registers over its (b, tile) items and all
+ *                    samples, one partial slab per workgroup column, added in ascending order by k_ordered_reduce - no
+ *                    atomics: the head's gradients have the same bits from run to run in both settings of
+ *                    matgcn_set_deterministic (which governs everything behind the head as before);
+ *   k_head_mc_dbias_* the bias gradient in two ordered stages, fp64 partial sums.
+ * Measured at Baltimore 403 / B = 64 / out = 24 (MI355X, tools/crps_train_time.py bm403 30 3, one process, routes
+ * alternating three times, median of 30 steps): the whole step on S = 8 / 32 samples 22.8 / 28.5 ms
+ * against 21.0 ms for the seeded masked-MAE step and 166 / 662 ms for S seeded steps; matgcn_forward_train_mc 9.47 ms at
+ * S = 32 against matgcn_forward_train 6.95 ms.  Kernels at S = 32 under a kernel trace of the serial schedule: k_head_mc
+ * 2.45 ms, k_head_mc_dseq 2.51 ms, k_head_mc_wgrad 1.74 ms - against 0.39 ms each for their 60.8 GFLOP at the nominal fp32
+ * MFMA rate: 4.5x to 6.4x off, not near the matrix pipe's time; k_crps_partial + k_loss_final + k_crps_grad 0.159 + 0.016 +
+ * 0.162 ms against about 0.04 ms for one read plus one write of the 79 MB of samples.
+ *
+ * matgcn_crps_loss / matgcn_crps_loss_grad: the CRPS matgcn_mc_scores reports, as a differentiable objective of the samples.
+ * Labels, mask, de-scaling and geometry are exactly matgcn_mc_scores' (the series label rule included).  Per unmasked
+ * element, in fp64 from the fp32 values, i 0-based in ascending order:
+ *   c = (1/S) sum_s |p_s - l| - (1/S^2) sum_i (2i - S + 1) p_(i)
+ * result[0] = float32(sum c / M) over all horizons, result[1 + k] horizon k alone; a group that keeps nothing gives 0
+ * (matgcn_loss's rule for its masked kinds).  out_steps <= 64.  Gradient of result[0]:
+ *   d_samples[s] = upstream * (std / M) * ( sgn(p_s - l) / S - (2 r_s - S + 1) / S^2 ),
+ * r_s the 0-based rank of sample s sorted by (value, sample index) - the index decides ties, so the sub-gradient is a
+ * definite number -, sgn(0) = 0 as in matgcn_loss's MAE gradient; formed in fp64, rounded once; masked elements get 0 in all
+ * S samples.  d_samples MAY be `samples` itself: a workgroup reads its tile completely before it writes it.  The sort is
+ * matgcn_mc_scores' LDS bitonic network with its tile rule (64 / 32 / 16 elements by S), over (value, index) pairs in the
+ * gradient (96 KB of LDS at most); the padding to a power of two never reaches a result.  Two stages in a fixed order -
+ * one workgroup per (b, horizon) row walks the row's tiles, then matgcn_loss's second stage -, no atomics, nothing
+ * allocated, all work on the caller's stream.  scratch: caller-owned device memory of matgcn_crps_loss_bytes (=
+ * matgcn_loss_bytes) bytes; the gradient call takes the scratch its value call left.  Every argument is checked on the host
+ * before anything is launched, with the refusals of matgcn_mc_scores. */
+int matgcn_train_mc_bytes(const matgcn_dims* dims, int samples, size_t* bytes);
+int matgcn_forward_train_mc(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
+                            const matgcn_series* src, const float* h0, const matgcn_dropout* dropout, int samples,
+                            float* mean, float* std, float* samples_out, void* workspace, size_t workspace_bytes,
+                            void* train, size_t train_bytes, void* stream);
+int matgcn_backward_mc(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
+                       const matgcn_series* src, const float* h0, const matgcn_dropout* dropout, int samples,
+                       const float* d_samples, const matgcn_grads* grads, float* d_h0, void* workspace,
+                       size_t workspace_bytes, void* train, size_t train_bytes, void* stream);
+int matgcn_crps_loss_bytes(int batch, int out_steps, size_t* bytes);
+int matgcn_crps_loss(const float* samples /* (S, B, out, N, od) */, int n_samples, const float* y, const int32_t* label_start, int batch,
+                     int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start, float mean, float std,
+                     float null_val, float min_s, void* scratch, size_t scratch_bytes, float* result /* 1 + out_steps */,
+                     void* stream);
+int matgcn_crps_loss_grad(const float* samples /* (S, B, out, N, od) */, int n_samples, const float* y, const int32_t* label_start, int batch,
+                          int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start, float mean,
+                          float std, float null_val, float min_s, const void* scratch, size_t scratch_bytes,
+                          float upstream, float* d_samples /* (S, B, out, N, od); may alias samples */, void* stream);
 
 /* ---- measurement hooks (bench.py; not on the hot path) ---------------------------------------
  * Time individual kernel launches in situ with HIP events recorded on the caller's stream.

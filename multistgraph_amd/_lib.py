@@ -205,10 +205,25 @@ _SIGNATURES = {
     "matgcn_profile_collect": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "matgcn_profile_disable": (C.c_int, []),
 }
+# Ensemble training (CRPS over dropout samples), a table of its own: _SIGNATURES is the list that tests/test_stream_order.py
+# sweeps name by name, and these entry points have their stream-order sweep in tests/test_crps_train.py.  load() and call()
+# treat the two tables as one.
+_ENSEMBLE_SIGNATURES = {
+    "matgcn_train_mc_bytes": (C.c_int, [C.POINTER(Dims), C.c_int, C.POINTER(C.c_size_t)]),
+    "matgcn_forward_train_mc": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), _P, _P, C.POINTER(Series), _P,
+                                          C.POINTER(Dropout), C.c_int, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "matgcn_backward_mc": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), _P, _P, C.POINTER(Series), _P, C.POINTER(Dropout),
+                                     C.c_int, _P, C.POINTER(Params), _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "matgcn_crps_loss_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "matgcn_crps_loss": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_float, C.c_float, C.c_float, C.c_float, _P, C.c_size_t, _P, _P]),
+    "matgcn_crps_loss_grad": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_float, C.c_float, C.c_float, C.c_float, _P, C.c_size_t, C.c_float, _P, _P]),
+}
 # matgcn_profile_* kernel kinds (MATGCN_PROF_*): k_mix = k_mix<1> (per-step graph mix), k_mix_pre = k_mix<0>,
 # k_gate = k_gate16, k_update = k_update16<0|1> (update [+ residual cell]), k_res_gru = k_update16<2>, k_px = k_px16
 PROF_KINDS = {1: "k_mix", 2: "k_gate", 4: "k_update", 8: "k_res_gru", 16: "k_px", 32: "k_head", 64: "k_mix_pre"}
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_ENSEMBLE_SIGNATURES)
 
 _lib = None
 _entries: dict = {}     # name -> the loaded function, as call() has looked it up
@@ -224,7 +239,7 @@ def load() -> C.CDLL:
             "libmatgcn.so is not built (%s). Run `python -m multistgraph_amd.build` "
             "(hipcc --offload-arch=gfx950); there is no CPU or PyTorch fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_ENSEMBLE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch, let it propagate
         fn.restype = res
         fn.argtypes = args
@@ -250,7 +265,7 @@ def call(name: str, *args) -> None:
     name include/matgcn.h does not declare raises before anything is called."""
     fn = _entries.get(name)
     if fn is None:
-        if name not in _SIGNATURES:
+        if name not in _SIGNATURES and name not in _ENSEMBLE_SIGNATURES:
             raise MatgcnError("%s is not an entry point of libmatgcn.so" % name)
         fn = _entries[name] = getattr(load(), name)
     status = fn(*args)

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmatgcn.so")
 SOURCES = ["matgcn_capi.hip"]
-DEPS = ["matgcn_capi.hip", "matgcn_eval.hip", "matgcn_kernels.hip", "matgcn_node16.hip", "matgcn_bwd.hip", "matgcn_bwd_kernels.hip", "matgcn_mc_scores.hip", "matgcn_conformal.hip", "matgcn_regions.hip", "matgcn_optim.hip", "matgcn_loss.hip", "matgcn_region_loss.hip",
+DEPS = ["matgcn_capi.hip", "matgcn_eval.hip", "matgcn_kernels.hip", "matgcn_node16.hip", "matgcn_bwd.hip", "matgcn_bwd_kernels.hip", "matgcn_mc_scores.hip", "matgcn_conformal.hip", "matgcn_regions.hip", "matgcn_optim.hip", "matgcn_loss.hip", "matgcn_region_loss.hip", "matgcn_crps.hip", "matgcn_head_mc_bwd.hip",
         "matgcn_internal.h",
         "matgcn_philox.h",
         os.path.join("..", "..", "include", "matgcn.h")]

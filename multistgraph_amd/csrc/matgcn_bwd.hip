@@ -163,6 +163,11 @@ struct Bwd {
   // partial slabs of its ordered reductions (TrainPlan::detArena floats), and the start of the deterministic tail
   float* det = nullptr;
   float* detTail = nullptr;
+  // matgcn_backward_mc (mcSamples > 0): the head stage runs over the samples' gradients (S, B, out, N, od) with sample s
+  // drawn at drop.offset + s (bwd_head_mc); its slabs sit in the ensemble tail of the train buffer
+  int mcSamples = 0;
+  const float* dSamples = nullptr;
+  TrainMcTail mcTail = {};
 };
 
 // dst[b][r][c] (= or +=) the `parts` compact slabs at part + p * stride, added in ascending p (k_ordered_reduce)
@@ -712,6 +717,42 @@ int bwd_head(Pass& pass, const float* dOut) {
   }
 
   return MATGCN_OK;
+}
+
+// The head stage of matgcn_backward_mc, beside bwd_head: the same three outputs - the sequence gradient at R.oDSeq[0] and
+// the gradients of end_conv's weight and bias - summed over the samples' masks (matgcn_head_mc_bwd.hip).  The weight and
+// bias gradients feed nothing in this pass: with two streams they run on the second one, as bwd_head's weight gradient.
+int bwd_head_mc(Pass& pass) {
+  PASS_LOCALS(pass);
+  HeadMcBwdArgs m;
+  memset(&m, 0, sizeof(m));
+  float* tail = tr + b.mcTail.start;
+  m.dS = b.dSamples; m.w = prm->end_conv_weight;
+  m.seq = c.ws + P.oSeq[P.L - 1] + (size_t)tOff * slab;     // forward_train_mc keeps the sequence without dropout
+  m.dSeq = tr + R.oDSeq[0] + (size_t)tOff * slab;
+  m.wPart = tail + b.mcTail.oWPart;
+  m.drop = b.drop; m.samples = b.mcSamples;
+  m.B = B; m.T = hT; m.N = N; m.Np = Np; m.CH = P.CH; m.od = P.od;
+  const unsigned tiles = (unsigned)(B * ((N + 31) / 32));
+  hipLaunchKernelGGL(k_head_mc_dseq, dim3(tiles), dim3(256), 0, s, m);
+  CHECK_LAUNCH();
+  hipStream_t hs = s;
+  if (pass.twoStreams) {
+    HIP_OK(hipEventRecord(g_wf.auxFork, s));
+    HIP_OK(hipStreamWaitEvent(pass.ws, g_wf.auxFork, 0));
+    hs = pass.ws;
+  }
+  hipLaunchKernelGGL(k_head_mc_wgrad, dim3((unsigned)b.mcTail.wParts, (unsigned)b.mcTail.wStepGroups, (unsigned)P.NTc),
+                     dim3(256), 0, hs, m);
+  CHECK_LAUNCH();
+  RETURN_IF(ordered_reduce(g->end_conv_weight, m.wPart, b.mcTail.wParts, (long)P.CH * hT * H, (long)P.CH * hT * H, false,
+                           hs));
+  double* biasPart = reinterpret_cast<double*>(tail + b.mcTail.oBiasPart);
+  hipLaunchKernelGGL(k_head_mc_dbias_partial, dim3((unsigned)P.CH, (unsigned)b.mcSamples), dim3(256), 0, hs, m, biasPart);
+  CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_head_mc_dbias_final, dim3((unsigned)((P.CH + 63) / 64)), dim3(64), 0, hs, biasPart, b.mcSamples,
+                     P.CH, g->end_conv_bias);
+  return launch_ok();
 }
 
 // gcn_off: a layer of dense GRU cells
@@ -1486,7 +1527,8 @@ int backward_impl(Bwd& b, const float* dOut) {
     HIP_OK(hipEventRecord(g_wf.auxDone, q.ws));   // (k_res_narrow2 on the chain's stream reads the time-major input)
   }
   RETURN_IF(bwd_clear(q));
-  RETURN_IF(bwd_head(q, dOut));
+  if (b.mcSamples > 0) RETURN_IF(bwd_head_mc(q));
+  else RETURN_IF(bwd_head(q, dOut));
   // A wavefront over the layers, as in the forward: step t of layer l needs the x-column gradient of layer l+1 for the
   // chunk of steps that holds t (and t-1) only - not its whole chain.  Every second layer therefore walks its chain (and
   // everything else that used to sit on the caller's stream for it) on a library stream, beside the chain of the layer
@@ -1543,12 +1585,20 @@ int matgcn_train_bytes(const matgcn_dims* dims, size_t* bytes) {
   return MATGCN_OK;
 }
 
+// what matgcn_forward_train_mc puts in the place of the head: k_head_mc over `samples` masks of the plain top sequence
+struct McHead {
+  DropDesc drop;
+  int samples;
+  float *mean, *stdev, *samplesOut;   // mean / stdev: null = into the ensemble tail of the train buffer
+};
+
 // seeded (matgcn_forward_train_seeded; null or !on: none): the dropout from the generator in place of drop_mask
+// mc (matgcn_forward_train_mc; null: none): no dropout on the way, `out` is not written, the head runs over the samples
 static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
                               const matgcn_series* src, const float* h0, const float* drop_mask, const DropDesc* seeded,
                               float* out, void* workspace, size_t workspace_bytes, void* train, size_t train_bytes,
-                              void* stream) {
-  if (!prepared || (!X && !src) || !out || !train) return MATGCN_ERR_NULL;
+                              void* stream, const McHead* mc = nullptr) {
+  if (!prepared || (!X && !src) || (!out && !mc) || !train) return MATGCN_ERR_NULL;
   const bool seed = seeded && seeded->on;
   if (seed && drop_mask) return MATGCN_ERR_BAD_ARG;
   if (src) RETURN_IF(check_series(dims, src->series, src->series_steps, src->label_start, src->rel_steps));
@@ -1562,6 +1612,12 @@ static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* para
   const Plan& P = c.P;
   RETURN_IF(make_train_plan(P, &c.R));
   if (train_bytes < (size_t)c.R.floats * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;
+  TrainMcTail mcTail = {};
+  if (mc) {   // before anything is enqueued: what k_head_mc holds in registers, and the tail of matgcn_train_mc_bytes
+    if (P.headT > 4 * HEAD_MC_STEPS || P.NTc > 2) return MATGCN_ERR_UNSUPPORTED;
+    mcTail = train_mc_tail(P, c.R, mc->samples);
+    if (train_bytes < (size_t)(mcTail.start + mcTail.floats) * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;
+  }
   c.train = (float*)train;
   // precision (matgcn_set_train_precision): bf16 operands for the graph mixes (mode >= 1) and the node-wise contractions
   // (mode 2, bf16 copies of the weight streams in the workspace) - as the inference forward of that mode; the saved
@@ -1626,7 +1682,13 @@ static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* para
     CHECK_LAUNCH();
     seqTop = dropped;
   }
-  RETURN_IF(head_padded(c, seqTop, out));
+  if (mc) {
+    float* tail = c.train + mcTail.start;
+    RETURN_IF(head_mc_padded(c, seqTop, mc->drop, mc->samples, mc->mean ? mc->mean : tail + mcTail.oMean,
+                             mc->stdev ? mc->stdev : tail + mcTail.oStd, mc->samplesOut));
+  } else {
+    RETURN_IF(head_padded(c, seqTop, out));
+  }
   note_train_mode(train, mode);
   return MATGCN_OK;
 }
@@ -1636,9 +1698,9 @@ static int forward_train_impl(const matgcn_dims* dims, const matgcn_params* para
 static int forward_train_entry(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
                                const matgcn_series* src, const float* h0, const float* drop_mask, const DropDesc* seeded,
                                float* out, void* workspace, size_t workspace_bytes, void* train, size_t train_bytes,
-                               void* stream) {
+                               void* stream, const McHead* mc = nullptr) {
   JOINED(forward_train_impl(dims, params, prepared, X, src, h0, drop_mask, seeded, out, workspace, workspace_bytes, train,
-                            train_bytes, stream), stream);
+                            train_bytes, stream, mc), stream);
 }
 
 int matgcn_forward_train(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
@@ -1665,7 +1727,8 @@ static int backward_entry(const matgcn_dims* dims, const matgcn_params* params, 
                           const matgcn_series* src, const float* h0, const float* drop_mask, const DropDesc* seeded,
                           const float* d_out,
                           const matgcn_grads* grads, float* d_h0, void* workspace, size_t workspace_bytes, void* train,
-                          size_t train_bytes, void* stream) {
+                          size_t train_bytes, void* stream, int mcSamples = 0) {
+  // mcSamples > 0 (matgcn_backward_mc): d_out is the samples' gradient (S, B, out, N, od), seeded the samples' descriptor
   if (!prepared || (!X && !src) || !d_out || !grads || !train) return MATGCN_ERR_NULL;
   if (src) RETURN_IF(check_series(dims, src->series, src->series_steps, src->label_start, src->rel_steps));
   Bwd b;
@@ -1679,6 +1742,12 @@ static int backward_entry(const matgcn_dims* dims, const matgcn_params* params, 
     b.drop = *seeded;
   }
   b.hasH0 = h0 != nullptr; b.dH0 = d_h0; b.src = src;
+  if (mcSamples > 0) {
+    if (b.c.P.headT > 4 * HEAD_MC_STEPS || b.c.P.NTc > 2) return MATGCN_ERR_UNSUPPORTED;   // as its forward
+    b.mcSamples = mcSamples; b.dSamples = d_out;
+    b.mcTail = train_mc_tail(b.c.P, b.c.R, mcSamples);
+    if (train_bytes < (size_t)(b.mcTail.start + b.mcTail.floats) * sizeof(float)) return MATGCN_ERR_SMALL_BUFFER;
+  }
   // the mode the matching forward_train ran with, whatever the setting is now (-1: that forward_train failed)
   const int mode = train_mode_of(train);
   if (mode < 0) return MATGCN_ERR_BAD_ARG;
@@ -1711,6 +1780,48 @@ int matgcn_backward_seeded(const matgcn_dims* dims, const matgcn_params* params,
   return on_main_stream(stream, [&](void* s) {
     return backward_entry(dims, params, prepared, X, src, h0, nullptr, &d, d_out, grads, d_h0, workspace, workspace_bytes,
                           train, train_bytes, s);
+  });
+}
+
+// ---- the ensemble step: the encoder once in both directions, the head over the samples (include/matgcn.h) ---------------
+int matgcn_train_mc_bytes(const matgcn_dims* dims, int samples, size_t* bytes) {
+  if (!bytes) return MATGCN_ERR_NULL;
+  if (samples < 1 || samples > MATGCN_MAX_MC_SAMPLES) return MATGCN_ERR_BAD_ARG;
+  Plan P;
+  RETURN_IF(make_plan(dims, &P));
+  TrainPlan R;
+  RETURN_IF(make_train_plan(P, &R));
+  const TrainMcTail t = train_mc_tail(P, R, samples);
+  *bytes = (size_t)(t.start + t.floats) * sizeof(float);
+  return MATGCN_OK;
+}
+
+int matgcn_forward_train_mc(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
+                            const matgcn_series* src, const float* h0, const matgcn_dropout* dropout, int samples,
+                            float* mean, float* std, float* samples_out, void* workspace, size_t workspace_bytes,
+                            void* train, size_t train_bytes, void* stream) {
+  if (!dropout || !samples_out) return MATGCN_ERR_NULL;
+  if (samples < 1 || samples > MATGCN_MAX_MC_SAMPLES) return MATGCN_ERR_BAD_ARG;
+  McHead mc = {};
+  RETURN_IF(make_drop_desc(dropout, &mc.drop));
+  mc.samples = samples; mc.mean = mean; mc.stdev = std; mc.samplesOut = samples_out;
+  return on_main_stream(stream, [&](void* s) {
+    return forward_train_entry(dims, params, prepared, X, src, h0, nullptr, nullptr, nullptr, workspace, workspace_bytes,
+                               train, train_bytes, s, &mc);
+  });
+}
+
+int matgcn_backward_mc(const matgcn_dims* dims, const matgcn_params* params, const void* prepared, const float* X,
+                       const matgcn_series* src, const float* h0, const matgcn_dropout* dropout, int samples,
+                       const float* d_samples, const matgcn_grads* grads, float* d_h0, void* workspace,
+                       size_t workspace_bytes, void* train, size_t train_bytes, void* stream) {
+  if (!dropout) return MATGCN_ERR_NULL;
+  if (samples < 1 || samples > MATGCN_MAX_MC_SAMPLES) return MATGCN_ERR_BAD_ARG;
+  DropDesc d = {};
+  RETURN_IF(make_drop_desc(dropout, &d));
+  return on_main_stream(stream, [&](void* s) {
+    return backward_entry(dims, params, prepared, X, src, h0, nullptr, &d, d_samples, grads, d_h0, workspace,
+                          workspace_bytes, train, train_bytes, s, samples);
   });
 }
 

@@ -23,6 +23,8 @@
 #include "matgcn_optim.hip"
 #include "matgcn_loss.hip"
 #include "matgcn_region_loss.hip"
+#include "matgcn_crps.hip"
+#include "matgcn_head_mc_bwd.hip"
 
 namespace {
 
@@ -335,6 +337,38 @@ inline long train_floats(const Plan& P, const TrainPlan& R, int mode) {
   return mode == 2 && !P.gcnOff ? R.floatsBf16 : mode == 3 ? R.floatsX3 : R.floats;
 }
 
+// The tail of a train buffer that serves the ensemble step (matgcn_train_mc_bytes): it starts behind the longest of the
+// three ends above plus the deterministic slabs - one offset whatever the settings of the moment are - and holds what
+// matgcn_forward_train_mc writes when the caller wants no mean / std, the partial slabs of the head's weight gradient over
+// the samples (one per workgroup column of k_head_mc_wgrad) and the per-sample partial sums of its bias gradient.
+struct TrainMcTail {
+  long start;                // first float of the tail in the train buffer
+  long oMean, oStd;          // (B, CH, N) each
+  long oWPart;               // [wParts][CH][headT][64]
+  long oBiasPart;            // [samples][CH] doubles
+  int wParts, wStepGroups;   // grid of k_head_mc_wgrad: x and y
+  long floats;               // of the tail
+};
+inline TrainMcTail train_mc_tail(const Plan& P, const TrainPlan& R, int samples) {
+  TrainMcTail t;
+  long base = R.floats > R.floatsBf16 ? R.floats : R.floatsBf16;
+  if (R.floatsX3 > base) base = R.floatsX3;
+  t.start = rup(base + R.detFloats, 64);
+  long o = 0;
+  auto take = [&](long n) { long at = o; o += rup(n, 64); return at; };
+  t.oMean = take((long)P.B * P.CH * P.N);
+  t.oStd = take((long)P.B * P.CH * P.N);
+  t.wStepGroups = (P.headT + 4 * HMB_WSTEPS - 1) / (4 * HMB_WSTEPS);
+  const long items = (long)P.B * ((P.N + 31) / 32);
+  long parts = 256 / (t.wStepGroups * P.NTc);             // about one workgroup per CU
+  if (parts < 1) parts = 1;
+  t.wParts = (int)(items < parts ? items : parts);
+  t.oWPart = take((long)t.wParts * P.CH * P.headT * H);
+  t.oBiasPart = take(2L * samples * P.CH);
+  t.floats = o;
+  return t;
+}
+
 // ---- optional in-situ launch timing (matgcn_profile_*) ------------------------------------------------
 struct Prof {
   int mask = 0, cap = 0, used = 0;
@@ -435,6 +469,7 @@ struct DeviceState {
   int nodeLds = 0;           // node_kernels_ready: dynamic LDS bytes the node kernels are opted into (function
                              // attributes are per device)
   bool chainFusedLds = false;   // chain_fused_ready: k_chain_res_fused<64> is opted into its dynamic LDS
+  int crpsLds = 0;           // matgcn_crps_loss_grad: k_crps_grad is opted into its 96 KB of dynamic LDS
 };
 DeviceState g_dev[MAX_DEVICES];
 inline int current_device() {

@@ -383,6 +383,71 @@ int matgcn_mc_scores_nodes(const float* samples, int n_samples, const float* y, 
   return launch_ok();
 }
 
+// ---- the ensemble's CRPS as a training objective (matgcn_crps.hip) ---------------------------------------------------------
+int matgcn_crps_loss_bytes(int batch, int out_steps, size_t* bytes) { return matgcn_loss_bytes(batch, out_steps, bytes); }
+
+namespace {
+// every check of the two CRPS entry points - the refusals of matgcn_mc_scores (grid, samples, the series label rule), the
+// scratch of matgcn_loss -; fills the kernels' argument block and the tile
+int crps_check(const float* samples, int n_samples, const float* y, const int32_t* label_start, int batch, int out_steps,
+               int nodes, int out_dim, int y_steps, int y_feat, int y_start, float mean, float std, float null_val,
+               float min_s, size_t scratch_bytes, CrpsArgs* a, long* blocks) {
+  RETURN_IF(mc_score_grid(batch, out_steps, nodes, out_dim, n_samples, &a->tilesPerRow, blocks));
+  RETURN_IF(label_view(LABELS_SERIES, y, label_start, batch, out_steps, nodes, out_dim, y_steps, y_feat, y_start, &a->lab));
+  size_t need = 0;
+  RETURN_IF(matgcn_crps_loss_bytes(batch, out_steps, &need));
+  if (scratch_bytes < need) return MATGCN_ERR_SMALL_BUFFER;
+  const McTile t = mc_tile(n_samples);
+  a->samples = samples; a->S = n_samples; a->P = t.P; a->logTE = t.logTE;
+  a->E = (long long)batch * out_steps * nodes * out_dim;
+  a->mean = mean; a->std = std; a->nullVal = null_val; a->minS = min_s;
+  return MATGCN_OK;
+}
+}  // namespace
+
+int matgcn_crps_loss(const float* samples, int n_samples, const float* y, const int32_t* label_start, int batch,
+                     int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start, float mean, float std,
+                     float null_val, float min_s, void* scratch, size_t scratch_bytes, float* result, void* stream) {
+  if (!samples || !y || !scratch || !result) return MATGCN_ERR_NULL;
+  CrpsArgs a;
+  long blocks = 0;
+  RETURN_IF(crps_check(samples, n_samples, y, label_start, batch, out_steps, nodes, out_dim, y_steps, y_feat, y_start, mean,
+                       std, null_val, min_s, scratch_bytes, &a, &blocks));
+  hipStream_t s = (hipStream_t)stream;
+  double* sc = (double*)scratch;
+  hipLaunchKernelGGL(k_crps_partial, dim3((unsigned)(batch * out_steps)), dim3(256), (size_t)mc_tile(n_samples).ldsBytes, s,
+                     a, sc);
+  CHECK_LAUNCH();
+  // the second stage of matgcn_loss's masked kinds: sum / count per horizon and over all, 0 where nothing is kept, and the
+  // count behind the slabs for the gradient
+  hipLaunchKernelGGL((k_loss_final<MATGCN_LOSS_MAE>), dim3(1), dim3(64), 0, s, sc, batch, out_steps, result);
+  return launch_ok();
+}
+
+int matgcn_crps_loss_grad(const float* samples, int n_samples, const float* y, const int32_t* label_start, int batch,
+                          int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start, float mean,
+                          float std, float null_val, float min_s, const void* scratch, size_t scratch_bytes,
+                          float upstream, float* d_samples, void* stream) {
+  if (!samples || !y || !scratch || !d_samples) return MATGCN_ERR_NULL;
+  CrpsArgs a;
+  long blocks = 0;
+  RETURN_IF(crps_check(samples, n_samples, y, label_start, batch, out_steps, nodes, out_dim, y_steps, y_feat, y_start, mean,
+                       std, null_val, min_s, scratch_bytes, &a, &blocks));
+  // (value, sample index) pairs: the floats of the tile and one 16-bit index each - 96 KB at most, opted into once
+  const int lds = (a.P << a.logTE) * (int)(sizeof(float) + sizeof(unsigned short));
+  if (lds > 64 * 1024) {
+    int& ready = dev_current().crpsLds;
+    if (!ready) {
+      RETURN_IF(lds_opt_in(reinterpret_cast<const void*>(k_crps_grad), MC_TILE_FLOATS * 6));
+      ready = 1;
+    }
+  }
+  const double* kept = (const double*)scratch + 2 * (size_t)batch * out_steps;
+  hipLaunchKernelGGL(k_crps_grad, dim3((unsigned)blocks), dim3(256), (size_t)lds, (hipStream_t)stream, a, kept, upstream,
+                     d_samples);
+  return launch_ok();
+}
+
 // ---- split conformal calibration of the band (matgcn_conformal.hip) -------------------------------------------------------
 int matgcn_mc_conformity(const float* samples, int n_samples, const float* y, const int32_t* label_start, int batch,
                          int out_steps, int nodes, int out_dim, int y_steps, int y_feat, int y_start,

@@ -27,6 +27,8 @@ from . import hidden_pad
 from .ops import (HotPath, PathSpec, diagonal_mask, group_sums, masked_mae_device, masked_mae_loss, mc_quantiles,
                   mc_quantiles_scaled, mc_scores, spec_from_config, train_loss_desc, train_loss_device)
 from .ops import tract_region_loss
+from .ops import crps_loss, crps_loss_device
+from ._lib import MAX_MC_SAMPLES
 from .ops import train_loss as train_loss_autograd
 from .regions import RegionMap
 
@@ -202,6 +204,42 @@ class _TrainStep(torch.autograd.Function):
                                                                       for k, p in zip(ctx.names, ctx.params))
 
 
+class _TrainStepMc(torch.autograd.Function):
+    """autograd node of one ensemble training forward, beside _TrainStep: matgcn_forward_train_mc returns the samples
+    (S, B, out, N, od) drawn at offsets offset .. offset + S - 1 of the (seed, offset, p) triple, matgcn_backward_mc takes
+    their gradient - the encoder runs once in both directions.  Generation check and parameter routing as _TrainStep."""
+
+    @staticmethod
+    def forward(ctx, path, x, dropout, samples, h0, names, *params):
+        h0 = None if h0 is None else h0.detach()
+        out = path.forward_train_mc(x, dropout, samples, h0)
+        ctx.path, ctx.x, ctx.dropout, ctx.names, ctx.h0 = path, x, dropout, names, h0
+        ctx.params = params
+        ctx.generation = path.train_generation
+        return out
+
+    @staticmethod
+    def backward(ctx, d_samples):
+        path = ctx.path
+        if path.train_generation != ctx.generation:
+            raise RuntimeError("MultiATGCN backward: another forward ran on this model between this forward and its "
+                               "backward; the saved activations live in the shared workspace (one graph at a time)")
+        state = {k: p for k, p in zip(ctx.names, ctx.params)}
+        grads = path.backward_mc(ctx.x, d_samples.contiguous(), state, ctx.dropout, ctx.h0)
+        return (None, None, None, None, grads.get(path.D_H0), None) + tuple(grads.get(k) if p.requires_grad else None
+                                                                            for k, p in zip(ctx.names, ctx.params))
+
+
+CRPS_LOSS = "crps"          # config['hip_train_loss']: the CRPS of a Monte-Carlo-dropout ensemble (ops.crps_loss)
+CRPS_NULL_VAL = 0.0         # its mask: calculate_loss's and score_mc's null value
+
+
+def _train_samples(value, key: str = "hip_train_samples") -> int:
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= MAX_MC_SAMPLES:
+        raise ValueError("%s = %r: expected an int from 1 to %d" % (key, value, MAX_MC_SAMPLES))
+    return int(value)
+
+
 class MultiATGCN(AbstractTrafficStateModel):
     def __init__(self, config, data_feature):
         super().__init__(config, data_feature)
@@ -248,8 +286,16 @@ class MultiATGCN(AbstractTrafficStateModel):
         # 1.0 and 0.25).  Attributes like the three above: checkpoints are unchanged.
         self.hip_train_loss = str(get("hip_train_loss", "none")).lower()
         self.hip_train_loss_delta = get("hip_train_loss_delta", None)
-        if self.hip_train_loss != "none":
+        if self.hip_train_loss not in ("none", CRPS_LOSS):
             train_loss_desc(self.hip_train_loss, 0.0, 1.0, self.hip_train_loss_delta)   # ValueError on a bad name or delta
+        # "crps": calculate_loss / calculate_loss_series return the mean CRPS of an ensemble of config['hip_train_samples']
+        # (1 .. 1024, default 16) dropout samples - one encoder pass in both directions, the head over the samples
+        # (matgcn_forward_train_mc / matgcn_crps_loss / matgcn_backward_mc).  A step consumes that many dropout offsets.
+        # The masks of S samples cannot come from torch's generator: "crps" needs hip_dropout = "device".
+        self.hip_train_samples = _train_samples(get("hip_train_samples", 16))
+        if self.hip_train_loss == CRPS_LOSS and self.hip_dropout != "device":
+            raise ValueError("hip_train_loss = 'crps' needs hip_dropout = 'device' (a torch-drawn mask cannot serve "
+                             "hip_train_samples samples), got hip_dropout = %r" % self.hip_dropout)
         # config['hip_train_regions']: a regions.RegionMap, its state_dict() or one region label per node;
         # config['hip_region_loss_weight'] (default 0.0 = off) and config['hip_tract_loss_weight'] (default 1.0): with a
         # region weight > 0 calculate_loss / calculate_loss_series return
@@ -260,6 +306,8 @@ class MultiATGCN(AbstractTrafficStateModel):
         self.hip_train_regions = _train_regions(get("hip_train_regions", None), self.num_nodes)
         self.hip_region_loss_weight = _loss_weight(get("hip_region_loss_weight", 0.0), "hip_region_loss_weight")
         self.hip_tract_loss_weight = _loss_weight(get("hip_tract_loss_weight", 1.0), "hip_tract_loss_weight")
+        if self.hip_train_loss == CRPS_LOSS and self.hip_train_regions is not None:
+            raise NotImplementedError("hip_train_loss = 'crps' with hip_train_regions: the CRPS of region totals is not built")
         if self.hip_region_loss_weight > 0.0 and self.hip_train_regions is None:
             raise ValueError("hip_region_loss_weight = %r needs a region map: set hip_train_regions"
                              % self.hip_region_loss_weight)
@@ -447,6 +495,45 @@ class MultiATGCN(AbstractTrafficStateModel):
             padded = hidden_pad.pad_state(dict(named), self.hidden_dim, self.feature_final)
             named = [(k, padded[k]) for k, _ in named]
         return _TrainStep.apply(hp, source, mask, h0, tuple(k for k, _ in named), *[p for _, p in named])
+
+    def _crps(self, source, batch: int, device, y, label_start, samples: int):
+        """The mean CRPS of an ensemble of ``samples`` dropout samples against the labels (``y`` windows, or with
+        label_start the resident series) - the composition of HotPath.forward_train_mc, ops.crps_loss and
+        HotPath.backward_mc.  With gradients enabled the samples carry the graph (one encoder pass in both directions);
+        without, they come from the inference forward (matgcn_forward_mc).  Consumes ``samples`` dropout offsets."""
+        affine = self._affine_scaler()
+        if affine is None:
+            raise NotImplementedError("the CRPS objective needs an affine scaler (StandardScaler / NoneScaler)")
+        needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        h0 = self._initial_state(batch)
+        h0 = None if h0 is None else (hidden_pad.pad_last(h0) if self._padded else h0.contiguous())
+        hp = self._path_for_batch(batch, device)
+        seed, offset = torch.initial_seed(), self._dropout_offset(samples)
+        if not needs_grad:
+            with torch.no_grad():
+                kept = hp.forward_mc(source, h0, seed=seed, offset=offset, p=DROPOUT_P, samples=samples,
+                                     keep_samples=True)[2]
+            return crps_loss_device(kept, y, self.start_dim, affine[0], affine[1], CRPS_NULL_VAL,
+                                    label_start=label_start)[0]
+        named = [(k, p) for k, p in self.named_parameters() if not k.startswith("static_initial")]
+        if self._padded:   # differentiable zero-padding, as in _run
+            padded = hidden_pad.pad_state(dict(named), self.hidden_dim, self.feature_final)
+            named = [(k, padded[k]) for k, _ in named]
+        kept = _TrainStepMc.apply(hp, source, (seed, offset, DROPOUT_P), samples, h0, tuple(k for k, _ in named),
+                                  *[p for _, p in named])
+        return crps_loss(kept, y, self.start_dim, affine[0], affine[1], CRPS_NULL_VAL, label_start=label_start)
+
+    def _crps_batch(self, batch, samples: int):
+        """``_crps`` of a window batch (``X``, ``y``) or a resident-series batch"""
+        if _is_series_batch(batch):
+            src = self._batch_source(batch)
+            return self._crps(src, int(src[1].shape[0]), src[0].device, src[0], src[1], samples)
+        x = batch["X"]
+        assert x.shape[2] == self.num_nodes
+        if not x.is_cuda:
+            raise RuntimeError("MultiATGCN runs on the HIP hot path only: batch['X'] is on %s." % x.device)
+        x = (x if x.dtype == torch.float32 else x.float()).contiguous()
+        return self._crps(x, int(x.shape[0]), x.device, batch["y"], None, samples)
 
     def forward(self, batch):
         if _is_series_batch(batch):    # MTHDatasetResident: windows and labels are gathered on the device (f-2)
@@ -689,6 +776,8 @@ class MultiATGCN(AbstractTrafficStateModel):
         the targets series[label_start[b] + o] gathered by the loss kernel on the device.  With gradients enabled this is
         the executor's training step (traffic_state_executor.py:411-422) without any host-side window or label."""
         src = self._series_source(series, label_start, rel_steps, trusted=_checked)
+        if self.hip_train_loss == CRPS_LOSS:
+            return self._crps(src, int(src[1].shape[0]), series.device, series, src[1], self.hip_train_samples)
         pred = self._run(src, int(src[1].shape[0]), series.device)
         ls = src[1]
         if self.hip_region_loss_weight > 0.0:
@@ -798,6 +887,8 @@ class MultiATGCN(AbstractTrafficStateModel):
         if _is_series_batch(batch):
             src = self._batch_source(batch)
             return self.calculate_loss_series(src[0], src[1], src[2], _checked=True)
+        if self.hip_train_loss == CRPS_LOSS:
+            return self._crps_batch(batch, self.hip_train_samples)
         y_true = batch["y"]
         y_predicted = self.predict(batch)
         if self.hip_region_loss_weight > 0.0:
@@ -832,7 +923,7 @@ class MultiATGCN(AbstractTrafficStateModel):
         out = fn(pred, y, self.start_dim, affine[0], affine[1], name, delta, label_start)
         return out if pred.requires_grad else out[0]
 
-    def train_loss(self, batch, name, delta=None, regions=None, region_weight=1.0, tract_weight=1.0):
+    def train_loss(self, batch, name, delta=None, regions=None, region_weight=1.0, tract_weight=1.0, samples=None):
         """One of the executor's eleven differentiable training objectives (TrafficStateExecutor._build_train_loss,
         traffic_state_executor.py:200-250; ops.TRAIN_LOSSES) of a window batch (``X``, ``y``) or a resident-series batch
         (``series``, ``label_start``): predict, de-scale, mask and reduce in a fixed order on the device (matgcn_loss); with
@@ -840,7 +931,13 @@ class MultiATGCN(AbstractTrafficStateModel):
         knee / quantile's level (None: 1.0 / 0.25, the reference's defaults).  The label channels start at ``start_dim``,
         as in calculate_loss.  ``regions`` (a regions.RegionMap, its state_dict() or one label per node; None: what
         this method always did): tract_weight * L(tracts) + region_weight * L(region totals) with the same objective on
-        both levels (matgcn_region_loss / matgcn_region_loss_grad); a weight of 0 skips its half."""
+        both levels (matgcn_region_loss / matgcn_region_loss_grad); a weight of 0 skips its half.
+        ``name`` = "crps": the mean CRPS of an ensemble of ``samples`` dropout samples (None: hip_train_samples), what
+        calculate_loss returns under hip_train_loss = "crps"; drawn on the device whatever hip_dropout says."""
+        if str(name).lower() == CRPS_LOSS:
+            if regions is not None:
+                raise NotImplementedError("train_loss 'crps' with regions: the CRPS of region totals is not built")
+            return self._crps_batch(batch, self.hip_train_samples if samples is None else _train_samples(samples, "samples"))
         train_loss_desc(name, 0.0, 1.0, delta)      # refuse a bad name or delta before any kernel runs
         if regions is not None:
             regions = _train_regions(regions, self.num_nodes)

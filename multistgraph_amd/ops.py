@@ -524,6 +524,60 @@ def mc_scores(samples: torch.Tensor, y: torch.Tensor, probs: Sequence[float], y_
     return sums
 
 
+def _crps_call(v: _LabelView, y_start, scale):
+    """the value call on the samples of ``v``: (scratch - kept for the gradient, so per call -, result (1 + out,))"""
+    dev = v.pred.device
+    need = C.c_size_t()
+    _lib.call("matgcn_crps_loss_bytes", v.b, v.out, C.byref(need))
+    scratch = torch.empty(need.value // 8, dtype=torch.float64, device=dev)
+    result = torch.empty(1 + v.out, dtype=torch.float32, device=dev)
+    _lib.call("matgcn_crps_loss", *v.args(y_start), *scale, scratch.data_ptr(), need.value, result.data_ptr(), _stream(dev))
+    return scratch, result
+
+
+def crps_loss_device(samples: torch.Tensor, labels: torch.Tensor, y_start: int = 0, mean: float = 0.0, std: float = 1.0,
+                     null_val: float = 0.0, min_s: float = 1e-4,
+                     label_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(1 + out,) tensor [the mean CRPS of the ensemble ``samples`` (S, B, out, N, od) over all unmasked elements, the same
+    per horizon] (matgcn_crps_loss): ``labels`` (the label windows, or with label_start the raw series), mask and geometry
+    as ``mc_scores``, whose CRPS sums it divides by their counts."""
+    v = _label_view(samples, labels, label_start, samples=True)
+    return _crps_call(v, y_start, (float(mean), float(std), float(null_val), float(min_s)))[1]
+
+
+class _CrpsLoss(torch.autograd.Function):
+    """the ensemble's mean CRPS with its gradient w.r.t. the samples (matgcn_crps_loss / matgcn_crps_loss_grad)"""
+
+    @staticmethod
+    def forward(ctx, samples, y, y_start, mean, std, null_val, min_s, label_start):
+        v = _label_view(samples.detach(), y, label_start, samples=True)
+        ctx.args = (int(y_start), (float(mean), float(std), float(null_val), float(min_s)))
+        scratch, result = _crps_call(v, *ctx.args)
+        ctx.view = v.save(ctx, scratch)
+        return result[0].clone()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        v, scratch = ctx.view.saved(ctx)
+        samples = v.pred
+        y_start, scale = ctx.args
+        # the gradient takes the place of the samples (a workgroup reads its tile completely before it writes it): no
+        # second (S, B, out, N, od) tensor.  The samples were made for this objective and nothing else reads them.
+        # (upstream stays on the device: reading it for the C argument would make the host wait for the stream)
+        _lib.call("matgcn_crps_loss_grad", *v.args(y_start), *scale, scratch.data_ptr(), scratch.numel() * 8, 1.0,
+                  samples.data_ptr(), _stream(samples.device))
+        return samples.mul_(upstream.detach().to(torch.float32)), None, None, None, None, None, None, None
+
+
+def crps_loss(samples: torch.Tensor, labels: torch.Tensor, y_start: int = 0, mean: float = 0.0, std: float = 1.0,
+              null_val: float = 0.0, min_s: float = 1e-4, label_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The scalar mean CRPS of the ensemble ``samples`` (S, B, out, N, od) with autograd support over the samples:
+    matgcn_crps_loss forward, matgcn_crps_loss_grad backward.  The backward writes the gradient IN PLACE of the samples
+    tensor - after it the tensor no longer holds the forecasts.  ``labels``: the label windows, or with label_start the
+    raw series."""
+    return _CrpsLoss.apply(samples, labels, y_start, mean, std, null_val, min_s, label_start)
+
+
 def mc_quantiles_scaled(samples: torch.Tensor, probs: Sequence[float], mean=None, std=None, group_mean=None,
                         group_std=None, clamp_min: float = float("nan")) -> torch.Tensor:
     """``mc_quantiles`` on the re-transformed scale (matgcn_mc_quantiles_scaled): ``samples`` (S, ..., N, od), every
@@ -1189,6 +1243,40 @@ class HotPath:
                        _ptr(kept), regrow=True)
         return (mean, std, kept) if keep_samples else (mean, std)
 
+    def _train_mc_buffer(self, samples: int) -> torch.Tensor:
+        """the train buffer of the ensemble step: matgcn_train_mc_bytes covers matgcn_train_bytes of every setting"""
+        nbytes = C.c_size_t()
+        _lib.call("matgcn_train_mc_bytes", C.byref(self.dims), int(samples), C.byref(nbytes))
+        if self._train is None or nbytes.value > self._train.numel() * 4:
+            self._train = self._buffer(nbytes.value)
+        return self._train
+
+    def forward_train_mc(self, x, dropout, samples: int, h0: Optional[torch.Tensor] = None,
+                         keep_stats: bool = False):
+        """matgcn_forward_train_mc: forward_train without dropout - the same saved activations - and the head over
+        ``samples`` masks, sample s drawn with (seed, offset + s, p) of ``dropout``.  Returns the (samples, B, out, N, od)
+        forecasts, with keep_stats (samples, mean, std).  The matching backward is backward_mc."""
+        xp, src, _keep = self._source(x)
+        h0 = self._h0(h0)
+        d = self._dropout(dropout)
+        if d is None:
+            raise _lib.MatgcnError("forward_train_mc needs dropout = (seed, offset, p)")
+        samples = int(samples)
+        self._need_prepared()
+        valid = 1 <= samples <= _lib.MAX_MC_SAMPLES      # (the library refuses the others; nothing is sized for them)
+        s = self.spec
+        kept = torch.empty((samples if valid else 1, self.batch, s.out_window, s.nodes, s.out_dim), dtype=torch.float32,
+                           device=self.device)
+        mean, std = (self._out(), self._out()) if keep_stats else (None, None)
+        with self._mode(self.lib.matgcn_set_train_precision), self._x3(), self._det():
+            if valid:
+                self._train_mc_buffer(samples)
+            else:
+                self._train_buffer()
+            self._call("matgcn_forward_train_mc", xp, src, _ptr(h0), C.byref(d), samples, _ptr(mean), _ptr(std),
+                       _ptr(kept), regrow=True, train=True)
+        return (kept, mean, std) if keep_stats else kept
+
     D_H0 = "__d_h0__"   # key of the initial-state gradient in backward()'s result
 
     def _grad_views(self, state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -1221,6 +1309,30 @@ class HotPath:
         drop_mask = self._mask(drop_mask)
         seeded = self._dropout(dropout, drop_mask)
         h0 = self._h0(h0)
+        name, drop = self._drop_variant("matgcn_backward", seeded, drop_mask)
+        return self._backward_call(name, (xp, src, _ptr(h0), drop, d_out.data_ptr()), state, h0)
+
+    def backward_mc(self, x, d_samples: torch.Tensor, state: Dict[str, torch.Tensor], dropout,
+                    h0: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """matgcn_backward_mc behind forward_train_mc (same x, dropout triple and h0): the gradients of ``backward`` summed
+        over the samples, from ``d_samples`` (samples, B, out, N, od) - the encoder's backward runs once."""
+        s = self.spec
+        xp, src, _keep = self._source(x)
+        if d_samples.dim() != 5:
+            raise _lib.MatgcnError("d_samples has shape %s, expected (S, B, out, N, od)" % (tuple(d_samples.shape),))
+        d_samples = _check_tensor(d_samples, "d_samples",
+                                  (d_samples.shape[0], self.batch, s.out_window, s.nodes, s.out_dim))
+        d = self._dropout(dropout)
+        if d is None:
+            raise _lib.MatgcnError("backward_mc needs the dropout = (seed, offset, p) of its forward_train_mc")
+        h0 = self._h0(h0)
+        return self._backward_call("matgcn_backward_mc", (xp, src, _ptr(h0), C.byref(d), int(d_samples.shape[0]),
+                                                          d_samples.data_ptr()), state, h0)
+
+    def _backward_call(self, entry: str, lead: tuple, state: Dict[str, torch.Tensor], h0) -> Dict[str, torch.Tensor]:
+        """What backward and backward_mc share: the gradient views and their routing, the call - entry point ``entry`` on
+        (*lead, grads, d_h0) - on the workspace and the train buffer as the forward left them."""
+        s = self.spec
         d_h0 = torch.empty_like(h0) if h0 is not None else None
         grads: Dict[str, torch.Tensor] = {}
         g = _lib.Params()
@@ -1252,11 +1364,9 @@ class HotPath:
             raise _lib.MatgcnError("backward() without a forward_train() before it")
         # the workspace and the train buffer as forward_train left them: no re-sizing here - a deterministic backward
         # behind a forward_train that ran without the setting reports MATGCN_ERR_SMALL_BUFFER
-        name, drop = self._drop_variant("matgcn_backward", seeded, drop_mask)
         with self._x3(), self._det():
-            status = self._status(name, (xp, src, _ptr(h0), drop, d_out.data_ptr(), C.byref(g), _ptr(d_h0)), *self._ws(),
-                                  train=True)
-        _lib.check(status, name)
+            status = self._status(entry, lead + (C.byref(g), _ptr(d_h0)), *self._ws(), train=True)
+        _lib.check(status, entry)
         if d_h0 is not None:
             grads[self.D_H0] = d_h0
         return grads
